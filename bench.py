@@ -13,6 +13,10 @@ Launch either way:
                                                                RANK / LOCAL_RANK / WORLD_SIZE variables are used)
 Neither path imports torch: barrier and max-over-ranks time go through RCCL (roam_comm_*), the ncclUniqueId through a
 rendezvous directory.  Rank 0 prints ONE JSON line with the `roofline` and `cpu_baseline` objects of DESIGN.md §5.
+A plain run does only what `value` needs: set-up, pre-roll and warm-up, the timed steps, the result line.  `--full` adds everything
+else the line can carry - the `roofline` and `cpu_baseline` objects, per-kernel and per-stage figures, the steady / retrack / endless
+/ single-sequence segments, the keyframe broadcast of a multi-rank run.  `--dump-outputs DIR` writes what the last timed step returned
+(rank 0's lanes) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 `--dry-engine` swaps the GPU engine for a stub (CPU test of this launcher; never a measurement).
 `--stream` measures ONE sequence instead (BASELINE configs 3 / 4 as the reference runs them): engine-only scan pairs/s of a single
 lane fed from a pinned ring, and its per-pair latency when every pose is awaited before the next frame is stepped."""
@@ -50,12 +54,12 @@ def parse_args(argv=None):
     ap.add_argument("--png", action="store_true", help="with --stream: also feed the sequence from PNG files (written first, untimed) - decode pool + H2D + step timed")
     ap.add_argument("--png-workers", type=int, default=0, help="host threads inflating PNGs ahead of the engine (0 = min(32, cores / 2))")
     ap.add_argument("--stream-start", type=int, default=280, help="first ground-truth motion of full_seq_1 used by --stream (the vehicle stands still for the first ~230 frames)")
-    ap.add_argument("--cpu-pairs", type=int, default=120, help="scan pairs timed on the CPU oracle, 1 core (0 = skip)")
-    ap.add_argument("--cpu-procs", type=int, default=-1, help="processes of the N-core CPU leg (-1 = half the logical cores, 0 = skip)")
+    ap.add_argument("--cpu-pairs", type=int, default=120, help="--full: scan pairs timed on the CPU oracle, 1 core (0 = skip)")
+    ap.add_argument("--cpu-procs", type=int, default=-1, help="--full: processes of the N-core CPU leg (-1 = half the logical cores, 0 = skip)")
     ap.add_argument("--no-md", action="store_true", help="motionDistortion OFF (Kabsch dead reckoning)")
     ap.add_argument("--no-retrack", action="store_true", help="round-1 workload: host-seeded features, no re-detection in the timed loop")
     ap.add_argument("--retrack-slots", type=int, default=0, help="lanes whose detection scratch is resident at once (0 = min(lanes, 2048))")
-    ap.add_argument("--kernel-reps", type=int, default=10)
+    ap.add_argument("--kernel-reps", type=int, default=10, help="--full: re-launches of each roofline candidate kernel alone")
     ap.add_argument("--h2d", action="store_true", help="stream every scan from pinned host memory over PCIe (double-buffered pool); reports the PCIe-inclusive rate")
     ap.add_argument("--engines", type=int, default=1, help="independent engine instances (contexts/streams) per GPU; lanes are split between them")
     ap.add_argument("--force-comm", action="store_true", help="create the RCCL communicator even at world size 1 (exercises the collective path on a 1-GPU box)")
@@ -63,9 +67,14 @@ def parse_args(argv=None):
                     "the keyframe exchange (roam_keyframe_exchange: one RCCL all-gather of fixed-size records) after EVERY step inside the loop, every rank "
                     "appending what it receives to its device-resident global map")
     ap.add_argument("--c5-frames", type=int, default=1000, help="scans per sequence of --config5")
-    ap.add_argument("--no-segments", action="store_true", help="skip the extra segments of the default run (endless ping-pong steps, single-sequence streaming)")
+    ap.add_argument("--no-segments", action="store_true", help="with --full: skip its extra segments (endless ping-pong steps, single-sequence streaming)")
+    ap.add_argument("--full", action="store_true", help="everything beside `value`: roofline (kernels re-launched alone), cpu_baseline, steady / retrack / "
+                    "endless / single-sequence segments, per-stage times, the keyframe broadcast of a multi-rank run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy")
     ap.add_argument("--dry-engine", action="store_true", help="CPU stub instead of the GPU engine: exercises launcher / rendezvous / reduction only")
     args = ap.parse_args(argv)
+    if args.dump_outputs and (args.stream or args.config5):
+        ap.error("--dump-outputs is for the batch run (not --stream / --config5)")
     if args.lanes is None:
         args.lanes = 1024 if args.h2d else 4096
     return args
@@ -254,6 +263,34 @@ def render_sequences(seeds, frames, md, work, procs):
         raise
 
 
+FEATURE_SAMPLE_LANES = 64
+
+
+def dump_outputs(d, engs, step, dry):
+    """--dump-outputs: what a caller of the timed path receives from its last step `step`, as DIR/<name>.npy (float64 / float32).
+    Every lane's result record (engines in lane order: pose, velocity, Kabsch R / h, counts, flags) and the tracked features the
+    step left behind in a fixed, seeded sample of FEATURE_SAMPLE_LANES lanes (rows concatenated in lane order; their lanes and counts
+    beside them).  4 096 lanes: < 1 MB."""
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    if dry:
+        res = [r for en in engs for r in en.results()]
+        for k in ("pose", "velocity", "n_tracked", "n_inliers", "lm_nfev"):
+            out[k] = np.array([r[k] for r in res], np.float64)
+    else:
+        rec = np.concatenate([en.results_array(step) for en in engs])
+        for k in rec.dtype.names:
+            out[k] = rec[k].astype(np.float64)
+        per = engs[0].lanes
+        lanes = np.sort(np.random.default_rng(20).choice(per * len(engs), size=min(FEATURE_SAMPLE_LANES, per * len(engs)), replace=False))
+        feats = [engs[b // per].lane_features(b % per) for b in lanes]
+        out["features_sample"] = np.concatenate(feats).astype(np.float32).reshape(-1, 2)
+        out["features_sample_lanes"] = lanes.astype(np.float64)
+        out["features_sample_counts"] = np.array([len(f) for f in feats], np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def run_rank(args):
     from radarslampy_amd import distributed as D
     rank, local_rank, world = D.rank_env()
@@ -288,7 +325,7 @@ def _run_rank(args, D, rank, local_rank, world, rdv):
         # the feature re-detection (DoH + ANMS) is part of the timed loop at the cadence the data dictates
         WORK = WORK_STEADY if args.no_retrack else WORK_RETRACK
         seqs = render_sequences([1000 * rank + 17 * d + 5 for d in range(Dn_)], T, not args.no_md, WORK, args.render_procs)
-        if rank == 0 and world == 1 and not (args.no_segments or args.no_retrack or args.h2d or args.no_md):
+        if args.full and rank == 0 and world == 1 and not (args.no_segments or args.no_retrack or args.h2d or args.no_md):
             stream_recs = stream_render(args, True)                # the --stream segment's records, before the GPU is touched
         from radarslampy_amd import _ffi
         from radarslampy_amd.engine import Engine
@@ -462,10 +499,12 @@ def _run_rank(args, D, rank, local_rank, world, rdv):
     for k in range(max(0, args.steps - 2), args.steps):
         consume(pre + args.warmup + k)
     res = eng.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engs, s - 1, args.dry_engine)
     # in-step kernel durations of the K timed steps (HIP event pairs recorded by the engine on the kernels' own streams), taken NOW:
     # the steady / forced segments below enqueue more steps
     live = None
-    if not args.dry_engine:
+    if args.full and not args.dry_engine:
         knames = ["ingest_peaks", "warp_quantise", "pyramid"] + ([] if args.no_retrack else ["doh_integral", "doh_det_maxima"])
         live = {k: eng.kernel_avg(k, args.steps)[0] for k in knames[:3]}
         if not args.no_retrack:
@@ -516,6 +555,7 @@ def _run_rank(args, D, rank, local_rank, world, rdv):
     kf_ms, comm_seen, map_seen = None, None, None
     if comm is not None:
         comm_seen = comm.info()
+    if comm is not None and args.full:
         if not args.dry_engine:
             eng.remote_map_reserve(max(8, 2 * world))
         comm.bcast_keyframe(eng, 0, 0)                                         # warm-up (channel setup)
@@ -534,7 +574,7 @@ def _run_rank(args, D, rank, local_rank, world, rdv):
 
     # steady vs retrack throughput beside the mix (after the timed region; single numbers of this rank)
     extra = {}
-    if not args.dry_engine and not args.no_retrack and not args.h2d:
+    if args.full and not args.dry_engine and not args.no_retrack and not args.h2d:
         stage_mix = eng.stage_times()
         for en in engs:
             en.set_retrack(2)                                   # every lane re-detects: the cost of a retrack pair
@@ -627,10 +667,11 @@ def _run_rank(args, D, rank, local_rank, world, rdv):
             "roofline": None, "cpu_baseline": None,
         }
         if not args.dry_engine:
+            out["config"]["whole_path_Bmin_GBs_per_gpu"] = round(13.07e6 * (value / world) / 1e9, 3)   # SURVEY 8d B_min per steady pair ONLY
+        if args.full and not args.dry_engine:
             out["config"].update(extra)
             if not extra:
                 out["config"]["stage_ms_last_step"] = {k: round(v, 4) for k, v in eng.stage_times().items()}
-            out["config"]["whole_path_Bmin_GBs_per_gpu"] = round(13.07e6 * (value / world) / 1e9, 3)   # SURVEY 8d B_min per steady pair ONLY
             # steady bytes of every scan + the strict bytes of every re-detection (polar payload + f64 integral image written, then read
             # once: 66.4 MB) over the step time: what the whole step moves algorithmically
             out["roofline"] = roofline(eng, args, B // max(1, len(engs)), out["config"].get("retrack_fraction") or 0.0, live)

@@ -9,6 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 ARGS = ["--dry-engine", "--steps", "4", "--warmup", "1", "--lanes", "8"]
+FULL = ARGS + ["--full"]                            # the multi-rank checks read the keyframe broadcast, a --full figure
 
 
 def _line(stdout):
@@ -38,7 +39,7 @@ def test_bench_single_process_dry():
 
 def test_bench_own_launcher_world2():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + ARGS, capture_output=True, text=True, timeout=120, env=env)
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + FULL, capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     _check(_line(r.stdout), 2, "bench.py --gpus")
 
@@ -46,7 +47,7 @@ def test_bench_own_launcher_world2():
 def test_bench_under_torch_distributed_run_world2():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29631", BENCH, "--gpus", "2"] + ARGS, capture_output=True, text=True, timeout=300, env=env)
+                        "--master-port", "29631", BENCH, "--gpus", "2"] + FULL, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     _check(_line(r.stdout), 2, "torch.distributed.run env")
 
@@ -56,9 +57,28 @@ def test_bench_under_torch_distributed_run_world8():
     one JSON line from rank 0 with n_gpus 8, every rank seen by the collective, every rank's keyframe in every rank's map"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                        "--master-port", "29651", BENCH, "--gpus", "8"] + ARGS, capture_output=True, text=True, timeout=300, env=env)
+                        "--master-port", "29651", BENCH, "--gpus", "8"] + FULL, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     _check(_line(r.stdout), 8, "torch.distributed.run env")
+
+
+def test_bench_dump_outputs_dry(tmp_path):
+    """--dump-outputs DIR: the last timed step's per-lane records as DIR/<name>.npy (float64), the same for two runs of the same arguments;
+    a plain run carries none of the --full figures"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, BENCH] + ARGS + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _line(r.stdout)
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["roofline"] is None and line["cpu_baseline"] is None
+        got = {f.name: np.load(f) for f in sorted(d.iterdir())}
+        assert {"pose.npy", "velocity.npy", "n_inliers.npy"} <= set(got)
+        assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+        assert got["pose.npy"].shape == (8, 3) and got["pose.npy"][0, 0] == 1 + 4          # the stub's pose counts the steps taken (warm-up + timed)
+        dumps.append(got)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
 
 
 def test_render_pool_is_shared_between_the_ranks_of_a_node(monkeypatch):
