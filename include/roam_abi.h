@@ -86,6 +86,19 @@ int32_t roam_peaks_polar_f32(roam_ctx *ctx, const float *polar, int32_t rows, in
 int32_t roam_peaks_record_u8(roam_ctx *ctx, const uint8_t *rec, int32_t rows, int64_t stride,
                              int32_t payload_off, int32_t clip, int32_t *out, int64_t cap,
                              int64_t *n_out);
+/* the same two with scipy.signal.find_peaks' distance / prominence conditions - getPointCloudPolarInd(polarImage, peakDistance,
+ * peakProminence) (getPointCloud.py:11-54, the find_peaks call at :33-35).  Per row, in find_peaks' order: local maxima; distance:
+ * d = ceil(distance), priority = np.argsort of the heights as NumPy 1.22.3 (the reference's pin) orders them, walked from the highest
+ * priority down, a kept peak suppresses every peak closer than d; prominence (wlen=None) of the survivors in float64, kept if
+ * prom_min <= prominence <= prom_max; then the reference's mean + std threshold.  distance == 0: no distance condition (any other
+ * value below 1 is ROAM_E_ARG; NaN suppresses nothing, as in find_peaks); a NaN bound is no bound, two NaN bounds no prominence condition; with no condition at all
+ * the call is roam_peaks_polar_f32 / roam_peaks_record_u8.  out, *n_out and the capacity rule as there. */
+int32_t roam_peaks_polar_f32_cond(roam_ctx *ctx, const float *polar, int32_t rows, int32_t cols,
+                                  double distance, double prom_min, double prom_max,
+                                  int32_t *out, int64_t cap, int64_t *n_out);
+int32_t roam_peaks_record_u8_cond(roam_ctx *ctx, const uint8_t *rec, int32_t rows, int64_t stride,
+                                  int32_t payload_off, int32_t clip, double distance, double prom_min,
+                                  double prom_max, int32_t *out, int64_t cap, int64_t *n_out);
 
 /* ---- a3: parseData.convertPolarImageToCartesian (parseData.py:100-135) -------------------
  * polar rows x cols f32 -> (2R x 2R), R = cols/2.  cart_f32 and/or cart_u8 may be NULL;

@@ -60,6 +60,10 @@ _SIGS = {
     "roam_png_pool_destroy": (C.c_int32, [_vp]),
     "roam_peaks_polar_f32": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int64, _P(C.c_int64)]),
     "roam_peaks_record_u8": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int64, _P(C.c_int64)]),
+    "roam_peaks_polar_f32_cond": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _vp, C.c_int64,
+                                              _P(C.c_int64)]),
+    "roam_peaks_record_u8_cond": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                              _vp, C.c_int64, _P(C.c_int64)]),
     "roam_polar_to_cart_f32": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_polar_to_cart_record_u8": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_klt_track_u8": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
@@ -120,6 +124,25 @@ _SIGS = {
     "roam_remote_map_get": (C.c_int32, [_vp, C.c_int32, _P(KeyframeHdr), _P(C.c_int32), _vp, C.c_int32, _vp, C.c_int64]),
 }
 ABI_SYMBOLS = tuple(_SIGS)
+
+
+def peak_conditions(distance=None, prominence=None):
+    """find_peaks' `distance` / `prominence` arguments as they are checked and unpacked there -> (distance, prom_min, prom_max) of
+    roam_peaks_*_cond: 0 = no distance condition, NaN = no bound.  distance < 1: ValueError, as find_peaks raises it.  prominence is
+    pmin or a 2-sequence (pmin, pmax), either entry None; per-sample (array) bounds are not supported: NotImplementedError."""
+    if distance is not None and distance < 1:
+        raise ValueError('`distance` must be greater or equal to 1')
+    pmin = pmax = None
+    if prominence is not None:
+        try:
+            pmin, pmax = prominence                  # scipy.signal._peak_finding._unpack_condition_args
+        except (TypeError, ValueError):
+            pmin, pmax = prominence, None
+        if isinstance(pmin, np.ndarray) or isinstance(pmax, np.ndarray):
+            raise NotImplementedError("per-sample (array-valued) prominence intervals are not supported")
+    nan = float("nan")
+    return (0.0 if distance is None else float(distance),
+            nan if pmin is None else float(pmin), nan if pmax is None else float(pmax))
 
 _lib = None
 
@@ -197,22 +220,32 @@ class Context:
             self.check(self.lib.roam_host_free(self.h, p))
 
     # ---- stage API -------------------------------------------------------------------
-    def peaks_polar_f32(self, polar):
+    def peaks_polar_f32(self, polar, distance=None, prominence=None):
+        """distance / prominence: find_peaks' conditions (peak_conditions); None, None = the plain detection"""
         img = np.ascontiguousarray(polar, np.float32)
         rows, cols = img.shape
         cap = rows * ((cols + 1) // 2)
         out = np.empty((cap, 2), np.int32)
         n = C.c_int64(0)
-        self.check(self.lib.roam_peaks_polar_f32(self.h, _ptr(img), rows, cols, _ptr(out), cap, C.byref(n)))
+        if distance is None and prominence is None:
+            self.check(self.lib.roam_peaks_polar_f32(self.h, _ptr(img), rows, cols, _ptr(out), cap, C.byref(n)))
+        else:
+            d, pmin, pmax = peak_conditions(distance, prominence)
+            self.check(self.lib.roam_peaks_polar_f32_cond(self.h, _ptr(img), rows, cols, d, pmin, pmax, _ptr(out), cap, C.byref(n)))
         return out[:n.value]
 
-    def peaks_record_u8(self, rec, payload_off=11, clip=2025):
+    def peaks_record_u8(self, rec, payload_off=11, clip=2025, distance=None, prominence=None):
         rec = np.ascontiguousarray(rec, np.uint8)
         rows, stride = rec.shape
         cap = rows * ((clip + 1) // 2)
         out = np.empty((cap, 2), np.int32)
         n = C.c_int64(0)
-        self.check(self.lib.roam_peaks_record_u8(self.h, _ptr(rec), rows, stride, payload_off, clip, _ptr(out), cap, C.byref(n)))
+        if distance is None and prominence is None:
+            self.check(self.lib.roam_peaks_record_u8(self.h, _ptr(rec), rows, stride, payload_off, clip, _ptr(out), cap, C.byref(n)))
+        else:
+            d, pmin, pmax = peak_conditions(distance, prominence)
+            self.check(self.lib.roam_peaks_record_u8_cond(self.h, _ptr(rec), rows, stride, payload_off, clip, d, pmin, pmax, _ptr(out),
+                                                          cap, C.byref(n)))
         return out[:n.value]
 
     def polar_to_cart_f32(self, polar, want_f32=True, want_u8=False):

@@ -1,6 +1,7 @@
 // C-ABI: context management + "stage" entry points (host arrays in / out, one reference
 // function each).  See include/roam_abi.h for the contract and the reference citations.
 #include "roam_internal.h"
+#include <cmath>
 #include <cstdlib>
 #include <new>
 
@@ -147,7 +148,8 @@ void *roam_scratch(roam_ctx *ctx, int slot, size_t bytes)
     if (!ctx) return ROAM_E_ARG;                  \
     HIP_TRY(ctx, hipSetDevice(ctx->device))
 
-static int32_t peaks_common(roam_ctx *ctx, PeakSrc src, int rows, int cols, int32_t *out, int64_t cap, int64_t *n_out)
+static int32_t peaks_common(roam_ctx *ctx, PeakSrc src, int rows, int cols, int32_t *out, int64_t cap, int64_t *n_out,
+                            const PeakCond *cond = nullptr)
 {
     const int stage_cap = (cols + 1) / 2;
     SCRATCH(stage, uint16_t, S_TMP0, sizeof(uint16_t) * (size_t)rows * stage_cap);
@@ -155,7 +157,10 @@ static int32_t peaks_common(roam_ctx *ctx, PeakSrc src, int rows, int cols, int3
     const int64_t dcap = (int64_t)rows * stage_cap;
     SCRATCH(dout, int32_t, S_OUT0, sizeof(int32_t) * 2 * (size_t)dcap);
     SCRATCH(dn, int32_t, S_OUT1, sizeof(int32_t));
-    HIP_TRY(ctx, launch_peaks(ctx->stream, src, 1, rows, cols, stage, stage_cap, rcount, dout, (int32_t)dcap, dn));
+    if (cond)
+        HIP_TRY(ctx, launch_peaks_cond(ctx->stream, src, 1, rows, cols, *cond, stage, stage_cap, rcount, dout, (int32_t)dcap, dn));
+    else
+        HIP_TRY(ctx, launch_peaks(ctx->stream, src, 1, rows, cols, stage, stage_cap, rcount, dout, (int32_t)dcap, dn));
     int32_t n = 0;
     D2H(&n, dn, sizeof(int32_t));
     SYNC();
@@ -188,6 +193,49 @@ extern "C" int32_t roam_peaks_record_u8(roam_ctx *ctx, const uint8_t *rec, int32
     H2D(din, rec, (size_t)rows * stride);
     PeakSrc src = {din, 0, stride, payload_off, 1, nullptr};
     return peaks_common(ctx, src, rows, clip, out, cap, n_out);
+}
+
+// distance 0 = no distance condition, else >= 1 (find_peaks' ValueError; a NaN distance passes its check and suppresses nothing there,
+// as d = 1 does here: two candidates are never adjacent); NaN prominence bounds = none.  false: no condition at all
+static bool peaks_cond_args(double distance, double prom_min, double prom_max, PeakCond *c, bool *bad)
+{
+    *bad = distance != 0.0 && distance < 1.0;
+    const double d = ceil(distance);
+    c->dist = distance == 0.0 ? 0 : std::isnan(d) ? 1 : (d < (double)(1 << 30) ? (int32_t)d : (1 << 30));
+    c->has_prom = !(std::isnan(prom_min) && std::isnan(prom_max));
+    c->prom_min = prom_min;
+    c->prom_max = prom_max;
+    return c->dist > 0 || c->has_prom;
+}
+
+extern "C" int32_t roam_peaks_polar_f32_cond(roam_ctx *ctx, const float *polar, int32_t rows, int32_t cols, double distance,
+                                             double prom_min, double prom_max, int32_t *out, int64_t cap, int64_t *n_out)
+{
+    ENTER();
+    PeakCond c;
+    bool bad;
+    const bool any = peaks_cond_args(distance, prom_min, prom_max, &c, &bad);
+    ARG_CHECK(ctx, !bad && polar && out && n_out && rows > 0 && cols >= 1 && cols <= ROAM_MAX_COLS && cap >= 0);
+    SCRATCH(din, float, S_IN0, sizeof(float) * (size_t)rows * cols);
+    H2D(din, polar, sizeof(float) * (size_t)rows * cols);
+    PeakSrc src = {din, 0, cols, 0, 0, nullptr};
+    return peaks_common(ctx, src, rows, cols, out, cap, n_out, any ? &c : nullptr);
+}
+
+extern "C" int32_t roam_peaks_record_u8_cond(roam_ctx *ctx, const uint8_t *rec, int32_t rows, int64_t stride, int32_t payload_off,
+                                             int32_t clip, double distance, double prom_min, double prom_max, int32_t *out,
+                                             int64_t cap, int64_t *n_out)
+{
+    ENTER();
+    PeakCond c;
+    bool bad;
+    const bool any = peaks_cond_args(distance, prom_min, prom_max, &c, &bad);
+    ARG_CHECK(ctx, !bad && rec && out && n_out && rows > 0 && clip >= 1 && clip <= ROAM_MAX_COLS && payload_off >= 0 &&
+                       stride >= payload_off + clip && cap >= 0);
+    SCRATCH(din, uint8_t, S_IN0, (size_t)rows * stride);
+    H2D(din, rec, (size_t)rows * stride);
+    PeakSrc src = {din, 0, stride, payload_off, 1, nullptr};
+    return peaks_common(ctx, src, rows, clip, out, cap, n_out, any ? &c : nullptr);
 }
 
 static int32_t warp_common(roam_ctx *ctx, WarpSrc src, int rows, int cols, float *cart_f32, uint8_t *cart_u8)

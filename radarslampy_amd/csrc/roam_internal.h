@@ -80,6 +80,18 @@ struct PeakSrc {
 // row_stage: B x rows x stage_cap u16; row_count: B x rows i32; out: B x cap x 2 i32; n_out: B i32
 hipError_t launch_peaks(hipStream_t st, PeakSrc src, int B, int rows, int cols, uint16_t *row_stage,
                         int stage_cap, int32_t *row_count, int32_t *out, int32_t cap, int32_t *n_out);
+// launch_peaks' second kernel alone (row_stage / row_count already filled)
+hipError_t launch_peaks_gather(hipStream_t st, int B, int rows, const uint16_t *row_stage, int stage_cap, const int32_t *row_count,
+                               int32_t *out, int32_t cap, int32_t *n_out);
+// find_peaks' distance / prominence conditions ahead of the threshold (peaks_cond.hip): dist = ceil(peakDistance), 0 = none;
+// has_prom = 0: no prominence condition, else prom_min <= prominence <= prom_max with NaN = no bound.  Same outputs as launch_peaks.
+struct PeakCond {
+    int32_t dist;
+    int32_t has_prom;
+    double prom_min, prom_max;
+};
+hipError_t launch_peaks_cond(hipStream_t st, PeakSrc src, int B, int rows, int cols, PeakCond cond, uint16_t *row_stage,
+                             int stage_cap, int32_t *row_count, int32_t *out, int32_t cap, int32_t *n_out);
 
 struct WarpSrc {
     const void *base;
