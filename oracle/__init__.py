@@ -628,14 +628,14 @@ TRANS_THRESHOLD_SQ = 4.0                     # Mapping.py:14-15
 class Keyframe:
     """Mapping.Keyframe (Mapping.py:21-125), fields the loop uses."""
 
-    def __init__(self, pose, featurePointsLocal, record_u8, velocity, with_peaks=True):
-        self.updateInfo(pose, featurePointsLocal, record_u8, velocity, with_peaks)
+    def __init__(self, pose, featurePointsLocal, record_u8, velocity, with_peaks=True, payload_off=11, clip=MAX_RANGE_CLIP_PX):
+        self.updateInfo(pose, featurePointsLocal, record_u8, velocity, with_peaks, payload_off, clip)
 
-    def updateInfo(self, pose, featurePointsLocal, record_u8, velocity, with_peaks=True):
+    def updateInfo(self, pose, featurePointsLocal, record_u8, velocity, with_peaks=True, payload_off=11, clip=MAX_RANGE_CLIP_PX):
         self.pose = np.asarray(pose, np.float64)
         self.featurePointsLocal = featurePointsLocal
         if with_peaks and record_u8 is not None:
-            self.pointCloud = peaks_from_record_u8(record_u8)               # Mapping.py:62
+            self.pointCloud = peaks_from_record_u8(record_u8, payload_off, clip)        # Mapping.py:62, in the record's own layout
         self.velocity = velocity
         self.prunedUndistortedLocals = MotionDistortionSolver.undistort(velocity, featurePointsLocal)[:, :2]
 
@@ -670,7 +670,7 @@ class OdometryPipeline:
         self.prevPyr = build_pyramid(self.prevCart8, 3)
         self.blobCoord = np.ascontiguousarray(init_features_xy, np.float32)
         metric = (self.blobCoord - RADAR_CART_CENTER) * RANGE_RESOLUTION_CART_M
-        self.old_kf = Keyframe(self.pose, metric, first_record_u8, np.zeros(3))
+        self.old_kf = Keyframe(self.pose, metric, first_record_u8, np.zeros(3), payload_off=self.off, clip=self.clip)
         self.last = {}
 
     def _cart_u8(self, rec):

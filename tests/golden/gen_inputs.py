@@ -140,3 +140,54 @@ def mds_problem(N: int, seed: int, yaw_per_frame: float, big: bool = False):
     Tinit = Tt @ _se2(rng.normal(0, 0.15), rng.normal(0, 0.15), rng.normal(0, 0.01))
     pose = np.array([Tt[0, 2], Tt[1, 2], np.arctan2(Tt[1, 0], Tt[0, 0])])
     return T0, p_w, p_jt, Tinit, np.hstack((v, pose))
+
+
+def layout_sequence(seed: int, n_frames: int, rows: int, clip: int, stride: int, payload_off: int, n_static: int = 320,
+                    n_movers: int = 0, scintillation: float = 0.0, distortion: bool = False):
+    """A synthetic sequence in another record layout: rows x stride bytes, `clip` power bins at `payload_off`, random metadata and
+    padding.  The Oxford world and trajectory of synth are shrunk by s = min(1, clip / 2025) (reflector and mover positions,
+    per-frame motion; not the movers' speed, so that they stay outliers to the clique's fixed 5.8 px), rendered as Oxford records,
+    and the first `clip` range bins are kept - an image of any size sees the whole shrunk world, with blobs as many bins wide as
+    in an Oxford record (resampling the range axis instead thins the 3-bin blobs away: at clip 132 the detector finds nothing).
+    Azimuth row i is rendered row floor(i * 400 / rows).  At clip = 2025, rows = 400 the power bytes are exactly those of synth.make_sequence.
+    -> (records list of (rows, stride) u8, poses (n, 3) in the shrunk world's metres)"""
+    from radarslampy_amd import synth
+    s = min(1.0, clip / 2025.0)
+    world = synth.World(seed, max(48, int(round(n_static * s))) if s < 1 else n_static, n_movers)
+    world.static = world.static * s
+    world.movers = world.movers * s
+    poses = synth.trajectory(n_frames, seed, speed_m=(0.8 * s, 1.6 * s))
+    src_rows = (np.arange(rows) * 400) // rows
+    rng = np.random.default_rng(seed + 104729)
+    recs = []
+    for t in range(n_frames):
+        vel = None
+        if distortion and t > 0:
+            d = np.linalg.inv(synth.se2(*poses[t - 1])) @ synth.se2(*poses[t])
+            vel = np.array([d[0, 2], d[1, 2], np.arctan2(d[1, 0], d[0, 0])]) / 0.25
+        ox = synth.render_record(world, poses[t], t, vel, scintillation=scintillation)
+        rec = rng.integers(0, 256, size=(rows, stride), dtype=np.uint8)
+        rec[:, payload_off:payload_off + clip] = ox[np.ix_(src_rows, synth.META + np.arange(clip))]
+        recs.append(rec)
+    return recs, poses
+
+
+# Engine record layouts beyond the Oxford one: (clip, rows, stride, payload_off).  The Cartesian image is W = 2 * (clip // 2) on a
+# side, and W picks the kernel of every pyramid level (csrc/pyrklt.hip launch_build_pyramid / launch_pyr_down; the branch each
+# level takes is restated and checked in tests/test_pyramid_dispatch_model.py).
+ENGINE_LAYOUTS = [
+    (2025, 400, 3779, 11),      # the Oxford layout: the control
+    (132, 400, 132, 0),
+    (497, 399, 504, 5),
+    (1000, 64, 1000, 0),
+    (1024, 400, 1027, 1),
+    (1028, 400, 1028, 0),
+    (1032, 1020, 1032, 0),
+    (2048, 400, 2048, 0),
+    (2052, 400, 2052, 0),
+    (3768, 400, 3779, 11),      # the unclipped Oxford record
+]
+
+# standalone tracker image sizes (h, w): the engine's W as squares, and non-square images whose levels end on odd rows / columns
+KLT_SIZES = [(2 * (c // 2),) * 2 for c, _, _, _ in ENGINE_LAYOUTS if c != 2025] + [
+    (300, 700), (700, 300), (130, 1024), (1024, 130), (1000, 129), (129, 1000), (517, 2049), (2049, 517), (300, 4000)]
