@@ -172,11 +172,24 @@ int32_t roam_doh_maxima(roam_ctx *ctx, const float *img, int32_t w, int32_t h, c
                         int32_t num_sigma, double threshold, int32_t *out_rcs, double *out_val,
                         int32_t cap, int32_t *n_out);
 
+/* ---- getFeatures.getBlobsFromCart(method="log") (skimage blob_log, getFeatures.py:22-53) -------------------------------
+ * image-scale part of blob_log: per sigma s, the float64 layer -gaussian_laplace(img, s) * scale[s] (scipy.ndimage: separable
+ * correlations, mode 'reflect', symmetric-kernel arithmetic), then the 3x3x3 maxima of the (row, col, sigma) cube above
+ * `threshold` (peak_local_max: outside the cube counts as 0; no peaks in a trivial cube).  img w x h, f32 (img_bytes_per_px 4,
+ * widened exactly) or f64 (8).  radius[s] in [0, 800]; kernels = for each s the order-0 then the order-2 weights of
+ * scipy's gaussian_filter1d (2 radius[s] + 1 each, symmetric; the caller computes them); scale[s] = sigma^2.
+ * out_rcs (cap,3) int32 [row, col, sigma_index] in C order, out_val (cap) the layer values; beyond cap ROAM_E_CAPACITY with the
+ * true count in n_out.  out_layers (optional, may be NULL): num_sigma x h x w f64, the layers. */
+int32_t roam_log_maxima(roam_ctx *ctx, const void *img, int32_t img_bytes_per_px, int32_t w, int32_t h, int32_t num_sigma,
+                        const int32_t *radius, const double *kernels, const double *scale, double threshold, int32_t *out_rcs,
+                        double *out_val, int32_t cap, int32_t *n_out, double *out_layers);
+
 /* ---- a4/a5 bookkeeping whose ORDER the reference's pinned third-party stack fixes (host code, no GPU; the engine's
  * device-side retrack runs the same functions on the GPU):
- * roam_prune_blobs   = skimage.feature.blob._prune_blobs as blob_doh calls it (getFeatures.py:47-51): candidate pairs in the
- *                      iteration order of the Python set that scipy cKDTree.query_pairs fills.  blobs (n,3) f64 rows
- *                      [row, col, sigma] in peak_local_max order, integer rows / cols; keep_out (n) u8.
+ * roam_prune_blobs   = skimage.feature.blob._prune_blobs as blob_doh / blob_log call it (getFeatures.py:47-51): candidate pairs in
+ *                      the iteration order of the Python set that scipy cKDTree.query_pairs fills.  blobs (n,3) f64 rows
+ *                      [row, col, sigma] in peak_local_max order, integer rows / cols in [0, 32767]; keep_out (n) u8.  Any
+ *                      number of points and pairs (beyond 32767 of either: a 32-bit host instantiation of the same code).
  * roam_argsort_np122 = np.argsort of the pinned NumPy 1.22.3 (unstable introsort) that adaptiveNMS applies to the
  *                      two-valued sigmas (getFeatures.py:69); order_out (n) i32. */
 int32_t roam_prune_blobs(const double *blobs, int32_t n, double overlap, uint8_t *keep_out);

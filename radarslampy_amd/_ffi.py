@@ -77,6 +77,8 @@ _SIGS = {
     "roam_mds_undistort": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_double, _vp, _vp]),
     "roam_ssc": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, _vp, _P(C.c_int32)]),
     "roam_doh_maxima": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_double, _vp, _vp, C.c_int32, _P(C.c_int32)]),
+    "roam_log_maxima": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_double, _vp, _vp, C.c_int32,
+                                    _P(C.c_int32), _vp]),
     "roam_engine_create": (C.c_int32, [_vp, _P(EngineCfg)]),
     "roam_engine_destroy": (C.c_int32, [_vp]),
     "roam_engine_upload_scan": (C.c_int32, [_vp, C.c_int32, _vp]),
@@ -371,6 +373,34 @@ class Context:
         self.check(self.lib.roam_doh_maxima(self.h, _ptr(img), w, h, _ptr(sig), len(sig), float(threshold), _ptr(rcs),
                                             _ptr(val), cap, C.byref(n)))
         return rcs[:n.value], val[:n.value]
+
+    def log_maxima(self, img, sigma_list, threshold, want_layers=False, cap=1 << 17):
+        """Laplacian-of-Gaussian scale space of blob_log and its 3x3x3 maxima.  img: f32 (widened exactly on the device) or
+        f64; anything else is converted to f64 first.  sigma_list: scalar sigmas.  -> (rcs (n,3) int32 [row, col, sigma_index]
+        in C order, values (n,) f64[, layers (num_sigma, h, w) f64 = -gaussian_laplace(img, s) * s**2])"""
+        from .gaussian import laplace_kernels
+        img = np.asarray(img)
+        img = np.ascontiguousarray(img, np.float32 if img.dtype == np.float32 else np.float64)
+        h, w = img.shape
+        sig = np.asarray(sigma_list, np.float64).reshape(-1)
+        ks = [laplace_kernels(s) for s in sig]
+        radius = np.array([k[0] for k in ks], np.int32)
+        kernels = np.ascontiguousarray(np.concatenate([np.concatenate([k0, k2]) for _, k0, k2 in ks]), np.float64)
+        scale = np.array([s * s for s in sig], np.float64)
+        layers = np.empty((len(sig), h, w), np.float64) if want_layers else None
+        for attempt in range(2):
+            rcs = np.empty((max(cap, 1), 3), np.int32)
+            val = np.empty(max(cap, 1), np.float64)
+            n = C.c_int32(0)
+            rc = self.lib.roam_log_maxima(self.h, _ptr(img), img.itemsize, w, h, len(sig), _ptr(radius), _ptr(kernels), _ptr(scale),
+                                          float(threshold), _ptr(rcs), _ptr(val), cap, C.byref(n), _ptr(layers))
+            if rc == ROAM_E_CAPACITY and attempt == 0:
+                cap = n.value
+                continue
+            self.check(rc)
+            break
+        out = (rcs[:n.value], val[:n.value])
+        return out + (layers,) if want_layers else out
 
 
 _default = {}

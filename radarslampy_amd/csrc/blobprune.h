@@ -33,8 +33,12 @@
 #define BP_MAX_PAIRS 32767       // pair indices are stored +1 in 16-bit set tables
 #define BP_LDS_PAIRS 4914        // below this count the set never grows past 8192 entries (LDS fast path)
 
-struct BpNode { int32_t split; int16_t split_dim, start, end, less, greater; };
-struct BpTask { int16_t a, b; int32_t mode; };            // leaf a x leaf b; mode 1 = every pair (no distance test)
+// NI / TI: index types of nodes and tasks.  int16_t for the device retrack (its LDS layout) and the host path within the limits
+// above; int32_t for the host-only wide instantiation (roam_prune_blobs beyond 32767 points or pairs)
+template <typename NI> struct BpNodeT { int32_t split; NI split_dim, start, end, less, greater; };
+template <typename TI> struct BpTaskT { TI a, b; int32_t mode; };   // leaf a x leaf b; mode 1 = every pair (no distance test)
+typedef BpNodeT<int16_t> BpNode;
+typedef BpTaskT<int16_t> BpTask;
 
 // ------------------------------------------------------------------------------------------------ nth_element
 // libstdc++ std::nth_element (introselect) on an index array, comparator = coordinate value only (scipy's)
@@ -122,10 +126,10 @@ BP_HDN void bp_nth_element(IDX *idx, int first, int nth, int last, const int16_t
 // stack: caller-provided scratch of 3 * 64 ints; node_cap: capacity of nodes (BP_MAX_NODES in LDS on the device).
 // one node of the build: bounds, split dimension, median split with scipy's partition passes.  Returns the first index of the
 // "greater" half (the node is split into [start, p) and [p, end)) or -1 for a leaf; nd receives split_dim / split.
-template <typename IDX>
-BP_HDN int bp_build_node(const int16_t *xy, IDX *idx, int start, int end, BpNode &nd)
+template <typename IDX, typename NI>
+BP_HDN int bp_build_node(const int16_t *xy, IDX *idx, int start, int end, BpNodeT<NI> &nd)
 {
-    nd.start = (int16_t)start; nd.end = (int16_t)end; nd.less = nd.greater = -1; nd.split_dim = -1; nd.split = 0;
+    nd.start = (NI)start; nd.end = (NI)end; nd.less = nd.greater = -1; nd.split_dim = -1; nd.split = 0;
     if (end - start <= BP_LEAF) return -1;
     int mx0 = bp_key(idx[start], xy, 0), mn0 = mx0, mx1 = bp_key(idx[start], xy, 1), mn1 = mx1;   // compact_nodes bounds
     for (int j = start + 1; j < end; j++) {
@@ -157,12 +161,12 @@ BP_HDN int bp_build_node(const int16_t *xy, IDX *idx, int start, int end, BpNode
         IDX t = idx[end - 1]; idx[end - 1] = idx[j]; idx[j] = t;
         p = end - 1;
     }
-    nd.split_dim = (int16_t)d; nd.split = split;
+    nd.split_dim = (NI)d; nd.split = split;
     return p;
 }
 
-template <typename IDX>
-BP_HDN int bp_build(const int16_t *xy, int n, IDX *idx, BpNode *nodes, int node_cap, int *stack)
+template <typename IDX, typename NI>
+BP_HDN int bp_build(const int16_t *xy, int n, IDX *idx, BpNodeT<NI> *nodes, int node_cap, int *stack)
 {
     for (int i = 0; i < n; i++) idx[i] = (IDX)i;
     int nn = 0, sp = 0;
@@ -172,8 +176,8 @@ BP_HDN int bp_build(const int16_t *xy, int n, IDX *idx, BpNode *nodes, int node_
         const int start = stack[3 * sp], end = stack[3 * sp + 1], link = stack[3 * sp + 2];
         if (nn >= node_cap) return -1;
         const int me = nn++;
-        if (link >= 0) { if (link & 1) nodes[link >> 1].greater = (int16_t)me; else nodes[link >> 1].less = (int16_t)me; }
-        BpNode nd;
+        if (link >= 0) { if (link & 1) nodes[link >> 1].greater = (NI)me; else nodes[link >> 1].less = (NI)me; }
+        BpNodeT<NI> nd;
         const int p = bp_build_node(xy, idx, start, end, nd);
         if (p >= 0) {
             if (sp + 2 > 64) return -1;
@@ -233,7 +237,9 @@ enum { BP_CHECK = 0, BP_NOCHECK = 1, BP_PUSH = 2, BP_POP = 3 };
 #define BP_ST(o, x, y) do { if (sp >= cap) return -1; st[3 * sp] = (o); st[3 * sp + 1] = (x); st[3 * sp + 2] = (y); sp++; } while (0)
 
 // tasks: leaf x leaf blocks in emission order.  st: scratch of 3 * cap ints.  returns the task count or -1 on overflow.
-BP_HDN int bp_tasks(const int16_t *xy, int n, const BpNode *nodes, double r, BpTask *tasks, int task_cap, int *st, int cap, BpTracker &tr)
+template <typename NI, typename TI>
+BP_HDN int bp_tasks(const int16_t *xy, int n, const BpNodeT<NI> *nodes, double r, BpTaskT<TI> *tasks, int task_cap, int *st, int cap,
+                    BpTracker &tr)
 {
     int mn0 = xy[0], mx0 = mn0, mn1 = xy[1], mx1 = mn1;
     for (int i = 1; i < n; i++) {
@@ -256,10 +262,10 @@ BP_HDN int bp_tasks(const int16_t *xy, int n, const BpNode *nodes, double r, BpT
             bp_tpush(tr, a & 1 ? 1 : 2, (a >> 1) & 1, nodes[b].split_dim, (double)nodes[b].split);
             continue;
         }
-        const BpNode &n1 = nodes[a], &n2 = nodes[b];
+        const BpNodeT<NI> &n1 = nodes[a], &n2 = nodes[b];
         const bool l1 = n1.split_dim == -1, l2 = n2.split_dim == -1;
         if (op == BP_NOCHECK) {
-            if (l1 && l2) { if (nt >= task_cap) return -1; tasks[nt].a = (int16_t)a; tasks[nt].b = (int16_t)b; tasks[nt].mode = 1; nt++; }
+            if (l1 && l2) { if (nt >= task_cap) return -1; tasks[nt].a = (TI)a; tasks[nt].b = (TI)b; tasks[nt].mode = 1; nt++; }
             else if (l1) { BP_ST(BP_NOCHECK, a, n2.greater); BP_ST(BP_NOCHECK, a, n2.less); }
             else if (a == b) { BP_ST(BP_NOCHECK, n1.greater, n2.greater); BP_ST(BP_NOCHECK, n1.less, n2.greater); BP_ST(BP_NOCHECK, n1.less, n2.less); }
             else { BP_ST(BP_NOCHECK, n1.greater, b); BP_ST(BP_NOCHECK, n1.less, b); }
@@ -268,7 +274,7 @@ BP_HDN int bp_tasks(const int16_t *xy, int n, const BpNode *nodes, double r, BpT
         if (tr.mind > tr.ub) continue;
         if (tr.maxd < tr.ub) { BP_ST(BP_NOCHECK, a, b); continue; }
         // which | less<<1 encodings: box 1 less = 3, box 1 greater = 1, box 2 less = 2, box 2 greater = 0
-        if (l1 && l2) { if (nt >= task_cap) return -1; tasks[nt].a = (int16_t)a; tasks[nt].b = (int16_t)b; tasks[nt].mode = 0; nt++; }
+        if (l1 && l2) { if (nt >= task_cap) return -1; tasks[nt].a = (TI)a; tasks[nt].b = (TI)b; tasks[nt].mode = 0; nt++; }
         else if (l1) {
             BP_ST(BP_POP, 0, 0); BP_ST(BP_CHECK, a, n2.greater); BP_ST(BP_PUSH, 0, b);
             BP_ST(BP_POP, 0, 0); BP_ST(BP_CHECK, a, n2.less); BP_ST(BP_PUSH, 2, b);
@@ -292,37 +298,48 @@ BP_HDN int bp_tasks(const int16_t *xy, int n, const BpNode *nodes, double r, BpT
 
 // pair (i < j) packed as i << 16 | j
 BP_HD uint32_t bp_pack(int i, int j) { return i < j ? ((uint32_t)i << 16) | (uint32_t)j : ((uint32_t)j << 16) | (uint32_t)i; }
+// the wide form: i << 32 | j
+BP_HD void bp_pack_to(uint32_t &o, int i, int j) { o = bp_pack(i, j); }
+BP_HD void bp_pack_to(uint64_t &o, int i, int j)
+{
+    o = i < j ? ((uint64_t)(uint32_t)i << 32) | (uint32_t)j : ((uint64_t)(uint32_t)j << 32) | (uint32_t)i;
+}
 
 // sequential expansion of the tasks (host; the device does the same with ballots over 64 candidates at a time)
-template <typename IDX>
-inline int bp_expand(const int16_t *xy, const IDX *idx, const BpNode *nodes, const BpTask *tasks, int nt, double ub, uint32_t *pairs, int cap)
+template <typename IDX, typename NI, typename TI, typename PAIR>
+inline int bp_expand(const int16_t *xy, const IDX *idx, const BpNodeT<NI> *nodes, const BpTaskT<TI> *tasks, int nt, double ub, PAIR *pairs,
+                     int cap)
 {
     int np = 0;
     for (int t = 0; t < nt; t++) {
-        const BpNode &n1 = nodes[tasks[t].a], &n2 = nodes[tasks[t].b];
+        const BpNodeT<NI> &n1 = nodes[tasks[t].a], &n2 = nodes[tasks[t].b];
         for (int i = n1.start; i < n1.end; i++)
             for (int j = (tasks[t].a == tasks[t].b ? i + 1 : n2.start); j < n2.end; j++) {
                 const int pi = idx[i], pj = idx[j];
                 const double d0 = (double)xy[2 * pi] - (double)xy[2 * pj], d1 = (double)xy[2 * pi + 1] - (double)xy[2 * pj + 1];
-                if (tasks[t].mode || d0 * d0 + d1 * d1 <= ub) { if (np >= cap) return -1; pairs[np++] = bp_pack(pi, pj); }
+                if (tasks[t].mode || d0 * d0 + d1 * d1 <= ub) { if (np >= cap) return -1; bp_pack_to(pairs[np++], pi, pj); }
             }
     }
     return np;
 }
 
 // ------------------------------------------------------------------------------------------------ CPython set order
-BP_HD uint64_t bp_tuple_hash(uint32_t packed)
+// hash((i, j)) of CPython >= 3.8 (hash(int) = the int itself below 2**61 - 1)
+BP_HD uint64_t bp_tuple_hash_ij(uint64_t i, uint64_t j)
 {
     const uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL, P5 = 2870177450012600261ULL;
     uint64_t acc = P5;
-    acc += (uint64_t)(packed >> 16) * P2; acc = (acc << 31) | (acc >> 33); acc *= P1;
-    acc += (uint64_t)(packed & 0xffffu) * P2; acc = (acc << 31) | (acc >> 33); acc *= P1;
+    acc += i * P2; acc = (acc << 31) | (acc >> 33); acc *= P1;
+    acc += j * P2; acc = (acc << 31) | (acc >> 33); acc *= P1;
     acc += 2ULL ^ (P5 ^ 3527539ULL);
     return acc == ~0ULL ? 1546275796ULL : acc;
 }
+BP_HD uint64_t bp_tuple_hash(uint32_t packed) { return bp_tuple_hash_ij(packed >> 16, packed & 0xffffu); }
+BP_HD uint64_t bp_tuple_hash(uint64_t packed) { return bp_tuple_hash_ij(packed >> 32, packed & 0xffffffffu); }
 
 // first free slot of key's probe sequence (set_add_entry / set_insert_clean: the keys are distinct, so no compare)
-BP_HD void bp_set_put(uint16_t *tab, uint32_t mask, uint64_t hash, uint16_t key1)
+template <typename TE>
+BP_HD void bp_set_put(TE *tab, uint32_t mask, uint64_t hash, TE key1)
 {
     uint64_t perturb = hash;
     uint32_t i = (uint32_t)hash & mask;
@@ -338,17 +355,18 @@ BP_HD void bp_set_put(uint16_t *tab, uint32_t mask, uint64_t hash, uint16_t key1
 // order (np) = indices into pairs in the iteration order of the Python set built by adding them in sequence.
 // tabA / tabB: ping-pong tables; capacities (entries) capA >= 2048 and capB >= 8192 suffice for np <= BP_LDS_PAIRS,
 // both >= 131072 for np <= BP_MAX_PAIRS.  Tables hold pair index + 1 (0 = empty).  returns np, or -1 if a table is too small.
-template <typename ORD>
-BP_HDN int bp_pyset_order(const uint32_t *pairs, int np, uint16_t *tabA, int capA, uint16_t *tabB, int capB, ORD *order)
+// PAIR / TE: uint32_t / uint16_t (pair indices < 32767), uint64_t / uint32_t in the host-only wide instantiation.
+template <typename PAIR, typename TE, typename ORD>
+BP_HDN int bp_pyset_order(const PAIR *pairs, int np, TE *tabA, int capA, TE *tabB, int capB, ORD *order)
 {
-    uint16_t *tab = tabA;
+    TE *tab = tabA;
     int cap_cur = capA, cap_other = capB;
-    uint16_t *other = tabB;
+    TE *other = tabB;
     uint32_t mask = 7;
     for (int k = 0; k < 8; k++) tab[k] = 0;
     int fill = 0;
     for (int p = 0; p < np; p++) {
-        bp_set_put(tab, mask, bp_tuple_hash(pairs[p]), (uint16_t)(p + 1));
+        bp_set_put(tab, mask, bp_tuple_hash(pairs[p]), (TE)(p + 1));
         fill++;
         if ((uint64_t)fill * 5 >= (uint64_t)mask * 3) {
             const int minused = fill > 50000 ? fill * 2 : fill * 4;
@@ -358,7 +376,7 @@ BP_HDN int bp_pyset_order(const uint32_t *pairs, int np, uint16_t *tabA, int cap
             for (uint32_t k = 0; k < newsize; k++) other[k] = 0;
             for (uint32_t k = 0; k <= mask; k++)
                 if (tab[k]) bp_set_put(other, newsize - 1, bp_tuple_hash(pairs[tab[k] - 1]), tab[k]);
-            uint16_t *t = tab; tab = other; other = t;
+            TE *t = tab; tab = other; other = t;
             const int c = cap_cur; cap_cur = cap_other; cap_other = c;
             mask = newsize - 1;
         }

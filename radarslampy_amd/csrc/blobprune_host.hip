@@ -6,17 +6,95 @@
 #include <vector>
 #include "blobprune.h"
 
+// the pass of _prune_blobs over the pairs in set order, with the ORIGINAL sigmas for the overlap test
+template <typename PAIR, typename ORD>
+static void prune_pass(const double *blobs, int n, double overlap, const PAIR *pairs, const ORD *order, int np, int shift, uint8_t *keep_out)
+{
+    std::vector<double> sig(n);
+    for (int i = 0; i < n; i++) sig[i] = blobs[3 * i + 2];
+    const PAIR lo = (PAIR)(((PAIR)1 << shift) - 1);
+    for (int k = 0; k < np; k++) {
+        const PAIR pr = pairs[order[k]];
+        const int i = (int)(pr >> shift), j = (int)(pr & lo);
+        if (sig[i] == 0 || sig[j] == 0) continue;           // a pruned member: the reference's pass changes nothing
+        if (bp_overlaps(blobs[3 * i], blobs[3 * i + 1], sig[i], blobs[3 * j], blobs[3 * j + 1], sig[j], overlap)) {
+            if (sig[i] > sig[j]) sig[j] = 0; else sig[i] = 0;
+        }
+    }
+    for (int i = 0; i < n; i++) keep_out[i] = sig[i] > 0;
+}
+
+// beyond 32767 points or pairs (LoG candidates of a whole scan: tens of thousands of points, millions of pairs): the same
+// algorithms of blobprune.h instantiated with 32-bit point / node / task indices, 64-bit pair keys and 32-bit set tables
+static int32_t prune_blobs_wide(const double *blobs, int n, double overlap, const int16_t *xy, double distance, uint8_t *keep_out)
+{
+    std::vector<int32_t> idx(n);
+    const int node_cap = 2 * n + 8;
+    std::vector<BpNodeT<int32_t>> nodes(node_cap);
+    int stack[3 * 64];
+    const int nn = bp_build(xy, n, idx.data(), nodes.data(), node_cap, stack);
+    if (nn < 0) return ROAM_E_CAPACITY;
+    std::vector<BpTaskT<int32_t>> tasks;
+    std::vector<int> st(3 * 65536);
+    BpTracker tr;
+    int nt = -1;
+    for (int64_t cap = 64 * (int64_t)nn + 64; nt < 0 && cap <= (1 << 26); cap *= 4) {
+        tasks.resize(cap);
+        nt = bp_tasks(xy, n, nodes.data(), distance, tasks.data(), (int)cap, st.data(), 65536, tr);
+    }
+    if (nt < 0) return ROAM_E_CAPACITY;
+    std::vector<uint64_t> pairs;
+    int np = -1;
+    for (int64_t cap = 16 * (int64_t)n + 1024; np < 0 && cap <= INT32_MAX / 8; cap *= 4) {
+        pairs.resize(cap);
+        np = bp_expand(xy, idx.data(), nodes.data(), tasks.data(), nt, tr.ub, pairs.data(), (int)cap);
+    }
+    if (np < 0) return ROAM_E_CAPACITY;
+    int64_t tcap = 8;                                       // a power of two above the largest table the set reaches
+    while (tcap <= 4 * (int64_t)np) tcap <<= 1;
+    std::vector<uint32_t> tabA(tcap), tabB(tcap);
+    std::vector<int32_t> order(np > 0 ? np : 1);
+    if (bp_pyset_order(pairs.data(), np, tabA.data(), (int)tcap, tabB.data(), (int)tcap, order.data()) != np) return ROAM_E_CAPACITY;
+    prune_pass(blobs, n, overlap, pairs.data(), order.data(), np, 32, keep_out);
+    return ROAM_OK;
+}
+
+// the 16-bit form: pair keys i << 16 | j, 16-bit set tables
+static int32_t prune_blobs_narrow(const double *blobs, int n, double overlap, const int16_t *xy, double distance, uint8_t *keep_out)
+{
+    std::vector<int16_t> idx(n);
+    const int node_cap = 2 * n + 8;
+    std::vector<BpNode> nodes(node_cap);
+    int stack[3 * 64];
+    const int nn = bp_build(xy, n, idx.data(), nodes.data(), node_cap, stack);
+    if (nn < 0) return ROAM_E_CAPACITY;
+    const int task_cap = 64 * nn + 64;
+    std::vector<BpTask> tasks(task_cap);
+    std::vector<int> st(3 * 1024);
+    BpTracker tr;
+    const int nt = bp_tasks(xy, n, nodes.data(), distance, tasks.data(), task_cap, st.data(), 1024, tr);
+    if (nt < 0) return ROAM_E_CAPACITY;
+    std::vector<uint32_t> pairs(BP_MAX_PAIRS);
+    const int np = bp_expand(xy, idx.data(), nodes.data(), tasks.data(), nt, tr.ub, pairs.data(), BP_MAX_PAIRS);
+    if (np < 0) return ROAM_E_CAPACITY;
+    std::vector<uint16_t> tabA(131072), tabB(131072);
+    std::vector<uint16_t> order(np > 0 ? np : 1);
+    if (bp_pyset_order(pairs.data(), np, tabA.data(), 131072, tabB.data(), 131072, order.data()) != np) return ROAM_E_CAPACITY;
+    prune_pass(blobs, n, overlap, pairs.data(), order.data(), np, 16, keep_out);
+    return ROAM_OK;
+}
+
 extern "C" {
 
-// skimage.feature.blob._prune_blobs (reference getFeatures.py:47-51 via blob_doh), pair order included.
+// skimage.feature.blob._prune_blobs (reference getFeatures.py:47-51 via blob_doh / blob_log), pair order included.
 // blobs (n,3) f64 rows [row, col, sigma] in peak_local_max order; rows / cols integer valued in [0, 32767].
-// keep_out (n) u8 = 1 for the surviving blobs.  No GPU involved.
+// keep_out (n) u8 = 1 for the surviving blobs.  No GPU involved.  Up to 32767 points and pairs the 16-bit form (the device
+// retrack's); above, the wide form.
 int32_t roam_prune_blobs(const double *blobs, int32_t n, double overlap, uint8_t *keep_out)
 {
     if (n < 0 || (n > 0 && (!blobs || !keep_out))) return ROAM_E_ARG;
     if (n == 0) return ROAM_OK;
-    if (n > 32767) return ROAM_E_CAPACITY;
-    std::vector<int16_t> xy(2 * (size_t)n), idx(n);
+    std::vector<int16_t> xy(2 * (size_t)n);
     double smax = blobs[2];
     for (int i = 0; i < n; i++) {
         const double r = blobs[3 * i], c = blobs[3 * i + 1];
@@ -25,35 +103,8 @@ int32_t roam_prune_blobs(const double *blobs, int32_t n, double overlap, uint8_t
         smax = blobs[3 * i + 2] > smax ? blobs[3 * i + 2] : smax;
     }
     const double distance = 2 * smax * sqrt(2.0);
-    const int node_cap = 2 * n + 8;
-    std::vector<BpNode> nodes(node_cap);
-    int stack[3 * 64];
-    const int nn = bp_build(xy.data(), n, idx.data(), nodes.data(), node_cap, stack);
-    if (nn < 0) return ROAM_E_CAPACITY;
-    const int task_cap = 64 * nn + 64;
-    std::vector<BpTask> tasks(task_cap);
-    std::vector<int> st(3 * 1024);
-    BpTracker tr;
-    const int nt = bp_tasks(xy.data(), n, nodes.data(), distance, tasks.data(), task_cap, st.data(), 1024, tr);
-    if (nt < 0) return ROAM_E_CAPACITY;
-    std::vector<uint32_t> pairs(BP_MAX_PAIRS);
-    const int np = bp_expand(xy.data(), idx.data(), nodes.data(), tasks.data(), nt, tr.ub, pairs.data(), BP_MAX_PAIRS);
-    if (np < 0) return ROAM_E_CAPACITY;
-    std::vector<uint16_t> tabA(131072), tabB(131072);
-    std::vector<uint16_t> order(np > 0 ? np : 1);
-    if (bp_pyset_order(pairs.data(), np, tabA.data(), 131072, tabB.data(), 131072, order.data()) != np) return ROAM_E_CAPACITY;
-    std::vector<double> sig(n);
-    for (int i = 0; i < n; i++) sig[i] = blobs[3 * i + 2];
-    for (int k = 0; k < np; k++) {
-        const uint32_t pr = pairs[order[k]];
-        const int i = (int)(pr >> 16), j = (int)(pr & 0xffffu);
-        if (sig[i] == 0 || sig[j] == 0) continue;           // a pruned member: the reference's pass changes nothing
-        if (bp_overlaps(blobs[3 * i], blobs[3 * i + 1], sig[i], blobs[3 * j], blobs[3 * j + 1], sig[j], overlap)) {
-            if (sig[i] > sig[j]) sig[j] = 0; else sig[i] = 0;
-        }
-    }
-    for (int i = 0; i < n; i++) keep_out[i] = sig[i] > 0;
-    return ROAM_OK;
+    const int32_t rc = n > 32767 ? ROAM_E_CAPACITY : prune_blobs_narrow(blobs, n, overlap, xy.data(), distance, keep_out);
+    return rc == ROAM_E_CAPACITY ? prune_blobs_wide(blobs, n, overlap, xy.data(), distance, keep_out) : rc;
 }
 
 // np.argsort(keys) with the tie order of the reference's pinned NumPy 1.22.3 (adaptiveNMS, getFeatures.py:69)

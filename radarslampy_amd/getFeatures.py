@@ -1,9 +1,10 @@
 """Feature (re)detection with the reference's names (reference getFeatures.py:13-118):
-Determinant-of-Hessian blobs (doh.hip) + SSC-ANMS (ssc.hip) + dedupe-append."""
+Determinant-of-Hessian (doh.hip) or Laplacian-of-Gaussian (log.hip) blobs + SSC-ANMS (ssc.hip) + dedupe-append."""
 import numpy as np
 
 from . import _ffi
 from .ANMS import ssc
+from .gaussian import blob_log_sigmas
 
 DEFAULT_FEATURE_PARAMS = dict(min_sigma=0.01, max_sigma=10, num_sigma=3, threshold=.0005, method="doh")
 PERCENT_FEATURE_LOSS_THRESHOLD = 0.75
@@ -25,7 +26,7 @@ def _prune_blobs(blobs, overlap):
     keep = np.zeros(len(bl), np.uint8)
     rc = _ffi.load_library().roam_prune_blobs(_ffi._ptr(bl), len(bl), C.c_double(overlap), _ffi._ptr(keep))
     if rc != _ffi.ROAM_OK:
-        raise _ffi.RoamError(rc, "roam_prune_blobs: %d blobs (integer pixel coordinates, <= 32767 candidate pairs)" % len(bl))
+        raise _ffi.RoamError(rc, "roam_prune_blobs: %d blobs (integer pixel coordinates in [0, 32767])" % len(bl))
     return bl[keep.astype(bool)]
 
 
@@ -44,19 +45,29 @@ def argsort_numpy122(keys) -> np.ndarray:
 
 def getBlobsFromCart(cartImage: np.ndarray, min_sigma=1, max_sigma=30, num_sigma=10, threshold=0.01, method="doh",
                      overlap=0.5) -> np.ndarray:
-    """-> (K,3) [r, c, sigma] (getFeatures.py:22-53; only the live method 'doh' is built).
-    Image-scale work (integral image, Hessian determinants, 3x3x3 maxima) runs on the MI355X
-    (doh.hip); the response ordering / sigma lookup / overlap pruning below follow
-    skimage.feature.blob_doh (peak_local_max ordering, _prune_blobs)."""
-    if method != "doh":
-        raise NotImplementedError(f"{method} not implemented! Use 'doh'")
-    sigma_list = np.linspace(min_sigma, max_sigma, num_sigma)
-    rcs, val = _ffi.default_context().doh_maxima(cartImage, sigma_list, threshold)
-    return blobs_from_maxima(rcs, val, sigma_list, overlap)
+    """-> (K,3) [r, c, sigma] (getFeatures.py:22-53; methods 'doh' and 'log').
+    Image-scale work runs on the MI355X: integral image, Hessian determinants and 3x3x3 maxima for
+    'doh' (doh.hip); Gaussian second-derivative filters and 3x3x3 maxima for 'log' (log.hip).  The
+    response ordering / sigma lookup / overlap pruning below follow skimage.feature.blob_doh and
+    blob_log (peak_local_max ordering, _prune_blobs).  'dog' raises in the reference itself (it passes
+    num_sigma to blob_dog, which has no such parameter), so it is refused here too."""
+    if method == "doh":
+        sigma_list = np.linspace(min_sigma, max_sigma, num_sigma)
+        rcs, val = _ffi.default_context().doh_maxima(cartImage, sigma_list, threshold)
+        return blobs_from_maxima(rcs, val, sigma_list, overlap)
+    if method == "log":
+        if not (np.isscalar(min_sigma) and np.isscalar(max_sigma)):
+            raise NotImplementedError("log: only scalar (isotropic) min_sigma / max_sigma are supported")
+        sigma_list = blob_log_sigmas(min_sigma, max_sigma, num_sigma)
+        threshold = max(threshold, 0.0)             # peak_local_max: max(threshold_abs, threshold_rel * max) with threshold_rel = 0
+        rcs, val = _ffi.default_context().log_maxima(cartImage, sigma_list, threshold)
+        return blobs_from_maxima(rcs, val, sigma_list, overlap)
+    raise NotImplementedError(f"{method} not implemented! Use 'doh' or 'log'")
 
 
 def blobs_from_maxima(rcs, val, sigma_list, overlap=0.5):
-    """host bookkeeping of blob_doh after the image-scale work: response order, sigma lookup, pruning"""
+    """host bookkeeping of blob_doh / blob_log after the image-scale work: response order, sigma lookup, pruning.  Ties of the
+    response keep C (row, col, sigma) order (a stable sort; see docs/PARITY.md for blob_log, where ties are common)"""
     if len(rcs) == 0:
         return np.empty((0, 3))
     idx = np.argsort(-val, kind="stable")         # peak_local_max: highest response first
