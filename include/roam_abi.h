@@ -109,6 +109,19 @@ int32_t roam_polar_to_cart_record_u8(roam_ctx *ctx, const uint8_t *rec, int32_t 
                                      int32_t payload_off, int32_t clip, float *cart_f32,
                                      uint8_t *cart_u8);
 
+/* ---- cv2.warpPolar(src, (dw, dh), (cx, cy), max_radius, INTER_LINEAR | WARP_FILL_OUTLIERS | flags) on float32 images
+ * (parseData.py:69-157: convertCartesianImageToPolar, convertPolarImageToCartesian, convertPolarImgToLogPolar).
+ * flags: ROAM_WARP_POLAR_LOG (semilog) and / or ROAM_WARP_POLAR_INVERSE (polar rows x cols -> Cartesian dh x dw; without it
+ * Cartesian rows x cols -> dh rows of angle x dw columns of radius).  n images of one geometry: image i starts src_image_stride
+ * floats after image i - 1, its rows src_row_stride floats apart; dst is n x dh x dw, contiguous.  dsize arrives resolved
+ * (OpenCV's defaults for a zero size are the caller's).  ROAM_E_ARG: a size <= 0 or > 16384, max_radius <= 0 (<= 1 with
+ * ROAM_WARP_POLAR_LOG) or not finite, a centre that is not finite, unknown flags. */
+#define ROAM_WARP_POLAR_LOG     1
+#define ROAM_WARP_POLAR_INVERSE 2
+int32_t roam_warp_polar_f32(roam_ctx *ctx, const float *src, int32_t n, int32_t rows, int32_t cols, int64_t src_row_stride,
+                            int64_t src_image_stride, float *dst, int32_t dw, int32_t dh, float cx, float cy,
+                            double max_radius, int32_t flags);
+
 /* ---- a7: cv2.calcOpticalFlowPyrLK as used by getTransformKLT.getTrackedPointsKLT
  * (getTransformKLT.py:317-381; LK_PARAMS :77-81: winSize 15, maxLevel 3, 10 iter, eps 0.03).
  * Images are w x h; *_f32 variants quantise (img*255 -> u8, :356-357) on the device.

@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROAM_LIB") or os.path.join(_HERE, "csrc", "libroam_hip.so")     # ROAM_LIB: an A/B build (profiles/build_variant.py)
 
 ROAM_OK, ROAM_E_ARG, ROAM_E_HIP, ROAM_E_CAPACITY, ROAM_E_NODEVICE, ROAM_E_STATE = 0, -1, -2, -3, -4, -5
+WARP_POLAR_LOG, WARP_POLAR_INVERSE = 1, 2      # roam_abi.h ROAM_WARP_POLAR_*
 MAX_FEATURES = 1024
 STEP_NEW_SEQUENCE = 0x40000000      # roam_abi.h ROAM_STEP_NEW_SEQUENCE: OR into a lane's scan index
 
@@ -66,6 +67,8 @@ _SIGS = {
                                               _vp, C.c_int64, _P(C.c_int64)]),
     "roam_polar_to_cart_f32": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_polar_to_cart_record_u8": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
+    "roam_warp_polar_f32": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_int32,
+                                        C.c_float, C.c_float, C.c_double, C.c_int32]),
     "roam_klt_track_u8": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "roam_klt_track_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "roam_pyr_down_u8": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
@@ -267,6 +270,28 @@ class Context:
         u = np.empty((W, W), np.uint8) if want_u8 else None
         self.check(self.lib.roam_polar_to_cart_record_u8(self.h, _ptr(rec), rows, stride, payload_off, clip, _ptr(f), _ptr(u)))
         return f, u
+
+    def warp_polar_f32(self, src, dsize_wh, center, max_radius, log=False, inverse=False):
+        """cv2.warpPolar(src, dsize_wh, center, max_radius, INTER_LINEAR | WARP_FILL_OUTLIERS [| WARP_POLAR_LOG] [| WARP_INVERSE_MAP])
+        on float32 (roam_warp_polar_f32).  src: (rows, cols) or a batch (n, rows, cols) of one geometry; dsize_wh = (dw, dh) already
+        resolved (no OpenCV defaults here).  A 2-D float32 view with unit column stride is read in place with its row stride; any
+        other input is made float32-contiguous first.  -> (dh, dw) or (n, dh, dw) float32"""
+        a = np.asarray(src)
+        if a.ndim not in (2, 3):
+            raise ValueError(f"warp_polar_f32: a 2-D image or a 3-D batch, not {a.ndim}-D")
+        if not (a.ndim == 2 and a.dtype == np.float32 and a.strides[1] == 4 and a.strides[0] % 4 == 0 and a.strides[0] >= 4 * a.shape[1]):
+            a = np.ascontiguousarray(a, np.float32)
+        batch = a.ndim == 3
+        a3 = a if batch else a[None]
+        n, rows, cols = a3.shape
+        row_stride = a3.strides[1] // 4 if rows > 1 else cols
+        image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+        dw, dh = int(dsize_wh[0]), int(dsize_wh[1])
+        out = np.empty((n, max(dh, 0), max(dw, 0)), np.float32)
+        flags = (WARP_POLAR_LOG if log else 0) | (WARP_POLAR_INVERSE if inverse else 0)
+        self.check(self.lib.roam_warp_polar_f32(self.h, _ptr(a3), n, rows, cols, row_stride, image_stride, _ptr(out), dw, dh,
+                                                float(center[0]), float(center[1]), float(max_radius), flags))
+        return out if batch else out[0]
 
     def pyr_down_u8(self, img):
         img = np.ascontiguousarray(img, np.uint8)

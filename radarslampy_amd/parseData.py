@@ -1,5 +1,6 @@
-"""Oxford record decode + polar->Cartesian warp with the reference's names
-(reference parseData.py:9-53,100-135).  The warp runs on the MI355X (warp.hip)."""
+"""Oxford record decode + polar <-> Cartesian warps with the reference's names
+(reference parseData.py:9-53,69-205,229-256).  The warps run on the MI355X (warp.hip, warppolar.hip)."""
+import numbers
 import os
 import time
 
@@ -27,14 +28,98 @@ def extractDataFromRadarImage(polarImgData: np.ndarray, maxRangeClipM: float = M
     return data, azimuths, RANGE_RESOLUTION_M, azimuths[1] - azimuths[0], valid, timestamps
 
 
+WARP_POLAR_MAX_SIDE = 16384                                   # roam_warp_polar_f32's largest image side
+
+
+def _image_2d(img, name: str) -> np.ndarray:
+    a = np.asarray(img)
+    if a.ndim != 2:
+        raise ValueError(f"{name}: expected a 2-D image, got shape {a.shape}")
+    return a
+
+
+def _cv_round(v: float) -> int:
+    """cvRound of a double: nearest integer, half to even"""
+    return int(np.rint(v))
+
+
+def warpPolarDsize(maxRadius: float, dsize=None):
+    """cv2.warpPolar's output size (dw, dh) for dsize = (width, height) or None: both <= 0 -> (cvRound(maxRadius),
+    cvRound(maxRadius * pi)); only the height <= 0 -> cvRound(width * pi).  A width <= 0 with a positive height: ValueError."""
+    w, h = (0, 0) if dsize is None else (int(dsize[0]), int(dsize[1]))
+    if w <= 0 and h <= 0:
+        w, h = _cv_round(maxRadius), _cv_round(maxRadius * np.pi)
+    elif h <= 0:
+        h = _cv_round(w * np.pi)
+    elif w <= 0:
+        raise ValueError(f"warpPolar: dsize width {w} with height {h}")
+    return w, h
+
+
+def _check_warp(dsize, shape, maxRadius: float, logPolarMode: bool):
+    """the arguments roam_warp_polar_f32 would refuse, as ValueError before any device call"""
+    if min(dsize) <= 0 or min(shape) <= 0:
+        raise ValueError(f"warpPolar: empty image ({shape[0]} x {shape[1]} -> {dsize[1]} x {dsize[0]})")
+    if max(dsize) > WARP_POLAR_MAX_SIDE or max(shape) > WARP_POLAR_MAX_SIDE:
+        raise ValueError(f"warpPolar: image side above {WARP_POLAR_MAX_SIDE} ({shape[0]} x {shape[1]} -> {dsize[1]} x {dsize[0]})")
+    if not np.isfinite(maxRadius) or maxRadius <= (1 if logPolarMode else 0):
+        raise ValueError(f"warpPolar: maxRadius {maxRadius} (must exceed {1 if logPolarMode else 0}"
+                         f"{' in log-polar mode' if logPolarMode else ''})")
+
+
+def convertCartesianImageToPolar(imgCart: np.ndarray, logPolarMode: bool = False, shapeHW=None) -> np.ndarray:
+    """square (w, w) Cartesian image -> (dh, dw) polar, centre (h/2, w/2), maxRadius w/2, linear or semilog radius
+    (parseData.py:69-97; roam_warp_polar_f32, warppolar.hip).  shapeHW: the output (H, W); None or zero sizes take OpenCV's defaults
+    (warpPolarDsize).  Unlike cv2, which remaps u8 and f64 natively, any input is converted to float32 first and the output is
+    float32."""
+    img = _image_2d(imgCart, "convertCartesianImageToPolar")
+    h, w = img.shape
+    assert w == h, "Should be a square Cartesian image"
+    center = (h / 2, w / 2)
+    maxRadius = w / 2
+    dsize = warpPolarDsize(maxRadius, None if shapeHW is None else (shapeHW[1], shapeHW[0]))
+    _check_warp(dsize, img.shape, maxRadius, logPolarMode)
+    return _ffi.default_context().warp_polar_f32(img, dsize, center, maxRadius, log=bool(logPolarMode), inverse=False)
+
+
 def convertPolarImageToCartesian(imgPolar: np.ndarray, logPolarMode: bool = False,
                                  downsampleFactor: int = DOWNSAMPLE_FACTOR,
                                  changeGlobalRangeResolution: bool = False) -> np.ndarray:
-    """(rows, cols) f32 polar -> (2R, 2R) f32 Cartesian, R = cols // 2 (parseData.py:100-135)."""
-    if logPolarMode or downsampleFactor != 2:
-        raise NotImplementedError("only the reference's live configuration (linear, downsampleFactor=2) is built")
-    cart, _ = _ffi.default_context().polar_to_cart_f32(imgPolar, want_f32=True, want_u8=False)
-    return cart
+    """(rows, cols) polar -> (2R, 2R) f32 Cartesian, R = cols // downsampleFactor (cols when downsampleFactor <= 1), centre (R, R)
+    (parseData.py:100-135).  The live configuration (linear, downsampleFactor 2) runs warp.hip's roam_polar_to_cart_f32; every
+    other one roam_warp_polar_f32 (warppolar.hip).  changeGlobalRangeResolution sets RANGE_RESOLUTION_CART_M =
+    RANGE_RESOLUTION_M * downsampleFactor, as the reference does.  Unlike cv2, which remaps u8 and f64 natively, any input is
+    converted to float32 first and the output is float32."""
+    img = _image_2d(imgPolar, "convertPolarImageToCartesian")
+    if not isinstance(downsampleFactor, numbers.Integral):
+        raise TypeError(f"downsampleFactor must be an integer, not {type(downsampleFactor).__name__}")
+    df = int(downsampleFactor)
+    cols = img.shape[1]
+    maxRadius = cols // df if df > 1 else cols
+    live = not logPolarMode and df == 2
+    if live:
+        if maxRadius <= 0 or img.shape[0] <= 0:
+            raise ValueError(f"convertPolarImageToCartesian: empty image ({img.shape[0]} x {cols} -> {2 * maxRadius} x {2 * maxRadius})")
+    else:
+        _check_warp((2 * maxRadius, 2 * maxRadius), img.shape, maxRadius, logPolarMode)
+    if changeGlobalRangeResolution:
+        global RANGE_RESOLUTION_CART_M
+        RANGE_RESOLUTION_CART_M = RANGE_RESOLUTION_M * downsampleFactor
+    ctx = _ffi.default_context()
+    if live:
+        cart, _ = ctx.polar_to_cart_f32(img, want_f32=True, want_u8=False)
+        return cart
+    return ctx.warp_polar_f32(img, (2 * maxRadius, 2 * maxRadius), (maxRadius, maxRadius), maxRadius, log=bool(logPolarMode),
+                              inverse=True)
+
+
+def convertPolarImgToLogPolar(imgPolar: np.ndarray) -> np.ndarray:
+    """polar -> Cartesian (downsampleFactor 1) -> semilog polar of OpenCV's default size (parseData.py:138-157)"""
+    img = _image_2d(imgPolar, "convertPolarImgToLogPolar")
+    R = img.shape[1]                                        # the Cartesian image is 2R x 2R, its polar radius R
+    _check_warp(warpPolarDsize(R), (2 * R, 2 * R), R, True)  # (the second warp's arguments, checked before the first one runs)
+    imgCart = convertPolarImageToCartesian(img, logPolarMode=False, downsampleFactor=1, changeGlobalRangeResolution=False)
+    return convertCartesianImageToPolar(imgCart, logPolarMode=True, shapeHW=None)
 
 
 def getRadarImgPaths(dataPath: str, timestampPath: str):
@@ -294,6 +379,29 @@ class RecordDecodePool:
         self.close()
 
 
+def getDataFromImgPathsByIndex(imgPathArr, index: int):
+    """extractDataFromRadarImage of record `index` of imgPathArr (parseData.py:160-180)"""
+    return extractDataFromRadarImage(readRadarRecord(imgPathArr[index]))
+
+
 def getPolarImageFromImgPaths(imgPathArr, index: int) -> np.ndarray:
-    polar, _, _, _, _, _ = extractDataFromRadarImage(readRadarRecord(imgPathArr[index]))
+    polar, _, _, _, _, _ = getDataFromImgPathsByIndex(imgPathArr, index)
     return polar
+
+
+def getCartImageFromImgPaths(imgPathArr, index: int) -> np.ndarray:
+    """Cartesian image of record `index` of imgPathArr at the live geometry (parseData.py:195-205)"""
+    return convertPolarImageToCartesian(getPolarImageFromImgPaths(imgPathArr, index))
+
+
+def getRadarStreamPolar(dataPath: str, timestampPath: str):
+    """every polar image of a sequence, stacked as (rows, cols, N) (parseData.py:229-256, without its prints); None for an empty
+    sequence, as in the reference"""
+    imgPathArray = getRadarImgPaths(dataPath, timestampPath)
+    streamArr = None
+    for i in range(len(imgPathArray)):
+        imgPolar = getPolarImageFromImgPaths(imgPathArray, i)
+        if streamArr is None:
+            streamArr = np.empty(imgPolar.shape + (len(imgPathArray),), dtype=imgPolar.dtype)
+        streamArr[:, :, i] = imgPolar
+    return streamArr
