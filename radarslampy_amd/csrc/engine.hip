@@ -440,6 +440,9 @@ __global__ __launch_bounds__(256) void g4_update_kernel(roam_engine_cfg cfg, con
     if (collect) {
         __shared__ int last_s, sh[4], base_s;
         // (no __threadfence(): on this GPU it writes the XCD's whole L2 back; the flags travel as device-scope atomics, the counter after them)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
+#error "g4_update_kernel's hand-off to its last block relies on gfx94x/95x storing with write-through and counting stores in vmcnt: s_waitcnt vmcnt(0) + relaxed atomics, no release/acquire pair"
+#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (t == 0) last_s = atomicAdd(rt_n + 1, 1) == (int)gridDim.x - 1;

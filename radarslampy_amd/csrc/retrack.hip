@@ -156,6 +156,9 @@ __global__ __launch_bounds__(256) void rt_integ_cols_kernel(RtArgs a, int first,
     // time (one round trip instead of one per band).  col_done[detection][column group] counts the finished bands and is left at zero.
     // The totals cross between workgroups - between XCDs, each with an L2 of its own - as device-scope atomic stores and loads, the
     // counter after them: a __threadfence() here writes the XCD's whole L2 back, 32 MB of integral image included (151 us instead of 18).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
+#error "rt_integ_cols_kernel's band totals reach the last workgroup relying on gfx94x/95x storing with write-through and counting stores in vmcnt: s_waitcnt vmcnt(0) + relaxed atomics, no release/acquire pair"
+#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) last_s = atomicAdd(a.col_done + ls * 64 + (int)blockIdx.x, 1) == nb - 1;
