@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """the motion-distortion solve of a whole batch ALONE: synchronous steps of a B-lane engine, the LM stage's event time
-(ROAM_LM_BLOCK=1 / ROAM_LM_WPE=n choose the kernel form).  usage: python profiles/lm_batch.py [lanes]"""
+usage: python profiles/lm_batch.py [lanes]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

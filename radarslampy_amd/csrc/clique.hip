@@ -220,11 +220,7 @@ __device__ __forceinline__ int cq_solve(CqCtx &c, uint64_t P0, int best, int tar
                 const int thr = best - size;                            // an improving clique needs >= thr neighbours inside P
                 uint64_t RM = 0, UN = 0, PE = 0;
                 int key = 0x7fffffff;
-#ifdef CQ_EXP_NOSPLIT
-                if (false) {
-#else
                 if (TWO && nw >= 2) {
-#endif
                     // the upper half of the vertex groups on the helper wavefront (round 5: the pass is the solver's unit of time -
                     // a dozen of them per search node - and the helper was idle outside the walk's descents)
                     NxMail *mb = c.mail;
@@ -278,7 +274,6 @@ __device__ __forceinline__ int cq_solve(CqCtx &c, uint64_t P0, int best, int tar
 #ifndef CQ_MATCH_AFTER
 #define CQ_MATCH_AFTER 256
 #endif
-#ifndef CQ_EXP_NOMATCH
             if (c.nodes > CQ_MATCH_AFTER) {
                 const int cnt = bs_count(P);
                 uint64_t Q = P;
@@ -297,7 +292,6 @@ __device__ __forceinline__ int cq_solve(CqCtx &c, uint64_t P0, int best, int tar
                 }
                 if (pruned) continue;
             }
-#endif
             depth++;
             if (lane < nw) {
                 c.stk[((int64_t)depth * 2) * c.nws + lane] = P;
@@ -679,9 +673,6 @@ __device__ void nx_build(const CqCtx &c, NxLds &L, NxSet &D, const uint16_t *seq
     D.used = n; D.tab = tab; D.occ = 0; D.mask = size - 1;
     D.perfect = false;
     D.ident = maxkey < size;
-#ifdef NX_EXP_NOBUILD
-    D.ident = true;
-#endif
     if (D.ident) return;
     NX_CNT(8)
     if (size <= 128 && n <= 128) {
@@ -1015,13 +1006,9 @@ __device__ __forceinline__ bool nx_walk(CqCtx &c, NxLds &L, int Kb, uint64_t ALL
             // the only clique of that size in the subtree, and no order has to be followed to find it: done.  (Round 5: this ends the
             // walk as soon as the last contested vertex is decided - before it, the uncontested rest of the clique was walked level by
             // level, the last ~19 levels with explicit 8- / 32-slot tables: 115 us of a 120-us problem of 60 correspondences.)
-#ifndef NX_EXP_NOSHORT
             if (cand.used == omega - size) { RF |= cand.live; return true; }
-#endif
             NX_CNT(6)
-#ifndef NX_EXP_NOBULK
             { NX_T0 nx_bulk(c, subg, cand, RF, size); NX_T1(0) }
-#endif
             int pu;
             { NX_T0 pu = nx_pivot(c, subg, cand.live); NX_T1(1) }
             const uint64_t prow = (lane < nw) ? c.A[(int64_t)pu * c.as + lane] : 0ull;
@@ -1064,9 +1051,7 @@ __device__ __forceinline__ bool nx_walk(CqCtx &c, NxLds &L, int Kb, uint64_t ALL
             if (got >= need) { ok = true; WIT = QB | RQ; }
         }
         if (!ok) continue;
-#ifndef NX_EXP_NOSHORT
         if (ncq == need) { RF = QB | Cq; return true; }                 // (the same one level earlier: no child sets to build)
-#endif
         // descend: subg_q = subg & adj[q], cand_q = cand & adj[q] - two independent replays, the second one on the helper wavefront
         // (round 5: a lone wavefront issues an instruction every ~7 cycles, and the two sets were 2/3 of a level)
         const int deg = bs_count(row);
@@ -1173,7 +1158,6 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void max_clique_kernel(const uint64
     // neighbours inside it, to a fixed point), and a core of exactly omega vertices IS that clique - the witness - whatever the order.
     // A few degree passes (~1 us each) against a walk of 100+ us: a quarter of the real / bench-like pairs (5 of 16 lone sets).
     bool unique = false;
-#ifndef NX_EXP_NOCORE
     if (c.complete && omega > 1) {
         uint64_t P = ALL;
         for (;;) {
@@ -1189,12 +1173,7 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void max_clique_kernel(const uint64
             P &= ~RM;
         }
     }
-#endif
-#ifdef NX_EXP_NOWALK
-    if (false) {
-#else
     if (c.complete && omega > 0 && !unique) {
-#endif
         uint64_t RF = 0;
         { NX_T0 if (nx_walk<TWO>(c, L, Kb, ALL, omega, WIT, RF)) REC = RF; NX_T1(11) }
     }
@@ -1255,7 +1234,7 @@ hipError_t launch_max_clique(hipStream_t st, const uint64_t *adj, const int32_t 
                              uint8_t *mask, int32_t *n_in, int32_t *flags, int32_t *order)
 {
     if (B <= 0 || K <= 0) return hipSuccess;
-    if (!count || B < 512 || getenv("ROAM_CLIQUE_NO_ORDER")) order = nullptr;
+    if (!count || B < 512) order = nullptr;
     if (order) hipLaunchKernelGGL(cq_order_kernel, dim3(1), dim3(1024), 0, st, count, B, K, order, 0);
     size_t lds = ((3 * sizeof(short) * (size_t)(K + 2) + 15) & ~(size_t)15) + 32 * 8 + nx_lds_bytes(K);
     const size_t kw = (size_t)K * ((K + 63) / 64);

@@ -77,7 +77,6 @@ struct Engine {
     double *T_wj0 = nullptr, *T_init = nullptr, *p_w = nullptr, *p_jt = nullptr;
     double *lm_work = nullptr, *lm_out = nullptr;
     int32_t *lm_nfev = nullptr, *lm_info = nullptr;
-    hipEvent_t ev_lm[2] = {};            // fork / join of the LM's workgroup form on the peaks' stream (batches)
     int32_t *lm_big = nullptr;           // MdsProblemDesc::big: the solves left to the workgroup form, two alternating lists
     int lm_big_slot = 0;
     roam_lane_result *results = nullptr;           // ring of RES_RING per-step records (RES_RING x B)
@@ -121,19 +120,10 @@ struct Engine {
     hipEvent_t tr_ev[64][6] = {};
     hipEvent_t rt_ev[64][3 * RT_TRACE_CHUNKS] = {};                    // every detection chunk of a step (the first RT_TRACE_CHUNKS): before | integral image | determinants
     bool rt_ev_ok[64] = {};
-    hipEvent_t ev_int = nullptr;                    // after the integral images of a step's (first) detection chunk
-    hipEvent_t ev_emit = nullptr;                   // after the first bookkeeping kernels behind the determinants (ROAM_PYR_AFTER_EMIT / ROAM_PEAKS_AFTER_EMIT)
-    int pyr_after_emit = 0, peaks_after_emit = 0;
-    hipEvent_t ev_emit2[2] = {};                    // the same moment, alternating between consecutive steps (ROAM_SWAP_WARP_PYR: the warp of step N + 2 waits for step N's)
-    int swap_warp_pyr = 0;
+    hipEvent_t ev_emit = nullptr;                   // batches of >= 256 lanes: after the first bookkeeping kernels behind a step's determinants (made by the
+                                                    // first step that detects; the peaks and the pyramid of every later step wait for it)
     RtSide det_side = {};                           // determinants of a chunk beside the next chunk's integral images (ROAM_DET_SIDE=chunk, 0: off)
     int det_chunk() const { return (det_side.chunk > 0 && retrack_sided(rt, B, &det_side)) ? det_side.chunk : rt.slots; }     // detections per launch of a detection kernel
-    int lm_side = 0;                                // ROAM_LM_SIDE=1 (experiment): the LM's workgroup form on the peaks' stream beside the wave form instead of behind it
-    hipEvent_t ev_emit_last = nullptr;              // (swap experiment) the event the last step recorded there
-    bool ev_int_valid = false;
-    int warp_after_int = 0;                         // ROAM_WARP_AFTER_INTEGRAL (experiment)
-    int peaks_after_int = 0;                        // ROAM_PEAKS_AFTER_INTEGRAL (experiment): the peak kernel waits for the same event as the pyramid
-    int pyr_after_int = 0;                          // ROAM_PYR_AFTER_INTEGRAL: the next pyramid waits for it (experiment, round 6)
     int64_t rt_image_px = 0;                        // pixels of the integral image that are written and read (the needed tiles of the phase list)
     bool tr_ev_ok[64] = {};                          // the step recorded its front-end event pairs (stage events were on when it was enqueued)
     int64_t stage_ev_step = -1;                     // the step whose ev[] (back-end stage events) are valid, -1: none
@@ -601,7 +591,7 @@ int32_t roam_engine_destroy(roam_ctx *ctx)
     auto kill = [](hipEvent_t &ev) { if (ev) { hipEventDestroy(ev); ev = nullptr; } };
     for (auto &ev : e->ev) kill(ev);
     for (int i = 0; i < 4; i++) { kill(e->det_side.ev_i[i]); kill(e->det_side.ev_d[i]); }
-    kill(e->ev_int); kill(e->ev_emit); kill(e->ev_emit2[0]); kill(e->ev_emit2[1]); kill(e->ev_lm[0]); kill(e->ev_lm[1]);
+    kill(e->ev_emit);
     kill(e->ev_join); kill(e->ev_pk0); kill(e->ev_pk1); kill(e->ev_warp); kill(e->ev_idx); kill(e->ev_peaks);
     for (int i = 0; i < 4; i++) { kill(e->ev_klt[i]); kill(e->ev_g4[i]); }
     for (auto &row : e->tr_ev) for (auto &ev : row) kill(ev);
@@ -751,33 +741,9 @@ int32_t roam_engine_create(roam_ctx *ctx, const roam_engine_cfg *cfg)
             // asked for: by the environment here, by roam_engine_debug_detect / roam_engine_time_kernel("doh_fused") on first use)
             const char *fv = getenv("ROAM_FUSED_DETECT");
             r.fused = (fv && fv[0] == '1') ? 1 : 0;
-            // Where the pyramid of the step after next runs (round 6).  Left alone it starts when its warp ends - beside the integral images
-            // of this step, the one pairing on this path that is WORSE than running the two one after the other (integral 31 ms + pyramid
-            // 15.5 ms in-step against 25 + 6.3 alone).  2: it waits for this step's determinants (1: for the integral images) and runs
-            // beside the next step's back end: +2 % on the default workload.  Batches only - a single sequence lives on the overlap of
-            // its front end with the previous pair's back end.  ROAM_PYR_AFTER_INTEGRAL = 0 / 1 / 2 overrides.
-            const char *pv = getenv("ROAM_PYR_AFTER_INTEGRAL");
-            e->pyr_after_int = pv ? atoi(pv) : (B >= 256 ? 2 : 0);
-            // the polar peaks of the step after next (needed by that step's keyframe glue only) wait for the same event: they run beside the
-            // one-wavefront-per-detection bookkeeping that ends this step instead of beside its back end: +2 % more (50.8 -> 51.8 k)
-            const char *kv = getenv("ROAM_PEAKS_AFTER_INTEGRAL");
-            e->peaks_after_int = kv ? atoi(kv) : (B >= 256 ? 1 : 0);
-            const char *wv = getenv("ROAM_WARP_AFTER_INTEGRAL");
-            e->warp_after_int = wv ? atoi(wv) : 0;
-            // ... and not for the determinants' end itself but for the first two kernels of the bookkeeping behind them (candidate order,
-            // longest-list-first ordering: 18 us + 0.6 ms alone): launched at the same moment as the pyramid's and the peaks' 130 000
-            // workgroups, whichever bookkeeping kernel came first waited ~3.8 ms for slots.  +0.8 % (52.6-52.8 -> 53.1-53.3 k, same box;
-            // the pyramid alone behind that event: nothing; the peaks alone: -1 %).  ROAM_PYR_AFTER_EMIT / ROAM_PEAKS_AFTER_EMIT = 0: as before
-            e->pyr_after_emit = getenv("ROAM_PYR_AFTER_EMIT") ? atoi(getenv("ROAM_PYR_AFTER_EMIT")) : (B >= 256 ? 1 : 0);
-            e->peaks_after_emit = getenv("ROAM_PEAKS_AFTER_EMIT") ? atoi(getenv("ROAM_PEAKS_AFTER_EMIT")) : (B >= 256 ? 1 : 0);
-            // (experiment) the warp and the pyramid trade places: the warp of step N + 2 beside step N's bookkeeping, the pyramid of step
-            // N + 1 beside step N's back end (after its tracker)
-            e->swap_warp_pyr = getenv("ROAM_SWAP_WARP_PYR") ? atoi(getenv("ROAM_SWAP_WARP_PYR")) : 0;
             // the determinants of a chunk of 1 024 detections beside the next chunk's integral images (launch_retrack; +1.7 %); needs both
             // halves of a 2 048-slot scratch.  ROAM_DET_SIDE=0: one launch of each kernel per chunk of `slots`, as until late round 6
             e->det_side.chunk = getenv("ROAM_DET_SIDE") ? atoi(getenv("ROAM_DET_SIDE")) : ((B >= 2048 && r.slots >= 2048) ? 1024 : 0);
-            e->lm_side = getenv("ROAM_LM_SIDE") ? atoi(getenv("ROAM_LM_SIDE")) : 0;      // (measured: nothing - 70.68 / 70.46 against 70.69 / 70.29 ms per step)
-            if (e->warp_after_int && !e->pyr_after_int) e->pyr_after_int = 1;     // (the event is made for either)
             r.fd_halo_words = (int64_t)retrack_fused_halo_words(e->W);
         }
         // candidate lists and bookkeeping tables per DETECTION (0.9 MB each): K4-K7 run once per step over all of them
@@ -1387,7 +1353,13 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
     hipStream_t sP = ctx->stream5;
     HIP_TRY(ctx, hipEventRecord(e->ev_idx, sA));
     HIP_TRY(ctx, hipStreamWaitEvent(sP, e->ev_idx, 0));
-    if (e->peaks_after_int && e->pyr_after_int && e->ev_int_valid) HIP_TRY(ctx, hipStreamWaitEvent(sP, (e->swap_warp_pyr && e->ev_emit_last) ? e->ev_emit_last : (e->peaks_after_emit && e->ev_emit) ? e->ev_emit : e->ev_int, 0));
+    // Batches (>= 256 lanes): the polar peaks (needed by this step's keyframe glue only) and the pyramid wait for the first bookkeeping
+    // kernels of the previous step's detection.  Left alone the pyramid starts when its warp ends - beside the integral images of that
+    // step, the one pairing on this path that is WORSE than running the two one after the other (integral 31 ms + pyramid 15.5 ms
+    // in-step against 25 + 6.3 alone) - and, launched at the determinants' end itself, the 130 000 workgroups of the two kept whichever
+    // bookkeeping kernel came first waiting ~3.8 ms for slots.  +2 % +2 % +0.8 % on the default workload (profiles/ROUNDS.md, round 6).
+    // Not for a single sequence: it lives on the overlap of its front end with the previous pair's back end.
+    if (e->ev_emit) HIP_TRY(ctx, hipStreamWaitEvent(sP, e->ev_emit, 0));
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(e->ev[ST_PEAKS], sP));
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(e->ev_pk0, sP));
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(tr[0], sP));
@@ -1396,17 +1368,12 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(e->ev_pk1, sP));
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(tr[5], sP));
     HIP_TRY(ctx, hipEventRecord(e->ev_peaks, sP));
-    if (e->warp_after_int && e->ev_int_valid) HIP_TRY(ctx, hipStreamWaitEvent(sA, e->ev_int, 0));
-    if (e->swap_warp_pyr && e->nstep >= 2 && e->ev_emit2[e->nstep & 1] && e->ev_int_valid) HIP_TRY(ctx, hipStreamWaitEvent(sA, e->ev_emit2[e->nstep & 1], 0));
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(tr[1], sA));
     HIP_TRY(ctx, launch_warp_gather(sA, e->warp_map, pool_warp_src(e, e->scan_idx[pb]), B, c.rows, c.clip, next, e->pd.lane_stride, e->warp_dark_zero));
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(tr[2], sA));
     HIP_TRY(ctx, hipEventRecord(e->ev_warp, sA));                         // end of stage A
     HIP_TRY(ctx, hipStreamWaitEvent(sB, e->ev_warp, 0));
-    if (e->swap_warp_pyr) {
-        if (e->nstep >= 1) HIP_TRY(ctx, hipStreamWaitEvent(sB, e->ev_klt[(e->nstep + 3) & 3], 0));      // the tracker of the step before this one
-    } else
-    if (e->pyr_after_int && e->ev_int_valid) HIP_TRY(ctx, hipStreamWaitEvent(sB, (e->pyr_after_emit && e->ev_emit) ? e->ev_emit : e->ev_int, 0));
+    if (e->ev_emit) HIP_TRY(ctx, hipStreamWaitEvent(sB, e->ev_emit, 0));
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(tr[3], sB));
     HIP_TRY(ctx, launch_build_pyramid(sB, next, e->pd, B, e->pyr_dark));
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(tr[4], sB));
@@ -1446,10 +1413,6 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
         P.N = KM; P.nstride = KS; P.nmax = KM; P.B = B; P.period = 0.25;
         for (int i = 0; i < 5; i++) P.sigma5[i] = c.sigma5[i];
         P.big = e->lm_big; P.big_slot = e->lm_big_slot; e->lm_big_slot ^= 1;
-        if (e->lm_side) {                                                    // batches: the workgroup form beside the wave form (the peaks' stream is idle here)
-            if (!e->ev_lm[0]) { HIP_TRY(ctx, hipEventCreateWithFlags(&e->ev_lm[0], hipEventDisableTiming)); HIP_TRY(ctx, hipEventCreateWithFlags(&e->ev_lm[1], hipEventDisableTiming)); }
-            P.side = ctx->stream5; P.ev_fork = e->ev_lm[0]; P.ev_join = e->ev_lm[1];
-        }
         HIP_TRY(ctx, launch_mds_solve(st, P, e->lm_work, e->lm_out, e->lm_nfev, e->lm_info, nullptr, nullptr));
     }
     if (e->stage_ev) HIP_TRY(ctx, hipEventRecord(e->ev[ST_GLUE], st));
@@ -1464,22 +1427,13 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
         // lanes that ran out of features (flag bit 2; listed by g4_update_kernel's last block): appendNewFeatures on the current scan +
         // keyframe refresh, on the device
         e->rt.res = res_slot;
-        if (e->pyr_after_int && !e->ev_int) HIP_TRY(ctx, hipEventCreateWithFlags(&e->ev_int, hipEventDisableTiming));
-        if ((e->pyr_after_emit || e->peaks_after_emit) && e->pyr_after_int && !e->ev_emit && B >= 256) HIP_TRY(ctx, hipEventCreateWithFlags(&e->ev_emit, hipEventDisableTiming));
-        if (e->swap_warp_pyr && e->pyr_after_int && B >= 256) {
-            // (swap experiment: the "first bookkeeping kernels are out" event alternates between two objects, so that a wait enqueued two
-            // steps later still finds this step's record; ev_emit is made to point at the one just recorded for the peaks' wait)
-            if (!e->ev_emit2[e->nstep & 1]) HIP_TRY(ctx, hipEventCreateWithFlags(&e->ev_emit2[e->nstep & 1], hipEventDisableTiming));
-        }
-        hipEvent_t emit_ev = (e->swap_warp_pyr && e->ev_emit2[e->nstep & 1]) ? e->ev_emit2[e->nstep & 1] : e->ev_emit;
+        if (B >= 256 && !e->ev_emit) HIP_TRY(ctx, hipEventCreateWithFlags(&e->ev_emit, hipEventDisableTiming));
         if (e->det_side.chunk > 0 && !e->det_side.ev_i[0]) {
             e->det_side.st = sB;
             for (int i = 0; i < 4; i++) { HIP_TRY(ctx, hipEventCreateWithFlags(&e->det_side.ev_i[i], hipEventDisableTiming)); HIP_TRY(ctx, hipEventCreateWithFlags(&e->det_side.ev_d[i], hipEventDisableTiming)); }
         }
-        HIP_TRY(ctx, launch_retrack(st, e->rt, B, e->stage_ev ? e->rt_ev[e->nstep & 63] : nullptr, RT_TRACE_CHUNKS, e->pyr_after_int ? e->ev_int : nullptr, e->pyr_after_int - 1, emit_ev,
+        HIP_TRY(ctx, launch_retrack(st, e->rt, B, e->stage_ev ? e->rt_ev[e->nstep & 63] : nullptr, RT_TRACE_CHUNKS, e->ev_emit,
                                     e->det_side.chunk > 0 ? &e->det_side : nullptr));
-        if (e->swap_warp_pyr) e->ev_emit_last = emit_ev;
-        if (e->pyr_after_int) e->ev_int_valid = true;
         if (e->rt_mode == 2) e->rt_floor = std::min(KS, e->kmax() + 256);
     }
     e->rt_ev_ok[e->nstep & 63] = e->rt_on && e->rt_mode && e->stage_ev;

@@ -211,10 +211,10 @@ __device__ __forceinline__ void lmw_lmpar(const double (&R)[6][6], double (&Tl)[
     }
 }
 
-// WPE: wavefronts per SIMD the register budget is cut to (1 = whatever the solve wants: ~290 registers, the lowest latency of a lone
-// solve; in a batch that shares the CUs with other steps' kernels, resident waves are what counts - launch_mds_solve)
-template <int PPT, int WPE>
-__global__ __launch_bounds__(64, WPE) void mds_lm_wave_kernel(MdsProblemDesc P, double *__restrict__ out6, int32_t *__restrict__ nfev_out,
+// the register budget is cut to two wavefronts per SIMD (the solve wants ~290 registers: in a batch that shares the CUs with other
+// steps' kernels, resident waves are what counts - launch_mds_solve)
+template <int PPT>
+__global__ __launch_bounds__(64, 2) void mds_lm_wave_kernel(MdsProblemDesc P, double *__restrict__ out6, int32_t *__restrict__ nfev_out,
                                                          int32_t *__restrict__ info_out, double *__restrict__ x0_out,
                                                          double *__restrict__ r0_out)
 {

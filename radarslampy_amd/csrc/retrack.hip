@@ -236,7 +236,6 @@ __global__ __launch_bounds__(256) void rt_integ_rows_kernel(RtArgs a, int first,
         }
         fetch(x, o, min(i + RR_DEPTH, ntiles - 1));                       // (past the end: the last tile again, never used)
         __syncthreads();
-#ifndef RR_NOCHAIN
         if (threadIdx.x < RR_ROWS) {
             // (columns past the image hold zeros: the chain runs through them, nothing of it is stored)
             double2 *row = reinterpret_cast<double2 *>(tile[threadIdx.x]);
@@ -259,9 +258,7 @@ __global__ __launch_bounds__(256) void rt_integ_rows_kernel(RtArgs a, int first,
                 for (int j = 0; j < 8; j++) row[j0 + 8 + j] = z[j];
             }
         }
-#endif
         __syncthreads();
-#ifndef RR_NOSTORE
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const int r = r0 + 2 * k + lr;
@@ -269,7 +266,6 @@ __global__ __launch_bounds__(256) void rt_integ_rows_kernel(RtArgs a, int first,
             if (r < H && c + 1 < W) *reinterpret_cast<double2 *>(S + (int64_t)r * a.SP + c) = t2;
             else if (r < H && c < W) S[(int64_t)r * a.SP + c] = t2.x;
         }
-#endif
     };
     int i0 = 0;
     for (; i0 + RR_DEPTH <= ntiles; i0 += RR_DEPTH) {
@@ -296,49 +292,23 @@ __global__ __launch_bounds__(256) void rt_integ_rows_kernel(RtArgs a, int first,
 // Both cumulative sums keep NumPy's sequential order; the float64 image is written ONCE (32.8 MB per detection instead of the
 // 98.6 MB moved by the two-pass kernels above, which stay for small chunks - see rt_one_sweep - and for image sizes above 2048).
 #ifndef RI_ROWS
-#define RI_ROWS 16                          // (32 with ONE tile buffer: see RI_SINGLE_BUF)
+#define RI_ROWS 16
 #endif
 #ifndef RI_WAVES
 #define RI_WAVES 4
 #endif
 #define RI_GROUPS (2048 / (64 * RI_WAVES))
-#ifndef RI_LDS_PAD
-#define RI_LDS_PAD 0                        // (occupancy experiments: profiles/build_variant.py)
-#endif
-// (round 6, measured and dropped: ONE tile buffer with the taps of A(i + 1) beside B(i) - half the LDS, so four workgroups per CU - is
-// bit-identical and slower: 6.90 ms per 512 detections against 6.58 at two workgroups per CU, 16.9 us per detection at three; eight column
-// waves per workgroup on one buffer: 10.2 ms.  More waves per CU make this kernel slower, not faster - profiles/r06_detection_experiments.txt)
-#ifndef RI_PHASE_SKIP
-#define RI_PHASE_SKIP 1                     // walk the list of phases that matter (retrack_build_phases) instead of all bands x groups
-#endif
+// (round 6, measured and dropped: ONE tile buffer with the taps of A(i + 1) beside B(i), with bands of 16 or of 32 rows - bit-identical,
+// no faster in the step; more waves per CU make this kernel slower, not faster: profiles/r06_detection_experiments.txt)
 #define RI_PHL_MAX 1024                     // phases of the largest image of the one-sweep kernel (128 bands x 8 groups)
 #ifndef RI_BD
 #define RI_BD 4                             // batches of eight columns the row wave reads ahead of its chain
 #endif
 #define RI_TP 66                            // tile pitch in doubles: even, so that the row wave moves two columns per LDS instruction (round 6)
-// ONE tile buffer and bands of 32 rows (-DRI_SINGLE_BUF=1 -DRI_ROWS=32; round 6, late; bit-identical, NOT the default).  The row wave is
-// what a phase waits for, and an LDS instruction costs it ~20 cycles whatever its active lanes (profiles/r06_detection_experiments.txt
-// items 10, 11): with 32 rows per band it carries twice the pixels per instruction.  The tiles of a 32-row band take the LDS of two
-// buffers of 16 rows, so there is one buffer: A2(i) (column sums -> tile) | barrier | B(i) beside A1(i + 1) (the taps of the next phase:
-// registers only) | barrier | C(i) (tile -> HBM).  512 detections launched together (one round, the two workgroups of every CU in step):
-// 6.46 -> 5.5 ms; 1 024: 12.5 -> 14.0; 1 900: 23.7 -> 22.9; 2 048: 24.8 -> 25.4; in the step (1 700-2 100 detections per launch): 23.44-23.50
-// against 23.36-23.48 ms per launch, 70.4-70.7 against 70.4-70.6 ms per step - once the workgroups of a CU are out of step, nothing.
-// (One buffer with 16-row bands: 6.75 ms per 512, slower than two.)
-#ifndef RI_SINGLE_BUF
-#define RI_SINGLE_BUF 0
-#endif
-#define RI_NBUF (RI_SINGLE_BUF ? 1 : 2)
-#ifndef RI_ROUND
-#define RI_ROUND 0                          // > 0: launch_retrack launches a chunk's integral images in rounds of that many workgroups
-#endif
-#define RI_LDS_BYTES (RI_NBUF * RI_WAVES * RI_ROWS * RI_TP * 8 + RI_LDS_PAD)
+#define RI_LDS_BYTES (2 * RI_WAVES * RI_ROWS * RI_TP * 8)     // two buffers of RI_WAVES tiles
 #ifndef RI_BOX
 #define RI_BOX 2560                         // (round 6: 1536 -> 2560, the LDS that is left at two workgroups per CU: fewer patches on the gather path, -2 %)
 #endif
-#ifndef RI_PREFETCH
-#define RI_PREFETCH 1                       // the box of the next phase is loaded one phase ahead (rt_integral_kernel)
-#endif
-//                        // bytes of polar footprint a column wave may stage (rt_integral_kernel)                      // two neighbouring codes in one (unaligned) load
 // the polar footprint of every (band, group, wave) patch of the sweep depends on the sampling map only: computed once per engine
 // (one wave per patch, the reduction the integral kernel used to redo for every detection and phase: 24 cross-lane exchanges)
 __global__ __launch_bounds__(64) void rt_boxtab_kernel(const uint32_t *__restrict__ map, int W, int cols, uint32_t *__restrict__ boxtab)
@@ -374,31 +344,25 @@ extern "C" int roam_debug_integral_prof(unsigned long long *out, int reset)
 #else
 #define RI_P(k)
 #endif
-__global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs a, int first, int ls0)
+__global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs a, int first)
 {
 #ifdef RI_PROF
     unsigned long long rip_[8] = {0}, rit_ = __builtin_amdgcn_s_memtime();
 #endif
     extern __shared__ __align__(16) double ri_lds[];
-    const int ls = ls0 + (int)blockIdx.x, slot = first + ls;      // (ls0: rounds of a chunk launched one after the other, RI_ROUND)
+    const int ls = (int)blockIdx.x, slot = first + ls;
     if (slot >= *a.rt_n || !rt_one_sweep(a, first) || a.fused) return;
     typedef double Tile[RI_ROWS][RI_TP];
     Tile *tiles = reinterpret_cast<Tile *>(ri_lds);                        // [2][RI_WAVES]
     const int W = a.W, H = a.W, t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const int nbands = (H + RI_ROWS - 1) / RI_ROWS;
     __shared__ float lut[256];
     __shared__ __align__(4) uint8_t box[RI_WAVES][RI_BOX];
     // the phases to walk: band | group << 8 | (tiles the determinant kernel reads, one bit per column wave) << 12, in sweep order
     // (retrack_build_phases: a phase is left out when nothing in it is lit and its row sums are either still zero or never read again)
     __shared__ uint16_t phl[RI_PHL_MAX];
     if (t < 256) lut[t] = rt_code_to_f32(t);
-#if RI_PHASE_SKIP
     const int nph = (int)a.phlist[0];
     for (int i = t; i < nph; i += (int)blockDim.x) phl[i] = (uint16_t)a.phlist[1 + i];
-#else
-    const int nph = nbands * RI_GROUPS;
-    for (int i = t; i < nph; i += (int)blockDim.x) phl[i] = (uint16_t)((i / RI_GROUPS) | ((i % RI_GROUPS) << 8) | (((1u << RI_WAVES) - 1u) << 12));
-#endif
     __syncthreads();
     // (an entry is read once - one LDS read a phase, a phase ahead - and passed on as a scalar)
     auto ph_ent = [&](int i) { return i < nph ? (int)__builtin_amdgcn_readfirstlane((int)phl[i]) : 0; };
@@ -416,7 +380,7 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
         uint32_t m[RI_ROWS];                                               // the map words of the NEXT A, in flight
         uint32_t ext0 = 0, ext1 = 0;                                       // the polar footprint (boxtab) of the patch of the A after the next, in flight
         uint32_t cur0 = 0xffff0000u, cur1 = 0;                             // ... of the next A (wave-uniform)
-        uint32_t raw[8];                                                   // the first eight pieces of the next A's box, in flight (RI_PREFETCH)
+        uint32_t raw[8];                                                   // the first eight pieces of the next A's box, in flight (prefetch_box)
         const int wave_u = __builtin_amdgcn_readfirstlane(wave);
         auto fetch = [&](int band, int g) {
             const int c = min(g * 64 * RI_WAVES + 64 * wave + lane, W - 1);
@@ -469,10 +433,8 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
         // passes while the row wave works on the tile in between
         auto prefetch_box = [&]() {
             cur0 = __builtin_amdgcn_readfirstlane(ext0); cur1 = __builtin_amdgcn_readfirstlane(ext1);
-#if RI_PREFETCH
             const Box b = geom(cur0, cur1);
             if (b.inside) load_pieces(b, 0);
-#endif
         };
         float v[RI_ROWS];                                                  // the pixels of the phase A1 has prepared for A2
         auto A1 = [&](int i, int e_n1, int e_n2) {                         // phase i of the list: the patch's pixels -> v[]; e_n1 / e_n2: the entries of the next two phases
@@ -493,7 +455,7 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
                     // (the general form below spends ~20 instructions per piece on clamps and addresses: a sixth of this kernel)
                     const int npiece = b.nrg * b.ncb;
                     for (int q0 = 0; q0 < npiece; q0 += 8) {
-                        if (q0 > 0 || !RI_PREFETCH) load_pieces(b, q0);
+                        if (q0 > 0) load_pieces(b, q0);                    // (the first eight came with prefetch_box)
                         store_pieces(b, q0, bx);
                     }
                 } else
@@ -521,17 +483,7 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
                         const float wx1 = __fmul_rn((float)((mk >> 22) & 31), 1.f / 32.f), wx0 = __fsub_rn(1.f, wx1);
                         const float wy1 = __fmul_rn((float)(mk >> 27), 1.f / 32.f), wy0 = __fsub_rn(1.f, wy1);
                         const uint8_t *q = bx + (iy - mny) * bp + (ix - mnx);
-#ifdef RI_TAP_VALU
-                        // (experiment: the float32-only decode of warp.hip instead of the table - three VALU instructions against one LDS read)
-                        auto dec = [](uint32_t k) { const float kf = (float)k; return __fmaf_rn(kf, 0x1.0101020000000p-8f, __fmul_rn(kf, -0x1.fdfdfe0000000p-33f)); };
-                        const float s00 = dec(q[0]), s01 = dec(q[1]), s10 = dec(q[bp]), s11 = dec(q[bp + 1]);
-#elif defined(RI_TAP16)
-                        // (experiment: the two neighbouring codes of a polar row in ONE 16-bit LDS read at any alignment)
-                        const uint32_t w0 = reinterpret_cast<const RtU16 *>(q)->v, w1 = reinterpret_cast<const RtU16 *>(q + bp)->v;
-                        const float s00 = lut[w0 & 255], s01 = lut[w0 >> 8], s10 = lut[w1 & 255], s11 = lut[w1 >> 8];
-#else
                         const float s00 = lut[q[0]], s01 = lut[q[1]], s10 = lut[q[bp]], s11 = lut[q[bp + 1]];   // lut[0] = 0: bins past the scan
-#endif
                         r_ = __fmul_rn(s00, __fmul_rn(wy0, wx0));
                         r_ = __fadd_rn(r_, __fmul_rn(s01, __fmul_rn(wy0, wx1)));
                         r_ = __fadd_rn(r_, __fmul_rn(s10, __fmul_rn(wy1, wx0)));
@@ -553,7 +505,7 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
         int gcur = 0;                                                      // the group whose running sums sit in acc[0]
         auto A2 = [&](int i, int band, int g) {
             const int c = g * 64 * RI_WAVES + 64 * wave + lane;
-            Tile &tl = tiles[(RI_SINGLE_BUF ? 0 : (i & 1)) * RI_WAVES + wave];
+            Tile &tl = tiles[(i & 1) * RI_WAVES + wave];
             {
                 // acc[0] is always the running sum of the CURRENT group's column: the array is rotated by one after every phase (8
                 // register moves; a group-indexed array was kept in scratch memory by the compiler: 16 MB of extra HBM writes per
@@ -582,7 +534,7 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
         auto C = [&](int i, int e) {
             const int band = ph_band(e), g = ph_group(e);
             const int c = g * 64 * RI_WAVES + 64 * wave + lane;
-            const Tile &tl = tiles[(RI_SINGLE_BUF ? 0 : (i & 1)) * RI_WAVES + wave];
+            const Tile &tl = tiles[(i & 1) * RI_WAVES + wave];
             const bool wanted = ((e >> (12 + wave_u)) & 1) != 0;              // does anything read this tile?
             if (c < W && wanted) {
                 double *q = S + (int64_t)band * RI_ROWS * SP + c;
@@ -602,19 +554,6 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
             prefetch_box();
             if (nph > 1) fetch_ext(ph_band(e_1) * RI_GROUPS + ph_group(e_1));
             A1(0, e_1, e_2);
-#if RI_SINGLE_BUF
-#pragma unroll 1
-            for (int i = 0; i < nph; i++) {
-                const int e_4 = ph_ent(i + 4);
-                A2(i, ph_band(e_0), ph_group(e_0));
-                __syncthreads();                                           // tile i is complete: B(i) runs ..
-                if (i + 1 < nph) A1(i + 1, e_2, e_3);                      // .. beside the taps of phase i + 1 (registers only)
-                __syncthreads();                                           // B(i) is complete
-                C(i, e_0);
-                e_m1 = e_0; e_0 = e_1; e_1 = e_2; e_2 = e_3; e_3 = e_4;
-            }
-        }
-#else
             A2(0, ph_band(e_0), ph_group(e_0));
 #pragma unroll 1
             for (int i = 0; i < nph; i++) {
@@ -631,7 +570,6 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
         }
         __syncthreads();
         if (nph > 0) C(nph - 1, e_m1);
-#endif
     } else {
         // ------------------------------------------------------------------------------------ the row wave: B(i)
         // (s_setprio 3 for this wave - the chain a phase waits for - moves the wait from the column waves' barrier to their taps: the row wave
@@ -649,7 +587,7 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
             RI_P(6)
             if (live) {
                 const int C0 = g * 64 * RI_WAVES, ncols = min(64 * RI_WAVES, W - C0);
-                Tile *tg = tiles + (RI_SINGLE_BUF ? 0 : (i & 1)) * RI_WAVES;
+                Tile *tg = tiles + (i & 1) * RI_WAVES;
                 int j = 0;
                 if (ncols >= 16) {
                     // batches of eight columns (eight dependent float64 additions), 16-byte LDS accesses (two columns per instruction)
@@ -690,13 +628,8 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
                     *q = carry;
                 }
             }
-#if RI_SINGLE_BUF
-            __syncthreads();                                               // (outside the lanes' branch: one barrier per wave)
-#endif
         }
-#if !RI_SINGLE_BUF
         __syncthreads();
-#endif
     }
 #ifdef RI_PROF
     if (lane == 0 && (wave == 0 || wave == RI_WAVES)) for (int k = 0; k < 8; k++) atomicAdd(&ri_prof[k + (wave == 0 ? 0 : 8)], rip_[k]);
@@ -763,10 +696,7 @@ __device__ __forceinline__ void rt_push_maxima(const RtArgs &a, int ls, int r, i
 #define SD_THREADS (512 * SD_HALVES)
 #define SD_RING_BYTES ((SD_RING + SD_DUP) * SD_PITCHB)
 #define SD_M2_ROWS (SD_T + 2)
-#ifndef SD_LDS_PAD
-#define SD_LDS_PAD 0
-#endif
-#define SD_LDS_BYTES (SD_RING_BYTES + 2 * SD_M2_ROWS * SD_PC * 8 + SD_LDS_PAD)
+#define SD_LDS_BYTES (SD_RING_BYTES + 2 * SD_M2_ROWS * SD_PC * 8)
 #define SD_NST ((SD_T * SD_BP + SD_THREADS - 1) / SD_THREADS)   // staged elements per thread and step (3)
 extern __shared__ __align__(16) char sd_smem[];
 
@@ -986,11 +916,7 @@ __global__ __launch_bounds__(SD_THREADS) void rt_det_strip_kernel(RtArgs a, int 
     // the march covers the strip's lit steps [first, last] only: it starts on the multiple of four at or below first - 1 (a dark step, or
     // step 0: nothing above it is read; the per-position maxima of "the step before" start as zeros, which is what dark steps hold) and
     // ends with step last + 1, whose zeros close the maxima of step last
-#ifdef SD_NO_TRIM
-    const int t_first = 0, t_last = nt - 1;
-#else
     const int t_first = (int)dtab[16], t_last = (int)dtab[17];
-#endif
     if (t_first >= nt) return;                                             // nothing but the corners: no candidates (uniform: before any barrier)
     const int tb = t_first >= 1 ? ((t_first - 1) & ~3) : 0, te = min(nt, t_last + 2);
     int frow = SD_T * tb;                                                  // first image row of the next load: 16 t + 16, t = tb - 1, tb, ..
@@ -1107,12 +1033,6 @@ __global__ __launch_bounds__(SD_THREADS) void rt_det_strip_kernel(RtArgs a, int 
     };
     for (int t = tb; t < te; t += 4) {
         if ((t & 31) == 0 || t == tb) { dk_w = dtab[t >> 5]; skf_w = dtab[8 + (t >> 5)]; }
-#ifdef SD_NO_LOADSKIP
-        skf_w = 0;
-#endif
-#ifdef SD_NO_DARK
-        dk_w = 0;
-#endif
         step(SdTag<0>(), t);
         if (t + 1 < te) step(SdTag<1>(), t + 1);
         if (t + 2 < te) step(SdTag<2>(), t + 2);
@@ -2028,7 +1948,7 @@ bool retrack_sided(const RtArgs &a, int B, const RtSide *side)
     return side && side->chunk > 0 && a.W <= 2048 && !a.fused && a.slots >= 2 * side->chunk && B > side->chunk;
 }
 
-hipError_t launch_retrack(hipStream_t st, const RtArgs &a, int B, hipEvent_t *trace, int ntrace, hipEvent_t after_integral, int after_det, hipEvent_t after_emit, const RtSide *side)
+hipError_t launch_retrack(hipStream_t st, const RtArgs &a, int B, hipEvent_t *trace, int ntrace, hipEvent_t after_order, const RtSide *side)
 {
     const int W = a.W, R = a.slots;
     // image-scale kernels chunk by chunk (the float64 integral images of `slots` detections are resident at once); the
@@ -2052,7 +1972,7 @@ hipError_t launch_retrack(hipStream_t st, const RtArgs &a, int B, hipEvent_t *tr
             ac.S = a.S + (size_t)(nc & 1) * C * a.SP * W;
             if (nc >= 2 && (e = hipStreamWaitEvent(st, side->ev_d[(nc - 2) & 3], 0)) != hipSuccess) return e;      // this bank's determinants are done
             if (tr && (e = hipEventRecord(tev[0], st)) != hipSuccess) return e;
-            if (B - first >= RI_MIN_DETECTIONS) hipLaunchKernelGGL(rt_integral_kernel, dim3(P), dim3(64 * (RI_WAVES + 1)), RI_LDS_BYTES, st, ac, first, 0);
+            if (B - first >= RI_MIN_DETECTIONS) hipLaunchKernelGGL(rt_integral_kernel, dim3(P), dim3(64 * (RI_WAVES + 1)), RI_LDS_BYTES, st, ac, first);
             const int P2 = min(P, RT_TWO_PASS_SLOTS);
             hipLaunchKernelGGL(rt_integ_cols_kernel, dim3((W + 63) / 64, (W + RC_BAND - 1) / RC_BAND, min(P2, RT_TWO_PASS_Z)), dim3(256), 0, st, ac, first, P2);
             hipLaunchKernelGGL(rt_integ_rows_kernel, dim3((W + RR_ROWS - 1) / RR_ROWS, min(P2, RT_TWO_PASS_Z)), dim3(256), 0, st, ac, first, P2);
@@ -2066,7 +1986,6 @@ hipError_t launch_retrack(hipStream_t st, const RtArgs &a, int B, hipEvent_t *tr
         }
         for (int k = max(0, nc - 2); k < nc; k++)
             if ((e = hipStreamWaitEvent(st, side->ev_d[k & 3], 0)) != hipSuccess) return e;
-        if (after_integral && after_det <= 1 && (e = hipEventRecord(after_integral, st)) != hipSuccess) return e;
     } else
     for (int first = 0; first < B; first += R) {
         const int P = min(R, B - first);
@@ -2075,13 +1994,7 @@ hipError_t launch_retrack(hipStream_t st, const RtArgs &a, int B, hipEvent_t *tr
         if (tr && (e = hipEventRecord(tev[0], st)) != hipSuccess) return e;
         if (W <= 2048 && a.fused && B - first >= RI_MIN_DETECTIONS) hipLaunchKernelGGL(rt_fused_kernel, dim3(P), dim3(FD_THREADS), FD_LDS_BYTES, st, a, first, 0);
         else if (W <= 2048 && B - first >= RI_MIN_DETECTIONS)               // (fewer lanes left than a one-sweep chunk needs: it would return at once)
-        {
-            // RI_ROUND > 0 (experiment): the chunk's detections in ROUNDS of that many workgroups, one launch each - the workgroups of a
-            // round start together and stay in step (every detection is the same work), which the one-buffer form likes
-            const int round = RI_ROUND > 0 ? RI_ROUND : P;
-            for (int sub = 0; sub < P; sub += round)
-                hipLaunchKernelGGL(rt_integral_kernel, dim3(min(round, P - sub)), dim3(64 * (RI_WAVES + 1)), RI_LDS_BYTES, st, a, first, sub);
-        }
+            hipLaunchKernelGGL(rt_integral_kernel, dim3(P), dim3(64 * (RI_WAVES + 1)), RI_LDS_BYTES, st, a, first);
         if ((e = hipGetLastError()) != hipSuccess) return e;              // (a refused launch - LDS attribute, grid - surfaces here, not after the chain)
         // (the two-pass form of chunks below RI_MIN_DETECTIONS detections; its band totals live in a.colT, RT_TWO_PASS_SLOTS entries)
         const int P2 = min(P, RT_TWO_PASS_SLOTS);
@@ -2089,9 +2002,7 @@ hipError_t launch_retrack(hipStream_t st, const RtArgs &a, int B, hipEvent_t *tr
         hipLaunchKernelGGL(rt_integ_rows_kernel, dim3((W + RR_ROWS - 1) / RR_ROWS, min(P2, RT_TWO_PASS_Z)), dim3(256), 0, st, a, first, P2);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (tr && (e = hipEventRecord(tev[1], st)) != hipSuccess) return e;
-        if (after_integral && !after_det && first == 0 && (e = hipEventRecord(after_integral, st)) != hipSuccess) return e;      // (the pyramid of a later step may wait for it)
         if ((e = launch_det(st, a, first, P)) != hipSuccess) return e;
-        if (after_integral && after_det == 1 && first + R >= B && (e = hipEventRecord(after_integral, st)) != hipSuccess) return e;
         if (tr && (e = hipEventRecord(tev[2], st)) != hipSuccess) return e;
     }
     if (B < 256) {
@@ -2101,8 +2012,6 @@ hipError_t launch_retrack(hipStream_t st, const RtArgs &a, int B, hipEvent_t *tr
         if ((e = hipGetLastError()) != hipSuccess) return e;
     } else {
         hipLaunchKernelGGL(rt_emit_kernel, dim3(B), dim3(256), 0, st, a, 0);
-        static const int emit_where = getenv("ROAM_EMIT_EVENT_WHERE") ? atoi(getenv("ROAM_EMIT_EVENT_WHERE")) : 1;     // 0 after rt_emit, 1 after the ordering (default), 2 after the small bookkeeping class
-        if (after_emit && emit_where == 0 && (e = hipEventRecord(after_emit, st)) != hipSuccess) return e;       // (a front-end kernel of a later step may wait for it)
         // the bookkeeping is one latency-bound wavefront per detection and its time grows with the candidate list: longest lists first
         // (in the default step 2.1 -> ... ms for the kernel; the work is the same, the tail is not)
         RtArgs ab = a;
@@ -2111,15 +2020,13 @@ hipError_t launch_retrack(hipStream_t st, const RtArgs &a, int B, hipEvent_t *tr
             if ((e = launch_order_by_count(st, a.cand_n, B, BP_MAX_PTS, a.blob_order_buf, 1)) != hipSuccess) return e;
             ab.blob_order = a.blob_order_buf;
         }
-        if (after_emit && emit_where == 1 && (e = hipEventRecord(after_emit, st)) != hipSuccess) return e;
+        if (after_order && (e = hipEventRecord(after_order, st)) != hipSuccess) return e;       // (front-end kernels of later steps wait for it)
         hipLaunchKernelGGL(rt_blobs_kernel<true>, dim3(B), dim3(64), 0, st, ab, 0);
-        if (after_emit && emit_where == 2 && (e = hipEventRecord(after_emit, st)) != hipSuccess) return e;
         hipLaunchKernelGGL(rt_blobs_kernel<false>, dim3(B), dim3(64), 0, st, ab, 0);
         e = launch_ssc_batch(st, a.kp, (int64_t)BP_MAX_PTS * 3, a.kp_n, BP_MAX_PTS, B, 200, 0.1, W, W, a.ssc_work, a.sel, a.sel_n, a.rt_n, 0);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(rt_append_kernel, dim3(B), dim3(256), 0, st, a, 0);
-    if (after_integral && after_det == 2 && (e = hipEventRecord(after_integral, st)) != hipSuccess) return e;     // (after the whole chain)
     return hipGetLastError();
 }
 
@@ -2148,7 +2055,7 @@ hipError_t launch_retrack_part(hipStream_t st, const RtArgs &a_in, int P, int wh
         return hipGetLastError();
     }
     if (which == 0) {
-        hipLaunchKernelGGL(rt_integral_kernel, dim3(P), dim3(64 * (RI_WAVES + 1)), RI_LDS_BYTES, st, a, 0, 0);
+        hipLaunchKernelGGL(rt_integral_kernel, dim3(P), dim3(64 * (RI_WAVES + 1)), RI_LDS_BYTES, st, a, 0);
         const int P2 = min(P, RT_TWO_PASS_SLOTS);
         hipLaunchKernelGGL(rt_integ_cols_kernel, dim3((W + 63) / 64, (W + RC_BAND - 1) / RC_BAND, min(P2, RT_TWO_PASS_Z)), dim3(256), 0, st, a, 0, P2);
         hipLaunchKernelGGL(rt_integ_rows_kernel, dim3((W + RR_ROWS - 1) / RR_ROWS, min(P2, RT_TWO_PASS_Z)), dim3(256), 0, st, a, 0, P2);

@@ -145,17 +145,10 @@ __global__ __launch_bounds__(256) void polar_to_cart_kernel(WarpSrc src, int row
 // code (round 5; rounds 1-4 went through (float)((double)k * (1.0 / 255.0)): a v_cvt_f64_u32 + a half-rate v_mul_f64 + a
 // v_cvt_f32_f64 per sample, and the staging of the polar boxes - one decode per sample and scan - was a third of this kernel's vector
 // instructions).  (float)(byte of a word) is ONE instruction (v_cvt_f32_ubyteN).
-#ifndef WG_DECODE_F64
-#define WG_DECODE_F64 0
-#endif
 __device__ __forceinline__ float code_to_f32(uint32_t k)
 {
-#if WG_DECODE_F64
-    return (float)__dmul_rn((double)k, 1.0 / 255.0);
-#else
     const float kf = (float)k;
     return __fmaf_rn(kf, 0x1.0101020000000p-8f, __fmul_rn(kf, -0x1.fdfdfe0000000p-33f));            // head + tail = 1 / 255 to 2^-57
-#endif
 }
 
 // pack: ix [0,12) | iy [12,22) | fx [22,27) | fy [27,32)
@@ -196,10 +189,7 @@ hipError_t launch_warp_map(hipStream_t st, int rows, int cols, uint32_t *map)
 #endif
 #define WG_TW 64          // tile width  (one wavefront = 64 consecutive pixels of a row)
 #define WG_TH 16          // tile height
-#define WG_BOX_ELEMS 4096     // polar samples staged per pass, already decoded to float32 (16 KB; WG_CELL: twice that)
-#ifndef WG_CELL
-#define WG_CELL 0             // (round 6 experiment) the box as CELLS {s[k][c], s[k+1][c]}: the four taps of a pixel are two neighbouring cells - ONE ds_read2_b64
-#endif
+#define WG_BOX_ELEMS 4096     // polar samples staged per pass, already decoded to float32 (16 KB)
 #ifndef WG_FILL_U
 #define WG_FILL_U 4       // scans whose box rows are loaded before the first load is consumed
 #endif
@@ -228,13 +218,12 @@ template <int M> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v)
 // written with one 16-byte LDS store (the LDS row pitch bp is a multiple of 4 floats).  wave wvs takes the row
 // groups wvs, wvs+4, ...; the U scans' loads are issued before the first is consumed.
 typedef uint32_t u32_a1 __attribute__((aligned(1)));
-template <int U, bool CHK, bool RAWK = false, bool CELL = false>
+template <int U, bool CHK>
 __device__ __forceinline__ void box_fill(const uint8_t *__restrict__ sp, int64_t lane_stride,
                                          const int32_t *__restrict__ lane_index, int l, int64_t row_stride, int rows,
                                          int cols, int mnx, int mny, int bw, int bp, int bh, int elems, int wvs, int lane,
-                                         float *__restrict__ bq, int pp = 0)
+                                         float *__restrict__ bq)
 {
-    // pp != 0: the swizzled layout of the kernel below (WG_SWZ) - sample c of a row at float c + (c >> 5), pitch pp
     int64_t so[U];
 #pragma unroll
     for (int u = 0; u < U; u++) so[u] = (lane_index ? (int64_t)lane_index[l + u] : (int64_t)(l + u)) * lane_stride;
@@ -247,7 +236,7 @@ __device__ __forceinline__ void box_fill(const uint8_t *__restrict__ sp, int64_t
             const int c = min(cb + c4, bp - 4);           // clamped lanes rewrite the last column group
             const int x0 = mnx + c;                       // first range bin of this lane's dword
             const uint8_t *srow = sp + (__mul24(r, (int)row_stride) + x0);       // rows * stride < 2^31 (launcher requirement)
-            float *drow = pp ? bq + (k * pp + c + (c >> 5)) : bq + (k * bp + c);
+            float *drow = bq + (k * bp + c);
             uint32_t raw[U];
 #pragma unroll
             for (int u = 0; u < U; u++) raw[u] = *reinterpret_cast<const u32_a1 *>(srow + so[u]);
@@ -256,49 +245,18 @@ __device__ __forceinline__ void box_fill(const uint8_t *__restrict__ sp, int64_t
                 float4 v;
                 // (CHK: the box reaches past the scan's last range bin - those samples are zero; most boxes do not, and are spared the
                 // four compares and selects per dword)
-                // RAWK: the codes as they are (integer blend, below): one v_cvt_f32_ubyteN per sample
-                v.x = (!CHK || x0 < cols) ? (RAWK ? (float)(raw[u] & 255u) : code_to_f32(raw[u] & 255u)) : 0.f;
-                v.y = (!CHK || x0 + 1 < cols) ? (RAWK ? (float)((raw[u] >> 8) & 255u) : code_to_f32((raw[u] >> 8) & 255u)) : 0.f;
-                v.z = (!CHK || x0 + 2 < cols) ? (RAWK ? (float)((raw[u] >> 16) & 255u) : code_to_f32((raw[u] >> 16) & 255u)) : 0.f;
-                v.w = (!CHK || x0 + 3 < cols) ? (RAWK ? (float)(raw[u] >> 24) : code_to_f32(raw[u] >> 24)) : 0.f;
-                if (CELL) {
-                    // sample (k, c) is the upper half of cell (k, c) and the lower half of cell (k - 1, c): two ds_write2_b32 each
-                    float *d = bq + 2 * (k * bp + c) + u * 2 * elems;
-                    d[0] = v.x; d[2] = v.y; d[4] = v.z; d[6] = v.w;
-                    if (k > 0) { float *e = d - 2 * bp + 1; e[0] = v.x; e[2] = v.y; e[4] = v.z; e[6] = v.w; }
-                } else
-                if (pp) {                                 // (4-byte aligned only: four dword stores; the slot before a 32-sample block repeats its first sample)
-                    float *d = drow + u * elems;
-                    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-                    if ((c & 31) == 0 && c > 0) d[-1] = v.x;
-                } else
-                    *reinterpret_cast<float4 *>(drow + u * elems) = v;
+                v.x = (!CHK || x0 < cols) ? code_to_f32(raw[u] & 255u) : 0.f;
+                v.y = (!CHK || x0 + 1 < cols) ? code_to_f32((raw[u] >> 8) & 255u) : 0.f;
+                v.z = (!CHK || x0 + 2 < cols) ? code_to_f32((raw[u] >> 16) & 255u) : 0.f;
+                v.w = (!CHK || x0 + 3 < cols) ? code_to_f32(raw[u] >> 24) : 0.f;
+                *reinterpret_cast<float4 *>(drow + u * elems) = v;
             }
         }
     }
 }
 
-// ---- exact blend (round 6).  The KLT input is trunc(v * 255) with v = ((s00 w00 + s01 w01) + s10 w10) + s11 w11 in float32, s = code / 255
-// and the weights multiples of 2^-10 that sum to 1.  With integer weights W = 1024 w the exact value of v * 255 is E = sum(W k) / 1024, a
-// multiple of 2^-10, and the float32 chain (one rounding for the decode, one per product, three for the sums, one for the scaling, all
-// operands non-negative) stays within 6.001 * 2^-24 * E < 9.2e-5 of it - a tenth of 2^-10.  So whenever E is NOT an integer the truncated
-// float equals floor(E) = sum(W k) >> 10, whatever the roundings did; only a sum that is an exact non-zero multiple of 1024 (the float may
-// land just below the integer: one pixel in ~1024) needs the float chain, and a sum of zero is zero either way.
-// sum(W k) is formed in FLOAT32 all the same - 64 W (at most 2^16) and k (at most 255) are integers, every product and partial sum is an
-// integer below 2^24, so three v_fma_f32 after one v_mul_f32 are exact in any order - because float32 multiply-adds are the cheapest
-// vector instructions on this chip (SIMD-32: half the cycles of an integer instruction; a first version with v_dot4_u32_u8 on packed codes
-// and 24-bit integer multiply-adds was bit-identical and took 14.3 ms against 10.5).  The box holds the codes as floats (one
-// v_cvt_f32_ubyteN per sample instead of the three-instruction exact quotient by 255), v_cvt_u32_f32 turns the sum into the integer
-// 64 sum(W k): byte 2 is the pixel and "multiple of 1024" reads "low half zero" (v_min3_u16 over a thread's four pixels).  Flagged pixels
-// go to a per-wave list and are recomputed by the float32 chain from global memory after the dword stores they correct (same wave, after
-// s_waitcnt vmcnt(0)): at the end of the workgroup, or earlier when the list runs full.
-#ifndef WG_INT_BLEND
-#define WG_INT_BLEND 0                      // NOT the default: bit-identical on every test, and slower (profiles/r06_warp_exact_blend.txt)
-#endif
-#ifndef WG_DIAG
-#define WG_DIAG 0                           // timing experiments (wrong bytes): 1 = no fill, 2 = no blend loop
-#endif
-#define WG_FIX_CAP 320                      // entries per wave; flushed at 64 before a pass of at most 256 new ones
+// (round 6, measured and dropped, all bit-identical and none faster: an exact integer blend with a float32 fix-up list
+// (profiles/r06_warp_exact_blend.txt); the box as cells of two rows, padded and swizzled box pitches (profiles/r06_warp_experiments.txt))
 
 __global__ __launch_bounds__(256) void warp_gather_kernel(const uint32_t *__restrict__ map, const uint8_t *__restrict__ pool,
                                                           int64_t lane_stride, int64_t row_stride, int payload_off,
@@ -306,7 +264,7 @@ __global__ __launch_bounds__(256) void warp_gather_kernel(const uint32_t *__rest
                                                           int cols, int W, uint8_t *__restrict__ cart_u8,
                                                           int64_t u8_lane_stride, int gx, int gy, int total, int dark_stays_zero)
 {
-    __shared__ __align__(16) float box[WG_BOX_ELEMS * (WG_CELL ? 2 : 1)];
+    __shared__ __align__(16) float box[WG_BOX_ELEMS];
     __shared__ int red[4][4];
     // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own
     // L2), so XCD x is given the x-th contiguous eighth of the (scan group, tile row, tile) list:
@@ -361,29 +319,13 @@ __global__ __launch_bounds__(256) void warp_gather_kernel(const uint32_t *__rest
     mny = __builtin_amdgcn_readfirstlane(mny); mxy = __builtin_amdgcn_readfirstlane(mxy);
     const bool any = mxx >= 0;
     const int bw = mxx - mnx + 2, bh = mxy - mny + 2;
-#ifndef WG_BP_MODE
-#define WG_BP_MODE 0
-#endif
-    int bp_ = (bw + 3) & ~3;                          // LDS pitch of a box row: whole 16-byte stores
-    if (WG_BP_MODE == 1 && (bp_ & 4) == 0) bp_ += 4;  // (experiment: an odd multiple of four floats - rows k, k + 1, .. start in different banks)
-    if (WG_BP_MODE == 2) { while ((bp_ & 31) != 4) bp_ += 4; }
-    const int bp = bp_;
-    // WG_SWZ (experiment, round 6; NOT the default): adjacent pixels of a tile whose rows run along the range axis sit two samples apart, so
-    // the 32 lanes of an LDS access group meet 16 banks.  With one spare float after every 32 samples of a box row the second half of
-    // such a group lands on the other parity; the spare slot repeats the sample that follows it, so that the pair (c, c + 1) stays two
-    // neighbouring floats.  Bit-identical, and no better: over all tiles the tap reads average 2.05 LDS cycles per 32-lane dword access
-    // with either layout (a model of the bank mapping over the real sampling map: profiles/r06_warp_experiments.txt) - the footprint of
-    // a tile is a slanted patch, not a stride - and the PMC conflict count rose (2.42e8 -> 2.73e8 with the four dword stores of the fill).
-#ifndef WG_SWZ
-#define WG_SWZ 0
-#endif
-    const int pp = WG_SWZ ? bp + (bp >> 5) + 1 : bp;   // physical pitch of a box row
-    const int elems = pp * bh;
+    const int bp = (bw + 3) & ~3;                     // LDS pitch of a box row: whole 16-byte stores
+    const int elems = bp * bh;
     const bool use_box = any && (elems <= WG_BOX_ELEMS);
     int off0[4], off1[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        if (use_box) { const int cc = ixv[j] - mnx; off0[j] = (iyv[j] - mny) * pp + cc + (WG_SWZ ? (cc >> 5) : 0); off1[j] = off0[j] + pp; }
+        if (use_box) { const int cc = ixv[j] - mnx; off0[j] = (iyv[j] - mny) * bp + cc; off1[j] = off0[j] + bp; }
         else {
             int r0 = iyv[j] - 1, r1 = iyv[j];
             if (r0 < 0) r0 += rows; else if (r0 >= rows) r0 -= rows;
@@ -431,104 +373,6 @@ __global__ __launch_bounds__(256) void warp_gather_kernel(const uint32_t *__rest
         }
         return;
     }
-#if WG_INT_BLEND
-    // box path, exact blend (see above); branch-free: pixels outside the scan get zero weights and offset 0
-    static_assert(WG_LB <= 32, "a list entry holds the scan in five bits");
-    __shared__ uint16_t fixl[4][WG_FIX_CAP];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        if (!in0[j]) { w00[j] = w01[j] = w10[j] = w11[j] = 0.f; off0[j] = off1[j] = 0; }
-        w00[j] = __fmul_rn(w00[j], 65536.f); w01[j] = __fmul_rn(w01[j], 65536.f);       // 64 W: integers up to 2^16
-        w10[j] = __fmul_rn(w10[j], 65536.f); w11[j] = __fmul_rn(w11[j], 65536.f);
-    }
-    const int wvs = __builtin_amdgcn_readfirstlane(wv);
-    const bool chk = mnx + bp > cols;                 // some staged column lies past the last range bin (wave-uniform)
-    const int per = max(1, min(WG_LB, WG_BOX_ELEMS / elems));
-    uint16_t *fl = fixl[wvs];
-    int nfix = 0;                                     // entries in this wave's list (wave-uniform)
-    const uint64_t below = (1ull << lane) - 1ull;
-    // the float32 chain for the listed pixels (entry = q | j << 5 | lane << 7: scan l0 + q, row 4 wv + j of the tile, column lane)
-    auto fix_pixels = [&]() {
-        __builtin_amdgcn_s_waitcnt(0x0f70);           // vmcnt(0): the dword stores these bytes correct have left
-        for (int i = lane; i < nfix; i += 64) {
-            const uint32_t e = fl[i];
-            const int q = e & 31, j = (e >> 5) & 3, ln = e >> 7;
-            const int xx = bx_ * WG_TW + ln, yy = y0 + wvs * 4 + j, l = l0 + q;
-            const uint32_t m = map[(int64_t)yy * W + xx];
-            const int ix = m & 4095, iy = (m >> 12) & 1023;
-            const float wx1 = __fmul_rn((float)((m >> 22) & 31), 1.f / 32.f), wx0 = __fsub_rn(1.f, wx1);
-            const float wy1 = __fmul_rn((float)(m >> 27), 1.f / 32.f), wy0 = __fsub_rn(1.f, wy1);
-            int r0 = iy - 1, r1 = iy;
-            if (r0 < 0) r0 += rows; else if (r0 >= rows) r0 -= rows;
-            if (r1 >= rows) r1 -= rows;
-            const uint8_t *p = pool + ((lane_index ? (int64_t)lane_index[l] : (int64_t)l) * lane_stride + payload_off);
-            const uint8_t *q0 = p + r0 * (int)row_stride + ix, *q1 = p + r1 * (int)row_stride + ix;
-            const bool i1 = ix + 1 < cols;
-            const float s00 = code_to_f32(q0[0]), s01 = i1 ? code_to_f32(q0[1]) : 0.f;
-            const float s10 = code_to_f32(q1[0]), s11 = i1 ? code_to_f32(q1[1]) : 0.f;
-            float v = __fmul_rn(s00, __fmul_rn(wy0, wx0));
-            v = __fadd_rn(v, __fmul_rn(s01, __fmul_rn(wy0, wx1)));
-            v = __fadd_rn(v, __fmul_rn(s10, __fmul_rn(wy1, wx0)));
-            v = __fadd_rn(v, __fmul_rn(s11, __fmul_rn(wy1, wx1)));
-            cart_u8[(int64_t)l * u8_lane_stride + (int64_t)yy * W + xx] = (uint8_t)quant_u8_unit(v);
-        }
-        nfix = 0;
-    };
-    for (int lb = l0; lb < l1; lb += per) {
-        const int nq = min(per, l1 - lb);
-        for (int qb = (WG_DIAG == 1 ? nq : 0); qb < nq;) {
-            const int rem = nq - qb;
-            const uint8_t *sp = pool + payload_off;
-            float *bq = box + qb * elems;
-#define WG_FILL(U_) { if (chk) box_fill<U_, true, true>(sp, lane_stride, lane_index, lb + qb, row_stride, rows, cols, mnx, mny, bw, bp, bh, elems, wvs, lane, bq, WG_SWZ ? pp : 0); \
-                      else box_fill<U_, false, true>(sp, lane_stride, lane_index, lb + qb, row_stride, rows, cols, mnx, mny, bw, bp, bh, elems, wvs, lane, bq, WG_SWZ ? pp : 0); qb += U_; }
-            if (rem >= 8 && WG_FILL_U >= 8) WG_FILL(8)
-            else if (rem >= 4 && WG_FILL_U >= 4) WG_FILL(4)
-            else if (rem >= 2 && WG_FILL_U >= 2) WG_FILL(2)
-            else WG_FILL(1)
-#undef WG_FILL
-        }
-        __syncthreads();
-        uint8_t *dq = dst + (int64_t)lb * u8_lane_stride;          // this thread's dword in scan lb, advanced per scan
-        for (int q = (WG_DIAG == 2 ? nq : 0); q < nq; q++) {
-            const float *bx = box + q * elems;
-            uint32_t sm[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const f32x2 ta = f32x2{bx[off0[j]], bx[off0[j] + 1]}, tb = f32x2{bx[off1[j]], bx[off1[j] + 1]};   // one ds_read2_b32 each
-                float e = __fmul_rn(ta.x, w00[j]);                                 // exact: integers below 2^24
-                e = __fmaf_rn(ta.y, w01[j], e);
-                e = __fmaf_rn(tb.x, w10[j], e);
-                e = __fmaf_rn(tb.y, w11[j], e);
-                sm[j] = (uint32_t)e;                                               // 64 * sum(W k)
-            }
-            uint32_t mn;
-            asm("v_min3_u16 %0, %1, %2, %3" : "=v"(mn) : "v"(sm[0]), "v"(sm[1]), "v"(sm[2]));
-            asm("v_min_u16 %0, %1, %2" : "=v"(mn) : "v"(mn), "v"(sm[3]));
-            if (WG_DIAG != 3 && WG_DIAG != 4 && __builtin_expect(__ballot((mn & 0xffffu) == 0u) != 0ull, 0)) {
-                // (rare) some pixel's sum has a zero low half: list the non-zero ones for the float chain
-                if (nfix > WG_FIX_CAP - 256) fix_pixels();
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const bool f = (sm[j] & 0xffffu) == 0u && sm[j] != 0u;
-                    const uint64_t bal = __ballot(f);
-                    if (f) fl[nfix + __popcll(bal & below)] = (uint16_t)((lb - l0 + q) | (j << 5) | (lane << 7));
-                    nfix += __popcll(bal);
-                }
-            }
-            // byte 2 of each sum is the pixel
-            const uint32_t pk = __builtin_amdgcn_perm(sm[1], sm[0], 0x0c0c0602u) | __builtin_amdgcn_perm(sm[3], sm[2], 0x06020c0cu);
-            const uint32_t v0 = quad_bcast<0>(pk), v1 = quad_bcast<1>(pk), v2 = quad_bcast<2>(pk), v3 = quad_bcast<3>(pk);
-            const uint32_t t01 = __builtin_amdgcn_perm(v1, v0, psel), t23 = __builtin_amdgcn_perm(v3, v2, psel);
-            const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute(pull << 2, (int)(t01 | (t23 << 16)));
-            if (sok) *reinterpret_cast<uint32_t *>(dq) = o;
-            dq += u8_lane_stride;
-        }
-        __syncthreads();
-    }
-    if (WG_DIAG != 4 && nfix > 0) fix_pixels();
-}
-#else
     // box path, written branch-free: pixels outside the scan get zero weights and offset 0, loads
     // past the end of a row / past the last scan of the pass are clamped onto a valid duplicate
     f32x2 wa[4], wb[4];
@@ -548,9 +392,9 @@ __global__ __launch_bounds__(256) void warp_gather_kernel(const uint32_t *__rest
         for (int qb = 0; qb < nq;) {
             const int rem = nq - qb;
             const uint8_t *sp = pool + payload_off;
-            float *bq = box + qb * elems * (WG_CELL ? 2 : 1);
-#define WG_FILL(U_) { if (chk) box_fill<U_, true, false, WG_CELL != 0>(sp, lane_stride, lane_index, lb + qb, row_stride, rows, cols, mnx, mny, bw, bp, bh, elems, wvs, lane, bq, WG_SWZ ? pp : 0); \
-                      else box_fill<U_, false, false, WG_CELL != 0>(sp, lane_stride, lane_index, lb + qb, row_stride, rows, cols, mnx, mny, bw, bp, bh, elems, wvs, lane, bq, WG_SWZ ? pp : 0); qb += U_; }
+            float *bq = box + qb * elems;
+#define WG_FILL(U_) { if (chk) box_fill<U_, true>(sp, lane_stride, lane_index, lb + qb, row_stride, rows, cols, mnx, mny, bw, bp, bh, elems, wvs, lane, bq); \
+                      else box_fill<U_, false>(sp, lane_stride, lane_index, lb + qb, row_stride, rows, cols, mnx, mny, bw, bp, bh, elems, wvs, lane, bq); qb += U_; }
             if (rem >= 8 && WG_FILL_U >= 8) WG_FILL(8)
             else if (rem >= 4 && WG_FILL_U >= 4) WG_FILL(4)
             else if (rem >= 2 && WG_FILL_U >= 2) WG_FILL(2)
@@ -561,18 +405,6 @@ __global__ __launch_bounds__(256) void warp_gather_kernel(const uint32_t *__rest
         uint8_t *dq = dst + (int64_t)lb * u8_lane_stride;          // this thread's dword in scan lb, advanced per scan
         for (int q = 0; q < nq; q++) {
             float vq[4];
-#if WG_CELL
-            // cells: (s00, s10) and (s01, s11) are two neighbouring 8-byte cells - one ds_read2_b64 per pixel
-            const f32x2 *cb = reinterpret_cast<const f32x2 *>(box) + q * elems;
-            f32x2 ta[4], tb[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) { ta[j] = cb[off0[j]]; tb[j] = cb[off0[j] + 1]; }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const f32x2 pa = ta[j] * f32x2{w00[j], w10[j]}, pb = tb[j] * f32x2{w01[j], w11[j]};      // (s00 w00, s10 w10), (s01 w01, s11 w11)
-                vq[j] = __fadd_rn(__fadd_rn(__fadd_rn(pa.x, pb.x), pa.y), pb.y);
-            }
-#else
             const float *bx = box + q * elems;
             f32x2 ta[4], tb[4];
 #pragma unroll
@@ -587,7 +419,6 @@ __global__ __launch_bounds__(256) void warp_gather_kernel(const uint32_t *__rest
                 const f32x2 pa = ta[j] * wa[j], pb = tb[j] * wb[j];
                 vq[j] = __fadd_rn(__fadd_rn(__fadd_rn(pa.x, pa.y), pb.x), pb.y);
             }
-#endif
             // (scalar multiplies here: a packed one makes the compiler pack the three adds above as well, at the
             // price of a dozen register moves)
             // (v_cvt_pk_u8_f32 would convert AND place the byte, but it ROUNDS to nearest where the reference's cast truncates - 11.0 ->
@@ -602,8 +433,6 @@ __global__ __launch_bounds__(256) void warp_gather_kernel(const uint32_t *__rest
         __syncthreads();
     }
 }
-
-#endif
 
 // requires W % 4 == 0, u8_lane_stride % 4 == 0, rows * row_stride + cols < 2^31
 hipError_t launch_warp_gather(hipStream_t st, const uint32_t *map, WarpSrc src, int B, int rows, int cols,
