@@ -215,6 +215,15 @@ int32_t roam_argsort_np122(const double *keys, int32_t n, int32_t *order_out);
 int32_t roam_fmt_rotation(roam_ctx *ctx, const float *src_polar, const float *tgt_polar, int32_t rows, int32_t cols,
                           int32_t clip_px, int32_t downsample, double *angle_rad, double *scale, double *response);
 
+/* FMT.getTranslationUsingPhaseCorrelation (FMT.py:13-33): cv2.phaseCorrelate(src, tgt, createHanningWindow((cols, rows), CV_32F))
+ * for `batch` pairs of rows x cols float32 images (row_stride / image_stride in elements).  hanning = 0: no window
+ * (cv2.phaseCorrelate(src, tgt)).  out_dxdy (batch, 2) f64 [dx, dy], out_response (batch) f64 (may be NULL).
+ * The images are zero-padded to the optimal DFT size (2^a 3^b 5^c) and transformed by the mixed-radix FFT of csrc/fft.hip; a large
+ * batch is processed in chunks that keep the device scratch under 2 GB.  ROAM_E_ARG: rows or cols outside [2, 4096], batch < 1,
+ * a null src / tgt / out_dxdy, row_stride < cols, image_stride smaller than one image's extent (batch > 1). */
+int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t batch, int32_t rows, int32_t cols,
+                                 int64_t row_stride, int64_t image_stride, int32_t hanning, double *out_dxdy, double *out_response);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous
@@ -431,6 +440,17 @@ int32_t roam_remote_map_reserve(roam_ctx *ctx, int32_t keyframes);
  * back with roam_remote_map_count / _get.  recv == NULL: only the layout is returned.  Needs roam_remote_map_reserve(>= world). */
 int32_t roam_debug_keyframe_append(roam_ctx *ctx, const uint8_t *recv, int32_t world, int64_t *rec_bytes, int32_t *locals_off,
                                    int32_t *peaks_off, int32_t *max_peaks);
+/* test / measurement: the 2-D FFT alone.  roam_debug_fft2_f64: rows x cols float64 planes (host; im_in may be NULL), both sizes
+ * 2^a 3^b 5^c in [1, 4096]; inverse != 0: the unscaled inverse.  roam_time_fft2: average milliseconds (HIP events, two warm runs
+ * first) of `what` on zero planes of that size (sizes from 2). */
+int32_t roam_debug_fft2_f64(roam_ctx *ctx, const double *re_in, const double *im_in, int32_t rows, int32_t cols, int32_t inverse,
+                            double *re_out, double *im_out);
+#define ROAM_TIME_FFT_FIVE      0   /* the five 2-D transforms of one phase correlation (two real forward, one inverse), transposes included */
+#define ROAM_TIME_DFT_FIVE      1   /* the same five as roam_fmt_rotation's direct DFTs (rows * cols <= 131072) */
+#define ROAM_TIME_FFT_ROWS      2   /* one row pass: `rows` transforms of length cols, in place */
+#define ROAM_TIME_FFT_TRANSPOSE 3   /* one transpose rows x cols -> cols x rows */
+#define ROAM_TIME_FFT_COLS      4   /* one column pass on the transposed plane: `cols` transforms of length rows, in place */
+int32_t roam_time_fft2(roam_ctx *ctx, int32_t rows, int32_t cols, int32_t what, int32_t reps, float *ms_per_rep);
 int32_t roam_remote_map_count(roam_ctx *ctx, int64_t *received, int32_t *resident);
 int32_t roam_remote_map_get(roam_ctx *ctx, int32_t index, roam_keyframe_hdr *hdr_out, int32_t *root_out, double *locals_xy,
                             int32_t cap_pts, int32_t *peaks, int64_t peaks_cap);

@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("ROAM_LIB") or os.path.join(_HERE, "csrc", "libroam_hi
 
 ROAM_OK, ROAM_E_ARG, ROAM_E_HIP, ROAM_E_CAPACITY, ROAM_E_NODEVICE, ROAM_E_STATE = 0, -1, -2, -3, -4, -5
 WARP_POLAR_LOG, WARP_POLAR_INVERSE = 1, 2      # roam_abi.h ROAM_WARP_POLAR_*
+TIME_FFT_FIVE, TIME_DFT_FIVE, TIME_FFT_ROWS, TIME_FFT_TRANSPOSE, TIME_FFT_COLS = range(5)      # roam_abi.h ROAM_TIME_*
+PHASE_CORRELATE_MAX = 4096      # largest image side of roam_phase_correlate_f32
 MAX_FEATURES = 1024
 STEP_NEW_SEQUENCE = 0x40000000      # roam_abi.h ROAM_STEP_NEW_SEQUENCE: OR into a lane's scan index
 
@@ -112,6 +114,9 @@ _SIGS = {
     "roam_engine_time_kernel": (C.c_int32, [_vp, C.c_char_p, C.c_int32, _P(C.c_float), _P(C.c_double)]),
     "roam_engine_debug_detect": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp]),
     "roam_fmt_rotation": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
+    "roam_phase_correlate_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp]),
+    "roam_debug_fft2_f64": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "roam_time_fft2": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
     "roam_prune_blobs": (C.c_int32, [_vp, C.c_int32, C.c_double, _vp]),
     "roam_argsort_np122": (C.c_int32, [_vp, C.c_int32, _vp]),
     "roam_comm_available": (C.c_int32, []),
@@ -148,6 +153,30 @@ def peak_conditions(distance=None, prominence=None):
     nan = float("nan")
     return (0.0 if distance is None else float(distance),
             nan if pmin is None else float(pmin), nan if pmax is None else float(pmax))
+
+
+def phase_correlate_args(src, tgt):
+    """The argument checks of Context.phase_correlate, made before any device call -> (src, tgt) as arrays.  Different shapes:
+    AssertionError (the reference's assert); neither a 2-D image nor a 3-D batch, or a side outside [2, 4096]: ValueError."""
+    a, b = np.asarray(src), np.asarray(tgt)
+    assert a.shape == b.shape, "Images need to have the same shape!"
+    if a.ndim not in (2, 3):
+        raise ValueError(f"phase_correlate: two 2-D images or two 3-D batches, not {a.ndim}-D")
+    if a.ndim == 3 and a.shape[0] < 1:
+        raise ValueError("phase_correlate: an empty batch")
+    rows, cols = a.shape[-2:]
+    if not (2 <= rows <= PHASE_CORRELATE_MAX and 2 <= cols <= PHASE_CORRELATE_MAX):
+        raise ValueError(f"phase_correlate: image sides in [2, {PHASE_CORRELATE_MAX}], not {rows} x {cols}")
+    return a, b
+
+
+def _f32_rows_in_place(a):
+    """a float32 view with unit column stride and forward row / image strides is read in place; anything else is copied"""
+    ok = a.dtype == np.float32 and a.strides[-1] == 4 and a.strides[-2] % 4 == 0 and a.strides[-2] >= 4 * a.shape[-1]
+    if ok and a.ndim == 3:
+        ok = a.strides[0] % 4 == 0 and a.strides[0] >= (a.shape[1] - 1) * a.strides[1] + 4 * a.shape[2]
+    return a if ok else np.ascontiguousarray(a, np.float32)
+
 
 _lib = None
 
@@ -386,6 +415,43 @@ class Context:
         self.check(self.lib.roam_fmt_rotation(self.h, _ptr(a), _ptr(b), a.shape[0], a.shape[1], int(clip_px), int(downsample),
                                               C.byref(ang), C.byref(sc), C.byref(rs)))
         return ang.value, sc.value, rs.value
+
+    def phase_correlate(self, src, tgt, hanning=True):
+        """FMT.getTranslationUsingPhaseCorrelation: cv2.phaseCorrelate(src, tgt[, cv2.createHanningWindow((cols, rows), CV_32F)])
+        (roam_phase_correlate_f32).  Two 2-D images -> ((dx, dy), response); two 3-D batches of one shape -> (dxdy (n, 2),
+        response (n,)).  float32 views with unit column stride are read in place, anything else is made float32-contiguous."""
+        a, b = phase_correlate_args(src, tgt)
+        a, b = _f32_rows_in_place(a), _f32_rows_in_place(b)
+        batch = a.ndim == 3
+        a3, b3 = (a, b) if batch else (a[None], b[None])
+        n, rows, cols = a3.shape
+        if a3.strides[0 if n > 1 else 1:] != b3.strides[0 if n > 1 else 1:]:     # one pair of strides describes both operands
+            a3, b3 = np.ascontiguousarray(a3), np.ascontiguousarray(b3)
+        row_stride = a3.strides[1] // 4
+        image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+        dxdy = np.empty((n, 2), np.float64)
+        resp = np.empty(n, np.float64)
+        self.check(self.lib.roam_phase_correlate_f32(self.h, _ptr(a3), _ptr(b3), n, rows, cols, row_stride, image_stride,
+                                                     1 if hanning else 0, _ptr(dxdy), _ptr(resp)))
+        if batch:
+            return dxdy, resp
+        return (float(dxdy[0, 0]), float(dxdy[0, 1])), float(resp[0])
+
+    def debug_fft2(self, plane, inverse=False):
+        """test entry: the 2-D FFT of csrc/fft.hip alone on one complex (or real) float64 plane -> complex128; inverse: unscaled"""
+        z = np.asarray(plane)
+        re = np.ascontiguousarray(z.real, np.float64)
+        im = np.ascontiguousarray(z.imag, np.float64) if np.iscomplexobj(z) else None
+        rows, cols = re.shape
+        ro, io = np.empty_like(re), np.empty_like(re)
+        self.check(self.lib.roam_debug_fft2_f64(self.h, _ptr(re), _ptr(im), rows, cols, 1 if inverse else 0, _ptr(ro), _ptr(io)))
+        return ro + 1j * io
+
+    def time_fft2(self, rows, cols, what, reps=20):
+        """milliseconds per repetition of `what` (TIME_*) at rows x cols, by HIP events after two warm runs"""
+        ms = C.c_float(0)
+        self.check(self.lib.roam_time_fft2(self.h, int(rows), int(cols), int(what), int(reps), C.byref(ms)))
+        return float(ms.value)
 
     def doh_maxima(self, img, sigmas, threshold, cap=1 << 18):
         """-> (rcs (n,3) int32 [row, col, sigma_index] in C order, values (n,) f64)"""

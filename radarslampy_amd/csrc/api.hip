@@ -47,6 +47,7 @@ int32_t roam_destroy(roam_ctx *ctx)
     roam_engine_destroy(ctx);
     hipStreamSynchronize(ctx->stream);
     for (auto &s : ctx->scratch) if (s.p) hipFree(s.p);
+    roam_fft_release(ctx);
     hipStreamSynchronize(ctx->stream2);
     hipStreamSynchronize(ctx->stream4);
     hipStreamSynchronize(ctx->stream5);

@@ -1,0 +1,489 @@
+// Mixed-radix FFT (complex float64, n = 2^a 3^b 5^c <= 4096) and FMT.getTranslationUsingPhaseCorrelation (reference FMT.py:13-33:
+// cv2.createHanningWindow + cv2.phaseCorrelate on two images of any shape) on top of it.  docs/KERNELS.md "FFT" has the structure.
+//
+//   rows:     fft_rows_kernel transforms whole rows in LDS.  Stockham autosort, radix 4 / 2 / 3 / 5, ONE buffer of 4096 complex
+//             (real and imaginary parts in two arrays of doubles, 64 KB per workgroup; 512 threads): a stage reads the
+//             inputs of all of a thread's butterflies into registers, the workgroup meets at a barrier, and only then are the
+//             outputs written to their permuted places.  Rows shorter than 2048 share a workgroup (2048 / n of them).
+//   columns:  a tiled transpose through LDS (fft_transpose_kernel, 32 x 32 tiles, both sides coalesced) and the row kernel again.
+//             The forward transform of phase correlation leaves the spectrum transposed (N x M); the cross-power spectrum is
+//             element-wise, and the inverse transform starts from that layout (columns first), so a 2-D transform costs ONE transpose.
+//   twiddles: cos / sin of 2 pi m / n, m = 0 .. n - 1, made on the host in long double, one table per (context, length), uploaded on
+//             first use.  A butterfly's twiddle index r k n / (Ns R) is an exact integer below n: no angle is reduced on the device.
+//   inverse:  unscaled (cv2.idft without DFT_SCALE) as swap(FFT(swap(x))), swap = exchange of real and imaginary part: the launcher
+//             exchanges the plane pointers, the kernel is the forward one.
+#include "roam_internal.h"
+#include <math.h>
+
+#define FFT_MAX_N 4096
+#define FFT_THREADS 512
+#define FFT_MAX_STAGES 12
+#ifndef FFT_SHARE_ELEMS
+#define FFT_SHARE_ELEMS 2048            // rows shorter than this share a workgroup
+#endif
+
+struct FftPlan {
+    int n, nstages;
+    int radix[FFT_MAX_STAGES];
+};
+
+struct FftTwiddle {
+    int n;
+    double *cs;                         // device: cos[n] then sin[n]
+};
+struct FftTwiddles {
+    std::vector<FftTwiddle> tables;
+};
+
+static bool fft_plan(int n, FftPlan *p)
+{
+    p->n = n; p->nstages = 0;
+    if (n < 1 || n > FFT_MAX_N) return false;
+    int m = n;
+    // odd radices first: a stage's writes have stride R doubles while Ns < 16, conflict-free on the LDS banks only for odd R
+    while (m % 5 == 0) { p->radix[p->nstages++] = 5; m /= 5; }
+    while (m % 3 == 0) { p->radix[p->nstages++] = 3; m /= 3; }
+    int twos = 0;
+    for (int t = m; t % 2 == 0; t /= 2) twos++;
+    if (twos & 1) { p->radix[p->nstages++] = 2; m /= 2; }
+    while (m % 4 == 0) { p->radix[p->nstages++] = 4; m /= 4; }
+    return m == 1;
+}
+
+void roam_fft_release(roam_ctx *ctx)
+{
+    if (!ctx->fft_tw) return;
+    for (auto &t : ctx->fft_tw->tables) (void)hipFree(t.cs);
+    delete ctx->fft_tw;
+    ctx->fft_tw = nullptr;
+}
+
+static const double *fft_twiddles(roam_ctx *ctx, int n)
+{
+    if (!ctx->fft_tw) ctx->fft_tw = new FftTwiddles();
+    for (auto &t : ctx->fft_tw->tables) if (t.n == n) return t.cs;
+    std::vector<double> h(2 * (size_t)n);
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    for (int m = 0; m < n; m++) {
+        const long double a = two_pi * (long double)m / (long double)n;
+        h[m] = (double)cosl(a); h[n + m] = (double)sinl(a);
+    }
+    FftTwiddle t{n, nullptr};
+    if (hipMalloc((void **)&t.cs, sizeof(double) * h.size()) != hipSuccess ||
+        hipMemcpy(t.cs, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        ROAM_SET_ERR(ctx, "twiddle table of length %d: allocation or upload failed", n);
+        if (t.cs) (void)hipFree(t.cs);
+        return nullptr;
+    }
+    ctx->fft_tw->tables.push_back(t);
+    return t.cs;
+}
+
+// forward DFT of R points in place (w = exp(-2 pi i / R))
+template <int R> __device__ __forceinline__ void fft_butterfly(double *xr, double *xi);
+
+template <> __device__ __forceinline__ void fft_butterfly<2>(double *xr, double *xi)
+{
+    const double ar = xr[0], ai = xi[0];
+    xr[0] = ar + xr[1]; xi[0] = ai + xi[1];
+    xr[1] = ar - xr[1]; xi[1] = ai - xi[1];
+}
+
+template <> __device__ __forceinline__ void fft_butterfly<3>(double *xr, double *xi)
+{
+    const double s60 = 0.86602540378443864676;
+    const double sr = xr[1] + xr[2], si = xi[1] + xi[2], dr = xr[1] - xr[2], di = xi[1] - xi[2];
+    const double mr = xr[0] - 0.5 * sr, mi = xi[0] - 0.5 * si, er = s60 * di, ei = -(s60 * dr);
+    xr[0] = xr[0] + sr; xi[0] = xi[0] + si;
+    xr[1] = mr + er; xi[1] = mi + ei;
+    xr[2] = mr - er; xi[2] = mi - ei;
+}
+
+template <> __device__ __forceinline__ void fft_butterfly<4>(double *xr, double *xi)
+{
+    const double t0r = xr[0] + xr[2], t0i = xi[0] + xi[2], t1r = xr[0] - xr[2], t1i = xi[0] - xi[2];
+    const double t2r = xr[1] + xr[3], t2i = xi[1] + xi[3], t3r = xr[1] - xr[3], t3i = xi[1] - xi[3];
+    xr[0] = t0r + t2r; xi[0] = t0i + t2i;
+    xr[2] = t0r - t2r; xi[2] = t0i - t2i;
+    xr[1] = t1r + t3i; xi[1] = t1i - t3r;
+    xr[3] = t1r - t3i; xi[3] = t1i + t3r;
+}
+
+template <> __device__ __forceinline__ void fft_butterfly<5>(double *xr, double *xi)
+{
+    const double c1 = 0.30901699437494742410, c2 = -0.80901699437494742410, s1 = 0.95105651629515357212, s2 = 0.58778525229247312917;
+    const double p1r = xr[1] + xr[4], p1i = xi[1] + xi[4], p2r = xr[2] + xr[3], p2i = xi[2] + xi[3];
+    const double d1r = xr[1] - xr[4], d1i = xi[1] - xi[4], d2r = xr[2] - xr[3], d2i = xi[2] - xi[3];
+    const double m1r = xr[0] + (c1 * p1r + c2 * p2r), m1i = xi[0] + (c1 * p1i + c2 * p2i);
+    const double m2r = xr[0] + (c2 * p1r + c1 * p2r), m2i = xi[0] + (c2 * p1i + c1 * p2i);
+    const double n1r = s1 * d1r + s2 * d2r, n1i = s1 * d1i + s2 * d2i;
+    const double n2r = s2 * d1r - s1 * d2r, n2i = s2 * d1i - s1 * d2i;
+    xr[0] = xr[0] + (p1r + p2r); xi[0] = xi[0] + (p1i + p2i);
+    xr[1] = m1r + n1i; xi[1] = m1i - n1r;
+    xr[4] = m1r - n1i; xi[4] = m1i + n1r;
+    xr[2] = m2r + n2i; xi[2] = m2i - n2r;
+    xr[3] = m2r - n2i; xi[3] = m2i + n2r;
+}
+
+// one Stockham stage of radix R over `rows_here` rows of length n held in sr / si; Ns = the product of the radices already done.
+// butterfly j of a row reads x[j + r n / R], multiplies by w^(r k), k = j mod Ns, w = exp(-2 pi i / (Ns R)), and writes
+// y[(j / Ns) Ns R + k + r Ns].  All reads of the workgroup happen before its first write (one buffer).
+template <int R>
+__device__ __forceinline__ void fft_stage(double *sr, double *si, const double *__restrict__ twc, const double *__restrict__ tws,
+                                          int n, int rows_here, int Ns)
+{
+    constexpr int NB = (FFT_MAX_N / R + FFT_THREADS - 1) / FFT_THREADS;
+    const int q = n / R, nb = rows_here * q, tstep = n / (Ns * R);
+    double vr[NB][R], vi[NB][R];
+    int dst[NB];
+#pragma unroll
+    for (int u = 0; u < NB; u++) {
+        const int b = (int)threadIdx.x + u * FFT_THREADS;
+        dst[u] = -1;
+        if (b < nb) {
+            const int row = b / q, j = b - row * q, k = j % Ns;
+            const int src = row * n + j;
+            vr[u][0] = sr[src]; vi[u][0] = si[src];
+#pragma unroll
+            for (int r = 1; r < R; r++) {
+                const double xr = sr[src + r * q], xi = si[src + r * q];
+                const int m = r * k * tstep;
+                const double c = twc[m], s = -tws[m];
+                vr[u][r] = xr * c - xi * s; vi[u][r] = xr * s + xi * c;
+            }
+            fft_butterfly<R>(vr[u], vi[u]);
+            dst[u] = row * n + (j - k) * R + k;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < NB; u++)
+        if (dst[u] >= 0) {
+#pragma unroll
+            for (int r = 0; r < R; r++) { sr[dst[u] + r * Ns] = vr[u][r]; si[dst[u] + r * Ns] = vi[u][r]; }
+        }
+    __syncthreads();
+}
+
+// forward FFT of total_rows contiguous rows of length plan.n; rows_per_wg rows per workgroup (rows_per_wg * n <= 4096).
+// re_in or im_in may be null (zeros), re_out or im_out may be null (not stored); in and out may be the same planes.
+__global__ __launch_bounds__(FFT_THREADS) void fft_rows_kernel(const double *re_in, const double *im_in, double *re_out, double *im_out,
+                                                               int64_t total_rows, FftPlan plan, int rows_per_wg,
+                                                               const double *__restrict__ twc, const double *__restrict__ tws)
+{
+    __shared__ double sr[FFT_MAX_N], si[FFT_MAX_N];
+    const int n = plan.n, t = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * rows_per_wg;
+    const int64_t left = total_rows - row0;
+    const int rows_here = left < rows_per_wg ? (int)left : rows_per_wg;
+    const int cnt = rows_here * n;
+    const int64_t base = row0 * n;
+    for (int i = t; i < cnt; i += FFT_THREADS) {
+        sr[i] = re_in ? re_in[base + i] : 0.0;
+        si[i] = im_in ? im_in[base + i] : 0.0;
+    }
+    __syncthreads();
+    int Ns = 1;
+    for (int s = 0; s < plan.nstages; s++) {
+        const int R = plan.radix[s];
+        if (R == 4) fft_stage<4>(sr, si, twc, tws, n, rows_here, Ns);
+        else if (R == 2) fft_stage<2>(sr, si, twc, tws, n, rows_here, Ns);
+        else if (R == 3) fft_stage<3>(sr, si, twc, tws, n, rows_here, Ns);
+        else fft_stage<5>(sr, si, twc, tws, n, rows_here, Ns);
+        Ns *= R;
+    }
+    for (int i = t; i < cnt; i += FFT_THREADS) {
+        if (re_out) re_out[base + i] = sr[i];
+        if (im_out) im_out[base + i] = si[i];
+    }
+}
+
+// (batch) M x N -> N x M, both planes; block (32, 8), grid (ceil(N / 32), ceil(M / 32), batch)
+__global__ __launch_bounds__(256) void fft_transpose_kernel(const double *__restrict__ re_in, const double *__restrict__ im_in, int M, int N,
+                                                            double *__restrict__ re_out, double *__restrict__ im_out)
+{
+    __shared__ double tr[32][33], ti[32][33];
+    const int64_t plane = (int64_t)blockIdx.z * M * N;
+    const int x0 = blockIdx.x * 32, y0 = blockIdx.y * 32;
+    for (int dy = threadIdx.y; dy < 32; dy += 8) {
+        const int x = x0 + threadIdx.x, y = y0 + dy;
+        if (x < N && y < M) { tr[dy][threadIdx.x] = re_in[plane + (int64_t)y * N + x]; ti[dy][threadIdx.x] = im_in[plane + (int64_t)y * N + x]; }
+    }
+    __syncthreads();
+    for (int dx = threadIdx.y; dx < 32; dx += 8) {
+        const int y = y0 + threadIdx.x, x = x0 + dx;
+        if (x < N && y < M) { re_out[plane + (int64_t)x * M + y] = tr[threadIdx.x][dx]; im_out[plane + (int64_t)x * M + y] = ti[threadIdx.x][dx]; }
+    }
+}
+
+static int32_t fft_rows(roam_ctx *ctx, const double *re_in, const double *im_in, double *re_out, double *im_out, int64_t total_rows, int n,
+                        bool inverse)
+{
+    FftPlan plan;
+    if (!fft_plan(n, &plan)) { ROAM_SET_ERR(ctx, "FFT length %d is not 2^a 3^b 5^c <= %d", n, FFT_MAX_N); return ROAM_E_ARG; }
+    const double *tw = fft_twiddles(ctx, n);
+    if (!tw) return ROAM_E_HIP;
+    int rpw = FFT_SHARE_ELEMS / n;
+    if (rpw < 1) rpw = 1;
+    const int64_t groups = (total_rows + rpw - 1) / rpw;
+    if (inverse) { const double *ti = re_in; re_in = im_in; im_in = ti; double *to = re_out; re_out = im_out; im_out = to; }
+    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)groups), dim3(FFT_THREADS), 0, ctx->stream, re_in, im_in, re_out, im_out, total_rows, plan,
+                       rpw, tw, tw + n);
+    HIP_TRY(ctx, hipGetLastError());
+    return ROAM_OK;
+}
+
+static int32_t fft_transpose(roam_ctx *ctx, const double *re_in, const double *im_in, int batch, int M, int N, double *re_out, double *im_out)
+{
+    hipLaunchKernelGGL(fft_transpose_kernel, dim3((N + 31) / 32, (M + 31) / 32, batch), dim3(32, 8), 0, ctx->stream, re_in, im_in, M, N, re_out,
+                       im_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return ROAM_OK;
+}
+
+#define FFT_TRY(call) do { const int32_t rc_ = (call); if (rc_ != ROAM_OK) return rc_; } while (0)
+
+// ------------------------------------------------------------------------------------------------ phase correlation
+// window (cv2.createHanningWindow: sqrt(float32(wr[y] wc[x])) from the float64 factors) times image, rounded to float32, zero-padded
+// into the M x N float64 plane.  wr == null: no window.  grid (ceil(N / 256), M, batch)
+__global__ __launch_bounds__(256) void pc_window_kernel(const float *__restrict__ img, int rows, int cols, const double *__restrict__ wr,
+                                                        const double *__restrict__ wc, int M, int N, double *__restrict__ out)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+    if (x >= N) return;
+    double val = 0.0;
+    if (x < cols && y < rows) {
+        const float v = img[((int64_t)b * rows + y) * cols + x];
+        val = wr ? (double)__fmul_rn(rn_sqrtf((float)(wr[y] * wc[x])), v) : (double)v;
+    }
+    out[((int64_t)b * M + y) * N + x] = val;
+}
+
+// np.fft.fftshift: shifted[i] = plane[(i + n - n / 2) mod n]
+__device__ __forceinline__ double pc_shifted(const double *__restrict__ c, int M, int N, int y, int x)
+{
+    int sy = y + M - M / 2, sx = x + N - N / 2;
+    if (sy >= M) sy -= M;
+    if (sx >= N) sx -= N;
+    return c[(int64_t)sy * N + sx];
+}
+
+// stage 1 of the peak search: block (blk, b) scans the indices [blk per, (blk + 1) per) of plane b's SHIFTED image in row-major
+// order and leaves its maximum and the lowest index that holds it
+__global__ __launch_bounds__(256) void pc_peak_partial_kernel(const double *__restrict__ c, int M, int N, int per, double *__restrict__ pv,
+                                                              int *__restrict__ pi)
+{
+    __shared__ double bv[256];
+    __shared__ int bi[256];
+    const int t = threadIdx.x, n = M * N, b = blockIdx.y;
+    const double *pl = c + (int64_t)b * n;
+    const int k0 = blockIdx.x * per, k1 = min(n, k0 + per);
+    double best = -1e300; int besti = n;
+    for (int k = k0 + t; k < k1; k += 256) {
+        const int y = k / N, x = k - y * N;
+        const double v = pc_shifted(pl, M, N, y, x);
+        if (v > best) { best = v; besti = k; }
+    }
+    bv[t] = best; bi[t] = besti;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (t < s && (bv[t + s] > bv[t] || (bv[t + s] == bv[t] && bi[t + s] < bi[t]))) { bv[t] = bv[t + s]; bi[t] = bi[t + s]; }
+        __syncthreads();
+    }
+    if (t == 0) { pv[(int64_t)b * gridDim.x + blockIdx.x] = bv[0]; pi[(int64_t)b * gridDim.x + blockIdx.x] = bi[0]; }
+}
+
+// stage 2: the first maximum of plane b among its nblk partial results, then the 5 x 5 weighted centroid on the plane scaled by
+// 1 / (M N) (the inverse transform is unscaled) -> out3[b] = {dx, dy, response}.  One workgroup per plane.
+__global__ __launch_bounds__(256) void pc_peak_final_kernel(const double *__restrict__ c, int M, int N, int nblk, const double *__restrict__ pv,
+                                                            const int *__restrict__ pi, double *__restrict__ out3)
+{
+    __shared__ double bv[256];
+    __shared__ int bi[256];
+    const int t = threadIdx.x, n = M * N, b = blockIdx.x;
+    const double *pl = c + (int64_t)b * n;
+    double best = -1e300; int besti = n;
+    for (int k = t; k < nblk; k += 256) {
+        const double v = pv[(int64_t)b * nblk + k]; const int i = pi[(int64_t)b * nblk + k];
+        if (v > best || (v == best && i < besti)) { best = v; besti = i; }
+    }
+    bv[t] = best; bi[t] = besti;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (t < s && (bv[t + s] > bv[t] || (bv[t + s] == bv[t] && bi[t + s] < bi[t]))) { bv[t] = bv[t + s]; bi[t] = bi[t + s]; }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const int at = bi[0] < n ? bi[0] : 0;               // a plane without a finite value: the centroid of its corner (NaN out)
+        const int py = at / N, px = at - py * N;
+        const int r0 = max(py - 2, 0), r1 = min(py + 2, M - 1), c0 = max(px - 2, 0), c1 = min(px + 2, N - 1);
+        const double inv = 1.0 / ((double)M * (double)N);
+        double sx = 0, sy = 0, sum = 0;
+        for (int y = r0; y <= r1; y++)
+            for (int x = c0; x <= c1; x++) {
+                const double v = pc_shifted(pl, M, N, y, x) * inv;
+                sx += (double)x * v; sy += (double)y * v; sum += v;
+            }
+        const double den = sum + 2.220446049250313e-16;
+        out3[3 * b + 0] = (double)N / 2.0 - sx / den;
+        out3[3 * b + 1] = (double)M / 2.0 - sy / den;
+        out3[3 * b + 2] = sum;
+    }
+}
+
+static bool fft_smooth(int n)
+{
+    FftPlan p;
+    return fft_plan(n, &p);
+}
+
+extern "C" int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t batch, int32_t rows, int32_t cols,
+                                            int64_t row_stride, int64_t image_stride, int32_t hanning, double *out_dxdy, double *out_response)
+{
+    if (!ctx) return ROAM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ARG_CHECK(ctx, src && tgt && out_dxdy && batch >= 1);
+    ARG_CHECK(ctx, rows >= 2 && rows <= FFT_MAX_N && cols >= 2 && cols <= FFT_MAX_N);
+    ARG_CHECK(ctx, row_stride >= cols && (batch == 1 || image_stride >= (int64_t)(rows - 1) * row_stride + cols));
+    const int M = optimal_dft_size(rows), N = optimal_dft_size(cols);
+    const size_t nmn = (size_t)M * N, nimg = (size_t)rows * cols;
+    // per pair: 7 float64 planes (windowed image | work re, im | F1 re, im | F2 re, im) and the two float32 images
+    const size_t per_pair = 7 * sizeof(double) * nmn + 2 * sizeof(float) * nimg;
+    size_t chunk = ((size_t)2000 << 20) / per_pair;
+    if (chunk < 1) chunk = 1;
+    if (chunk > (size_t)batch) chunk = batch;
+    if (chunk > 32768) chunk = 32768;
+    const int per = (int)((nmn + 1023) / 1024) < 1024 ? 1024 : (int)((nmn + 1023) / 1024);     // indices per stage-1 block: at most 1024 blocks
+    const int nblk = (int)((nmn + per - 1) / per);
+    hipStream_t st = ctx->stream;
+    float *d_src = (float *)roam_scratch(ctx, S_IN0, sizeof(float) * nimg * chunk);
+    float *d_tgt = (float *)roam_scratch(ctx, S_IN1, sizeof(float) * nimg * chunk);
+    double *d_f = (double *)roam_scratch(ctx, S_TMP2, sizeof(double) * nmn * 7 * chunk);
+    double *d_win = (double *)roam_scratch(ctx, S_TMP1, sizeof(double) * ((size_t)rows + cols));
+    double *d_pv = (double *)roam_scratch(ctx, S_TMP0, sizeof(double) * (size_t)nblk * chunk);
+    int *d_pi = (int *)roam_scratch(ctx, S_TMP3, sizeof(int) * (size_t)nblk * chunk);
+    double *d_out = (double *)roam_scratch(ctx, S_OUT0, sizeof(double) * 3 * chunk);
+    if (!d_src || !d_tgt || !d_f || !d_win || !d_pv || !d_pi || !d_out) return ROAM_E_HIP;
+    std::vector<double> win((size_t)rows + cols), o(3 * chunk);
+    if (hanning) {
+        for (int y = 0; y < rows; y++) win[y] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(rows - 1) * (double)y));
+        for (int x = 0; x < cols; x++) win[rows + x] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(cols - 1) * (double)x));
+        HIP_TRY(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(double) * win.size(), hipMemcpyHostToDevice, st));
+    }
+    for (size_t b0 = 0; b0 < (size_t)batch; b0 += chunk) {
+        const int nb = (int)(((size_t)batch - b0) < chunk ? ((size_t)batch - b0) : chunk);
+        const size_t pl = nmn * nb;                          // one plane of the chunk
+        double *a = d_f, *tr = d_f + pl, *ti = d_f + 2 * pl, *F[2][2] = {{d_f + 3 * pl, d_f + 4 * pl}, {d_f + 5 * pl, d_f + 6 * pl}};
+        const float *host[2] = {src, tgt};
+        float *dev[2] = {d_src, d_tgt};
+        for (int k = 0; k < 2; k++) {
+            for (int i = 0; i < nb; i++) {
+                const float *h = host[k] + (int64_t)(b0 + i) * image_stride;
+                if (row_stride == cols)                      // a 2-D copy moves the rows one by one
+                    HIP_TRY(ctx, hipMemcpyAsync(dev[k] + (size_t)i * nimg, h, sizeof(float) * nimg, hipMemcpyHostToDevice, st));
+                else
+                    HIP_TRY(ctx, hipMemcpy2DAsync(dev[k] + (size_t)i * nimg, sizeof(float) * cols, h, sizeof(float) * row_stride,
+                                                  sizeof(float) * cols, rows, hipMemcpyHostToDevice, st));
+            }
+            hipLaunchKernelGGL(pc_window_kernel, dim3((N + 255) / 256, M, nb), dim3(256), 0, st, dev[k], rows, cols,
+                               hanning ? d_win : (const double *)nullptr, d_win + rows, M, N, a);
+            HIP_TRY(ctx, hipGetLastError());
+            FFT_TRY(fft_rows(ctx, a, nullptr, tr, ti, (int64_t)nb * M, N, false));
+            FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, F[k][0], F[k][1]));
+            FFT_TRY(fft_rows(ctx, F[k][0], F[k][1], F[k][0], F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
+        }
+        HIP_TRY(ctx, launch_fmt_cross_power(st, F[0][0], F[0][1], F[1][0], F[1][1], (int)pl, tr, ti));
+        FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
+        FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, F[0][0], F[0][1]));
+        FFT_TRY(fft_rows(ctx, F[0][0], F[0][1], a, nullptr, (int64_t)nb * M, N, true));                  // real part only
+        hipLaunchKernelGGL(pc_peak_partial_kernel, dim3(nblk, nb), dim3(256), 0, st, a, M, N, per, d_pv, d_pi);
+        hipLaunchKernelGGL(pc_peak_final_kernel, dim3(nb), dim3(256), 0, st, a, M, N, nblk, d_pv, d_pi, d_out);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (int i = 0; i < nb; i++) {
+            out_dxdy[2 * (b0 + i)] = o[3 * i]; out_dxdy[2 * (b0 + i) + 1] = o[3 * i + 1];
+            if (out_response) out_response[b0 + i] = o[3 * i + 2];
+        }
+    }
+    return ROAM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ test / measurement entries
+extern "C" int32_t roam_debug_fft2_f64(roam_ctx *ctx, const double *re_in, const double *im_in, int32_t rows, int32_t cols, int32_t inverse,
+                                       double *re_out, double *im_out)
+{
+    if (!ctx) return ROAM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ARG_CHECK(ctx, re_in && re_out && im_out && rows >= 1 && rows <= FFT_MAX_N && cols >= 1 && cols <= FFT_MAX_N);
+    ARG_CHECK(ctx, fft_smooth(rows) && fft_smooth(cols));
+    const int M = rows, N = cols;
+    const size_t nmn = (size_t)M * N;
+    double *d = (double *)roam_scratch(ctx, S_TMP2, sizeof(double) * nmn * 4);
+    if (!d) return ROAM_E_HIP;
+    double *ar = d, *ai = d + nmn, *br = d + 2 * nmn, *bi = d + 3 * nmn;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(ar, re_in, sizeof(double) * nmn, hipMemcpyHostToDevice, st));
+    if (im_in) HIP_TRY(ctx, hipMemcpyAsync(ai, im_in, sizeof(double) * nmn, hipMemcpyHostToDevice, st));
+    else HIP_TRY(ctx, hipMemsetAsync(ai, 0, sizeof(double) * nmn, st));
+    FFT_TRY(fft_rows(ctx, ar, ai, ar, ai, M, N, inverse != 0));
+    FFT_TRY(fft_transpose(ctx, ar, ai, 1, M, N, br, bi));
+    FFT_TRY(fft_rows(ctx, br, bi, br, bi, N, M, inverse != 0));
+    FFT_TRY(fft_transpose(ctx, br, bi, 1, N, M, ar, ai));
+    HIP_TRY(ctx, hipMemcpyAsync(re_out, ar, sizeof(double) * nmn, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(im_out, ai, sizeof(double) * nmn, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return ROAM_OK;
+}
+
+extern "C" int32_t roam_time_fft2(roam_ctx *ctx, int32_t rows, int32_t cols, int32_t what, int32_t reps, float *ms_per_rep)
+{
+    if (!ctx) return ROAM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ARG_CHECK(ctx, ms_per_rep && reps >= 1 && what >= 0 && what <= 4 && rows >= 2 && rows <= FFT_MAX_N && cols >= 2 && cols <= FFT_MAX_N);
+    ARG_CHECK(ctx, fft_smooth(rows) && fft_smooth(cols));
+    ARG_CHECK(ctx, what != ROAM_TIME_DFT_FIVE || (int64_t)rows * cols <= (1 << 17));       // the direct form is O(M N (M + N))
+    const int M = rows, N = cols;
+    const size_t nmn = (size_t)M * N;
+    double *d = (double *)roam_scratch(ctx, S_TMP2, sizeof(double) * nmn * 7);
+    if (!d) return ROAM_E_HIP;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemsetAsync(d, 0, sizeof(double) * nmn * 7, st));
+    double *a = d, *tr = d + nmn, *ti = d + 2 * nmn, *F[2][2] = {{d + 3 * nmn, d + 4 * nmn}, {d + 5 * nmn, d + 6 * nmn}};
+    hipEvent_t e0, e1;
+    HIP_TRY(ctx, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); ROAM_SET_ERR(ctx, "hipEventCreate failed"); return ROAM_E_HIP; }
+    int32_t rc = ROAM_OK;
+    for (int rep = -2; rep < reps && rc == ROAM_OK; rep++) {                 // two warm runs (they also upload the twiddle tables)
+        if (rep == 0) (void)hipEventRecord(e0, st);
+        if (what == ROAM_TIME_FFT_FIVE) {
+            for (int k = 0; k < 2 && rc == ROAM_OK; k++) {
+                rc = fft_rows(ctx, a, nullptr, tr, ti, M, N, false);
+                if (rc == ROAM_OK) rc = fft_transpose(ctx, tr, ti, 1, M, N, F[k][0], F[k][1]);
+                if (rc == ROAM_OK) rc = fft_rows(ctx, F[k][0], F[k][1], F[k][0], F[k][1], N, M, false);
+            }
+            if (rc == ROAM_OK) rc = fft_rows(ctx, tr, ti, tr, ti, N, M, true);
+            if (rc == ROAM_OK) rc = fft_transpose(ctx, tr, ti, 1, N, M, F[0][0], F[0][1]);
+            if (rc == ROAM_OK) rc = fft_rows(ctx, F[0][0], F[0][1], a, nullptr, M, N, true);
+        } else if (what == ROAM_TIME_DFT_FIVE) {
+            for (int k = 0; k < 2; k++) (void)launch_fmt_dft2(st, a, nullptr, M, N, -1.0, tr, ti, F[k][0], F[k][1]);
+            (void)launch_fmt_dft2(st, tr, ti, M, N, 1.0, F[0][0], F[0][1], a, nullptr);
+        } else if (what == ROAM_TIME_FFT_ROWS) {
+            rc = fft_rows(ctx, tr, ti, tr, ti, M, N, false);
+        } else if (what == ROAM_TIME_FFT_TRANSPOSE) {
+            rc = fft_transpose(ctx, tr, ti, 1, M, N, F[0][0], F[0][1]);
+        } else {
+            rc = fft_rows(ctx, tr, ti, tr, ti, N, M, false);
+        }
+    }
+    (void)hipEventRecord(e1, st);
+    hipError_t e = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (rc != ROAM_OK) return rc;
+    HIP_TRY(ctx, e);
+    HIP_TRY(ctx, hipGetLastError());
+    *ms_per_rep = ms / (float)reps;
+    return ROAM_OK;
+}

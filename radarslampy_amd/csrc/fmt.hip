@@ -188,7 +188,23 @@ __global__ __launch_bounds__(256) void fmt_peak_kernel(const double *__restrict_
     }
 }
 
-static int optimal_dft_size(int n)
+hipError_t launch_fmt_cross_power(hipStream_t st, const double *r1, const double *i1, const double *r2, const double *i2, int n, double *cr,
+                                  double *ci)
+{
+    hipLaunchKernelGGL(fmt_cross_power_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r1, i1, r2, i2, n, cr, ci);
+    return hipGetLastError();
+}
+
+hipError_t launch_fmt_dft2(hipStream_t st, const double *re_in, const double *im_in, int M, int N, double sign, double *tmp_re, double *tmp_im,
+                           double *re_out, double *im_out)
+{
+    const dim3 gmn((N + 63) / 64, M);
+    hipLaunchKernelGGL(fmt_dft_x_kernel, gmn, dim3(64), 0, st, re_in, im_in, M, N, sign, tmp_re, tmp_im);
+    hipLaunchKernelGGL(fmt_dft_y_kernel, gmn, dim3(64), 0, st, tmp_re, tmp_im, M, N, sign, re_out, im_out);
+    return hipGetLastError();
+}
+
+int optimal_dft_size(int n)
 {
     int best = 0;
     for (long p2 = 1; p2 < 2L * n; p2 *= 2)

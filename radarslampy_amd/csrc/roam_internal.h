@@ -22,6 +22,7 @@ struct DevBuf {
 
 struct Engine;
 struct Comm;
+struct FftTwiddles;
 
 struct roam_ctx {
     int device = 0;
@@ -37,6 +38,7 @@ struct roam_ctx {
     int cu_count = 0;
     Engine *engine = nullptr;
     Comm *comm = nullptr;              // RCCL communicator (comm.hip), optional
+    FftTwiddles *fft_tw = nullptr;     // twiddle tables by FFT length (fft.hip), made on first use
 };
 
 #define ROAM_SET_ERR(ctx, ...) snprintf((ctx)->err, sizeof((ctx)->err), __VA_ARGS__)
@@ -181,3 +183,14 @@ int32_t roam_comm_bcast_bytes(roam_ctx *ctx, void *dev_buf, size_t bytes, int ro
 int roam_comm_rank(const roam_ctx *ctx);
 int roam_comm_world(const roam_ctx *ctx);
 int32_t roam_comm_allgather_bytes(roam_ctx *ctx, const void *send, void *recv, size_t bytes, hipStream_t st);
+
+// fmt.hip kernels for fft.hip: the normalised cross-power spectrum of n bins (fmt_cross_power_kernel), and one direct 2-D DFT
+// (fmt_dft_x_kernel into tmp, then fmt_dft_y_kernel; im_in / im_out may be null) for timing the FFT against it
+hipError_t launch_fmt_cross_power(hipStream_t st, const double *r1, const double *i1, const double *r2, const double *i2, int n, double *cr,
+                                  double *ci);
+hipError_t launch_fmt_dft2(hipStream_t st, const double *re_in, const double *im_in, int M, int N, double sign, double *tmp_re, double *tmp_im,
+                           double *re_out, double *im_out);
+// fmt.hip: cv2.getOptimalDFTSize: the smallest 2^a 3^b 5^c >= n
+int optimal_dft_size(int n);
+// fft.hip: free the context's twiddle tables
+void roam_fft_release(roam_ctx *ctx);
