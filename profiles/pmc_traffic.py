@@ -3,7 +3,7 @@
 kernel and launch of `units` detections - memory-side bytes (gfx950-corrected as MI355X_MICROARCH.md prescribes: FETCH_SIZE
 tallies 128-byte requests at 64 bytes, x 2; cross-check TCC_MISS x 128 B), VALU wave-instructions, LDS array cycles - together
 with the hash of the kernel's source file, so that bench.py can tell whether the numbers still describe the code it runs.
-The hash is the one profiles/pmc_det.sh wrote NEXT TO the counters when it measured (source_fingerprint.txt: the translation unit,
+The hash is the one profiles/pmc_det.sh wrote NEXT TO the counters when it measured (source_fingerprint_<unit>.txt: the translation unit,
 every header of csrc/ and the build flags - radarslampy_amd/build.py fingerprint), not one taken when this script runs.
 Round 6: the integral image counts with the tiles that exist (the ones rt_det_strip_kernel loads and rt_integral_kernel therefore
 writes: 87.7 % of a 2024 x 2024 image, retrack_build_phases) - IMAGE_FRACTION below.
@@ -25,17 +25,22 @@ def collect(counter):
 C = {c: collect(c) for c in ("FETCH_SIZE", "WRITE_SIZE", "TCC_MISS_sum", "TCC_HIT_sum", "TCC_EA0_RDREQ_sum", "TCP_TCC_READ_REQ_sum",
                              "SQ_INSTS_VALU", "SQ_INSTS_LDS", "SQ_LDS_IDX_ACTIVE", "SQ_LDS_BANK_CONFLICT", "GRBM_GUI_ACTIVE")}
 IMAGE_FRACTION = 0.8770                       # needed tiles / all tiles of the 2024 x 2024 image (engine: rt_image_px; 0.8789 with the 32-row tiles of -DRI_ROWS=32)
-ALGO = {"rt_det_strip_kernel": ("retrack.hip", IMAGE_FRACTION * 2024 * 2024 * 8.0,
+ALGO = {"rt_det_strip_kernel": ("retrack_det.hip", IMAGE_FRACTION * 2024 * 2024 * 8.0,
                                 "float64 integral image marched in 62-column strips through an LDS ring: memory-side reads {ratio:.2f} x the algorithmic bytes "
                                 "(L2 hit rate {hit:.0%} on the lines neighbouring strips share); VALU issue, LDS array and HBM each about half busy - "
                                 "a step's phases (staging, per-wave skip test, 16 box pairs, maxima, barrier) run one after the other inside a workgroup "
                                 "and only two workgroups fit a CU (74 KB of LDS each)"),
-        "rt_integral_kernel": ("retrack.hip", 400 * 2025 + IMAGE_FRACTION * 2024 * 2024 * 8.0,
+        "rt_integral_kernel": ("retrack_integral.hip", 400 * 2025 + IMAGE_FRACTION * 2024 * 2024 * 8.0,
                                "one sweep, both float64 prefix sums in NumPy's sequential order, the tiles the determinant kernel reads written once (28.7 MB per detection; algorithmic "
                                "bytes = polar payload + that image, the sampling-map words it also reads are the same table for every detection and mostly L2 hits: "
                                "memory-side {ratio:.2f} x algorithmic, L2 hit rate {hit:.0%}); latency chain of ~955 phases per detection, two workgroups per CU")}
-fp_file = os.path.join(root, "source_fingerprint.txt")
-FP = open(fp_file).read().strip() if os.path.exists(fp_file) else None
+
+
+def measured_fingerprint(src):
+    fp_file = os.path.join(root, f"source_fingerprint_{src}.txt")
+    return open(fp_file).read().strip() if os.path.exists(fp_file) else None
+
+
 kernels = {}
 for k, (src, algo, note) in ALGO.items():
     if k not in C["FETCH_SIZE"]:
@@ -45,7 +50,7 @@ for k, (src, algo, note) in ALGO.items():
     miss = C["TCC_MISS_sum"].get(k, 0.0) * 128.0
     hit = C["TCC_HIT_sum"].get(k, 0.0)
     req = hit + C["TCC_MISS_sum"].get(k, 0.0)
-    kernels[k] = {"source_file": src, "source_fingerprint": FP,
+    kernels[k] = {"source_file": src, "source_fingerprint": measured_fingerprint(src),
                   "algorithmic_bytes_per_launch": int(algo * units),
                   "fetch_bytes_uncorrected": int(C["FETCH_SIZE"][k] * 1024), "fetch_bytes_x2_gfx950": int(f2), "tcc_miss_x_128B": int(miss),
                   "write_bytes": int(w), "hbm_bytes_per_launch_corrected": int(f2 + w),

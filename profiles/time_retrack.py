@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""cost of the device-side retrack (retrack.hip): B lanes that ALL run out of features in one step.
+"""cost of the device-side retrack (retrack.hip and the retrack_*.hip units): B lanes that ALL run out of features in one step.
 usage: python profiles/time_retrack.py [lanes] [slots]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -13,10 +13,14 @@ LIB = os.path.join(CSRC, "libroam_hip.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
-# per-file additions.  retrack.hip: its determinant kernel lives on 8-byte LDS reads, and the backend's load/store optimizer pairs them
-# into ds_read2_b64, which moves 8 bytes per lane at HALF the rate of ds_read_b64 on gfx950 (128 against 256 B/clk per CU)
+# per-file additions.  retrack_det.hip: its determinant kernel lives on 8-byte LDS reads, and the backend's load/store optimizer pairs them
+# into ds_read2_b64, which moves 8 bytes per lane at HALF the rate of ds_read_b64 on gfx950 (128 against 256 B/clk per CU).
+# The other three retrack units were one file with it and keep the flags because their machine code is not the same without them
+# (device assembly compared kernel by kernel): retrack_integral.hip - rt_integral_kernel, rt_integ_cols_kernel, rt_integ_rows_kernel (328
+# instead of 324 registers), rt_boxtab_kernel; retrack_blobs.hip - rt_emit_kernel, rt_blobs_kernel<true/false>, rt_book_kernel;
+# retrack.hip - rt_collect_kernel, rt_append_kernel.  Whether the paired form is any slower there has not been measured.
 NO_PAIRING = ["-Xclang", "-target-feature", "-Xclang", "-load-store-opt", "-mllvm", "-amdgpu-load-store-vectorizer=0"]
-EXTRA = {"retrack.hip": NO_PAIRING}
+EXTRA = {f: NO_PAIRING for f in ("retrack.hip", "retrack_integral.hip", "retrack_det.hip", "retrack_blobs.hip")}
 
 
 def fingerprint(sources):

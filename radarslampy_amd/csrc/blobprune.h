@@ -1,6 +1,6 @@
 // blobprune.h - the ORDER-DEPENDENT bookkeeping of the reference's feature detection, restated so that one piece of
 // code serves the host entry points (roam_prune_blobs, roam_argsort_np122: radarslampy_amd/getFeatures.py) and the
-// device-side retrack of the engine (retrack.hip, one wavefront per lane; the sequential parts run on lane 0 with
+// device-side retrack of the engine (retrack_blobs.hip, one wavefront per lane; the sequential parts run on lane 0 with
 // their working set in LDS).
 //
 //   skimage.feature.blob._prune_blobs (called by blob_doh, reference getFeatures.py:47-51) visits the overlapping

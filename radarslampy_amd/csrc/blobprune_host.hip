@@ -1,6 +1,6 @@
 // Host entry points of the order-dependent blob bookkeeping (blobprune.h): pure CPU code inside libroam_hip.so, used by
 // radarslampy_amd/getFeatures.py for the stage-level blob_doh / adaptiveNMS mirrors.  The engine's device-side retrack
-// (retrack.hip) runs the same functions on the GPU.
+// (retrack_blobs.hip) runs the same functions on the GPU.
 #include "roam_internal.h"
 #include <math.h>
 #include <vector>

@@ -1,7 +1,7 @@
-// doh_common.h - device functions shared by the stage-level DoH kernels (doh.hip) and the engine's retrack (retrack.hip):
+// doh_common.h - device functions shared by the stage-level DoH kernels (doh.hip) and the engine's retrack (retrack_det.hip):
 // the box-filter Hessian determinant of skimage's _hessian_matrix_det, operation by operation (oracle/c/doh.c).
 // The integral image is read through an accessor (indices clipped at the image border like skimage's _integ).  hessian_box /
-// hessian_det_pruned below are the box layouts and the pruning rule that retrack.hip's strip-march kernel (rt_det_strip_kernel)
+// hessian_det_pruned below are the box layouts and the pruning rule that retrack_det.hip's strip-march kernel (rt_det_strip_kernel)
 // implements with its own LDS addressing: its comments refer to them.
 #pragma once
 #include "roam_internal.h"

@@ -1,5 +1,5 @@
 // npsort_wave.h - np.argsort of NumPy 1.22.3 (npy_aquicksort) by one wavefront, on any key type.  The reference pins numpy 1.22.3
-// and two of its results depend on that sort's order among equal keys: getFeatures.adaptiveNMS (the two-valued sigmas, retrack.hip)
+// and two of its results depend on that sort's order among equal keys: getFeatures.adaptiveNMS (the two-valued sigmas, retrack_blobs.hip)
 // and scipy.signal.find_peaks(distance=...) (the priority order of equal peak heights, peaks_cond.hip).  The sequential pieces are
 // blobprune.h's bp_aheapsort / bp_aquicksort_range.  Include after a definition of __syncthreads / __ballot (hip_runtime).
 #pragma once
@@ -15,7 +15,7 @@
 // tests/test_parallel_partition_model.py); the smaller ones are sorted one lane per segment, all at once, by the sequential code.
 // 530 two-valued sigmas on one lane were ~100 us of a lone detection's bookkeeping.  work: 3 x 256 ints, Lp / Rp: num uint16 each.
 #define QS_WAVE_MIN 64
-// KEY: the sort key (any type with operator<); the wave compares KV copies of it: int for integer codes (as retrack.hip has always
+// KEY: the sort key (any type with operator<); the wave compares KV copies of it: int for integer codes (as retrack_blobs.hip has always
 // done), the key itself otherwise
 template <typename KEY> struct NpWaveKey { typedef KEY type; };
 template <> struct NpWaveKey<uint8_t> { typedef int type; };

@@ -1,9 +1,9 @@
-// retrack.h - arguments of the device-side feature (re)detection (retrack.hip), filled by the engine
+// retrack.h - arguments and entry points of the device-side feature (re)detection (retrack*.hip; overview: retrack.hip), filled by the engine
 #pragma once
 #include "roam_internal.h"
 #include "blobprune.h"
 
-#define RT_TWO_PASS_SLOTS 200     // = RI_MIN_DETECTIONS of retrack.hip: chunks of at least that many detections take the one-sweep kernel
+#define RT_TWO_PASS_SLOTS 200     // chunks of at least that many detections take the one-sweep kernel (rt_one_sweep), smaller ones the two-pass pair
 enum { RT_F_CAND_OVERFLOW = 1, RT_F_TREE_OVERFLOW = 2, RT_F_PAIR_OVERFLOW = 4, RT_F_FEAT_OVERFLOW = 8 };
 
 struct RtArgs {

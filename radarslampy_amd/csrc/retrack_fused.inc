@@ -1,4 +1,4 @@
-// retrack_fused.inc - part of retrack.hip (included there, after the strip-march determinant kernel whose helpers it uses).
+// retrack_fused.inc - part of retrack_det.hip (included there, after the strip-march determinant kernel whose helpers it uses).
 //
 // K1 + K2 + K3 in ONE kernel: integral image, Hessian determinants and 3 x 3 x 3 maxima of a detection without the float64 integral
 // image ever leaving the CU (getFeatures.py:39-51, skimage blob_doh: integral_image -> _hessian_matrix_det -> peak_local_max).

@@ -1,4 +1,4 @@
-// ssc_body: the one-wavefront SSC of ssc.hip (see there), shared with the single-launch bookkeeping kernel of small batches (retrack.hip)
+// ssc_body: the one-wavefront SSC of ssc.hip (see there), shared with the single-launch bookkeeping kernel of small batches (retrack_blobs.hip)
 #pragma once
 #define SSC_BITMAP_BYTES 65536
 // the batched (engine) launch asks for a quarter of that: four square widths out of five of a 2024 x 2024 image need less than 1 KB of

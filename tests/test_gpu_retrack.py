@@ -1,4 +1,4 @@
-"""GPU (-m gpu): feature (re)detection INSIDE roam_engine_step (retrack.hip) - appendNewFeatures of the reference's loop
+"""GPU (-m gpu): feature (re)detection INSIDE roam_engine_step (retrack.hip and its units retrack_integral / _det / _blobs.hip) - appendNewFeatures of the reference's loop
 (RawROAMSystem.py:250-271, getFeatures.py:74-118) without a host round trip - against the oracle's loop body, on synthetic
 sequences and on the reference's 11 real data/tiny scans."""
 import numpy as np
@@ -90,7 +90,7 @@ def test_engine_device_retrack_matches_oracle():
 
 def test_large_chunk_takes_the_one_sweep_integral_kernel():
     """chunks of >= 200 detections use rt_integral_kernel (one sweep, image written once), smaller ones the two-pass kernels
-    (retrack.hip: rt_one_sweep): 224 lanes on three distinct sequences all run out of features in the same step; every lane
+    (retrack_geom.h: rt_one_sweep): 224 lanes on three distinct sequences all run out of features in the same step; every lane
     must end with the oracle's features for its sequence, bit for bit - and so must the same lanes through 2-detection chunks"""
     from radarslampy_amd import _ffi, synth
     from radarslampy_amd.engine import Engine

@@ -1,4 +1,4 @@
-"""CPU: the LOGIC of csrc/retrack.hip's wave-parallel k-d tree node build (rb_partition_hoare / rb_nth_element_wave / the scipy
+"""CPU: the LOGIC of csrc/retrack_blobs.hip's wave-parallel k-d tree node build (rb_partition_hoare / rb_nth_element_wave / the scipy
 partition pass of rb_build_node_wave), restated in Python next to the sequential algorithms it replaces - libstdc++'s
 std::nth_element (introselect: median of three to the front, unguarded Hoare partition, insertion sort below four elements) and
 scipy cKDTree's partition pass - on random arrays with heavy ties: the same array, element for element, and the same cut.  (The
@@ -169,7 +169,7 @@ def aquicksort_par(v):
 
 
 def test_aquicksort_segments_in_any_order_with_list_rule_partitions():
-    """csrc/retrack.hip rb_aquicksort_wave: NumPy 1.22's argsort (npy_aquicksort) with its segments processed in ANY order - each with
+    """csrc/retrack_blobs.hip rb_aquicksort_wave: NumPy 1.22's argsort (npy_aquicksort) with its segments processed in ANY order - each with
     the depth budget of its parent minus one - and every Hoare loop replaced by the two ordered lists of stop positions, against the
     oracle's restatement of the sequential algorithm (itself pinned against NumPy 1.22.3 outputs): two-valued keys (the detector's
     sigmas), all-equal keys, few and many distinct keys, 1 to 1 500 elements"""
