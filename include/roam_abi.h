@@ -122,6 +122,24 @@ int32_t roam_warp_polar_f32(roam_ctx *ctx, const float *src, int32_t n, int32_t 
                             int64_t src_image_stride, float *dst, int32_t dw, int32_t dh, float cx, float cy,
                             double max_radius, int32_t flags);
 
+/* cv2.warpAffine(src, M, (dw, dh), INTER_LINEAR [| WARP_INVERSE_MAP], BORDER_CONSTANT 0) on float32 images
+ * (FMT.rotateImg, FMT.py:93-100).  n images of one shape; M: m_count x 6 doubles (row-major 2 x 3),
+ * m_count == 1 (one matrix for all images) or m_count == n (one per image).  Image i starts src_image_stride floats after
+ * image i - 1, its rows src_row_stride floats apart; dst is n x dh x dw, contiguous.  Without ROAM_WARP_AFFINE_INVERSE_MAP M maps
+ * source to destination and is inverted on the host as OpenCV inverts it (a singular M becomes all zeros: every output pixel is
+ * src[0, 0]); with it M maps destination to source.  OpenCV's fixed-point coordinates: 1/1024 px per term, summed in int32, 1/32 px
+ * for the bilinear weights, tap indices saturated to int16 - exact while the source coordinates stay below 2^20 px (the caller's
+ * check; _ffi.warp_affine_args).  ROAM_E_ARG: a null pointer, n < 1, a side < 1 or > 16384, m_count not in {1, n}, unknown flags,
+ * src_row_stride < cols, src_image_stride smaller than one image's extent (n > 1). */
+#define ROAM_WARP_AFFINE_INVERSE_MAP 1
+int32_t roam_warp_affine_f32(roam_ctx *ctx, const float *src, int32_t n, int32_t rows, int32_t cols,
+                             int64_t src_row_stride, int64_t src_image_stride, const double *M, int32_t m_count,
+                             float *dst, int32_t dw, int32_t dh, int32_t flags);
+/* measurement aid: average milliseconds (HIP events, two warm runs first) of the warp_affine_kernel launch that warps n resident
+ * rows x cols images (zeros) by the forward matrix M (6 doubles) into n images of the same size; no host transfer is timed */
+int32_t roam_time_warp_affine(roam_ctx *ctx, int32_t n, int32_t rows, int32_t cols, const double *M, int32_t reps,
+                              float *ms_per_rep);
+
 /* ---- a7: cv2.calcOpticalFlowPyrLK as used by getTransformKLT.getTrackedPointsKLT
  * (getTransformKLT.py:317-381; LK_PARAMS :77-81: winSize 15, maxLevel 3, 10 iter, eps 0.03).
  * Images are w x h; *_f32 variants quantise (img*255 -> u8, :356-357) on the device.

@@ -1,5 +1,10 @@
-"""Fourier-Mellin registration with the reference's names (reference FMT.py:10-90): the rotation prior (csrc/fmt.hip) and the
-translation by phase correlation (csrc/fft.hip); the computation runs on the MI355X.  SURVEY §8f-f4."""
+"""Fourier-Mellin registration with the reference's names (reference FMT.py:10-100): the rotation prior (csrc/fmt.hip), the
+translation by phase correlation (csrc/fft.hip) and the rotation of an image (csrc/warpaffine.hip); the computation runs on the
+MI355X.  SURVEY §8f-f4."""
+import math
+
+import numpy as np
+
 from . import _ffi
 from .parseData import RANGE_RESOLUTION_CART_M
 
@@ -20,3 +25,34 @@ def getRotationUsingFMT(srcPolarImg, targetPolarImg, downsampleFactor: int = FMT
     assert srcPolarImg.shape == targetPolarImg.shape, "Images need to have the same shape!"
     clip = int(maxRangeClipM / RANGE_RESOLUTION_CART_M) if maxRangeClipM > 0 else 0
     return _ffi.default_context().fmt_rotation(srcPolarImg, targetPolarImg, clip_px=clip, downsample=int(downsampleFactor))
+
+
+def getRotationMatrix2D(center, angle, scale):
+    """cv2.getRotationMatrix2D -> (2, 3) float64: the centre rounded to float32 (cv::Point2f), the rest in float64; angle in degrees,
+    positive = counter-clockwise with the image's y axis pointing down.  Host code only."""
+    cx, cy = float(np.float32(center[0])), float(np.float32(center[1]))
+    rad = float(angle) * math.pi / 180.0
+    a, b = math.cos(rad) * float(scale), math.sin(rad) * float(scale)
+    return np.array([[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]], np.float64)
+
+
+def rotateImg(image, angle_degrees):
+    """FMT.py:93-100: cv2.warpAffine(image, getRotationMatrix2D((w / 2, h / 2), angle_degrees, 1.0), (w, h), INTER_LINEAR)
+    (roam_warp_affine_f32, warpaffine.hip).  Unlike cv2, which remaps u8 and f64 natively, any input is converted to float32 first
+    and the output is float32.  image may be a 3-D batch of one shape; angle_degrees is then one angle for all images or a 1-D array
+    with one angle per image, and the whole batch is one launch.  Argument errors (Context.warp_affine_f32's, a non-finite angle,
+    an angle array that does not match the batch) are ValueError before any device call."""
+    img = np.asarray(image)
+    if img.ndim not in (2, 3):
+        raise ValueError(f"rotateImg: a 2-D image or a 3-D batch, not {img.ndim}-D")
+    h, w = img.shape[-2:]
+    ang = np.asarray(angle_degrees, np.float64)
+    if ang.ndim > 1 or (ang.ndim == 1 and (img.ndim != 3 or len(ang) != img.shape[0])):
+        raise ValueError(f"rotateImg: one angle, or one per image of a 3-D batch, not angles of shape {ang.shape} for an image of "
+                         f"shape {img.shape}")
+    if not np.isfinite(ang).all():
+        raise ValueError("rotateImg: the angle is not finite")
+    center = (w / 2, h / 2)
+    M = getRotationMatrix2D(center, ang, 1.0) if ang.ndim == 0 else np.stack([getRotationMatrix2D(center, t, 1.0) for t in ang])
+    _ffi.warp_affine_args(img, M, (w, h))
+    return _ffi.default_context().warp_affine_f32(img, M, (w, h))

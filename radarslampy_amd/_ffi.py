@@ -11,6 +11,9 @@ LIB_PATH = os.environ.get("ROAM_LIB") or os.path.join(_HERE, "csrc", "libroam_hi
 
 ROAM_OK, ROAM_E_ARG, ROAM_E_HIP, ROAM_E_CAPACITY, ROAM_E_NODEVICE, ROAM_E_STATE = 0, -1, -2, -3, -4, -5
 WARP_POLAR_LOG, WARP_POLAR_INVERSE = 1, 2      # roam_abi.h ROAM_WARP_POLAR_*
+WARP_AFFINE_INVERSE_MAP = 1     # roam_abi.h ROAM_WARP_AFFINE_INVERSE_MAP
+WARP_AFFINE_MAX_SIDE = 16384    # largest image side of roam_warp_affine_f32
+WARP_AFFINE_MAX_COORD = 2.0 ** 20   # source coordinates (px) the fixed-point sums of roam_warp_affine_f32 hold without overflow
 TIME_FFT_FIVE, TIME_DFT_FIVE, TIME_FFT_ROWS, TIME_FFT_TRANSPOSE, TIME_FFT_COLS = range(5)      # roam_abi.h ROAM_TIME_*
 PHASE_CORRELATE_MAX = 4096      # largest image side of roam_phase_correlate_f32
 MAX_FEATURES = 1024
@@ -71,6 +74,9 @@ _SIGS = {
     "roam_polar_to_cart_record_u8": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_warp_polar_f32": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_int32,
                                         C.c_float, C.c_float, C.c_double, C.c_int32]),
+    "roam_warp_affine_f32": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int32, _vp, C.c_int32,
+                                         C.c_int32, C.c_int32]),
+    "roam_time_warp_affine": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _P(C.c_float)]),
     "roam_klt_track_u8": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "roam_klt_track_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "roam_pyr_down_u8": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
@@ -168,6 +174,49 @@ def phase_correlate_args(src, tgt):
     if not (2 <= rows <= PHASE_CORRELATE_MAX and 2 <= cols <= PHASE_CORRELATE_MAX):
         raise ValueError(f"phase_correlate: image sides in [2, {PHASE_CORRELATE_MAX}], not {rows} x {cols}")
     return a, b
+
+
+def invert_affine(M):
+    """cv2.warpAffine's in-place inversion of a 2 x 3 matrix, operation by operation in float64 (a singular matrix -> all zeros)
+    -> the six coefficients of the destination -> source map"""
+    M0, M1, M2, M3, M4, M5 = (float(v) for v in np.asarray(M, np.float64).ravel())
+    D = M0 * M4 - M1 * M3
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = M4 * D, M0 * D
+    M0, M1, M3, M4 = A11, M1 * -D, M3 * -D, A22
+    b1 = -M0 * M2 - M1 * M5
+    b2 = -M3 * M2 - M4 * M5
+    return np.array([M0, M1, b1, M3, M4, b2], np.float64)
+
+
+def warp_affine_args(src, M, dsize_wh, inverse_map=False):
+    """The argument checks of Context.warp_affine_f32, made before any device call -> (src as an array, M as (m_count, 6) float64,
+    dw, dh).  ValueError: src neither a 2-D image nor a 3-D batch; M not (2, 3) or (n, 2, 3) (a stack of matrices needs a batch of as
+    many images); a non-finite M; an empty source or output; a side above 16384; a map that sends any of the four corners of
+    the destination to a source coordinate of magnitude >= 2^20 px (or to no finite one), evaluated in float64 with the inverted
+    matrix."""
+    a = np.asarray(src)
+    if a.ndim not in (2, 3):
+        raise ValueError(f"warp_affine_f32: a 2-D image or a 3-D batch, not {a.ndim}-D")
+    m = np.asarray(M, np.float64)
+    if m.shape != (2, 3) and not (a.ndim == 3 and m.shape == (a.shape[0], 2, 3)):
+        raise ValueError(f"warp_affine_f32: M of shape (2, 3){' or (%d, 2, 3)' % a.shape[0] if a.ndim == 3 else ''}, not {m.shape}")
+    if not np.isfinite(m).all():
+        raise ValueError("warp_affine_f32: M is not finite")
+    dw, dh = int(dsize_wh[0]), int(dsize_wh[1])
+    if min(dw, dh) <= 0 or min(a.shape) <= 0:
+        raise ValueError(f"warp_affine_f32: empty image ({a.shape} -> {dh} x {dw})")
+    if max(dw, dh, a.shape[-2], a.shape[-1]) > WARP_AFFINE_MAX_SIDE:
+        raise ValueError(f"warp_affine_f32: image side above {WARP_AFFINE_MAX_SIDE} ({a.shape[-2]} x {a.shape[-1]} -> {dh} x {dw})")
+    m = np.ascontiguousarray(m.reshape(-1, 6))
+    for k in range(len(m)):
+        inv = m[k] if inverse_map else invert_affine(m[k])
+        inv = [float(v) for v in inv]
+        worst = max(abs(inv[r] * x + inv[r + 1] * y + inv[r + 2]) for r in (0, 3) for x in (0, dw - 1) for y in (0, dh - 1))
+        if not worst < WARP_AFFINE_MAX_COORD:
+            raise ValueError(f"warp_affine_f32: matrix {k} maps a corner of the output to source coordinate {worst:g} px; the "
+                             f"fixed-point coordinates hold magnitudes below 2^20 px")
+    return a, m, dw, dh
 
 
 def _f32_rows_in_place(a):
@@ -321,6 +370,35 @@ class Context:
         self.check(self.lib.roam_warp_polar_f32(self.h, _ptr(a3), n, rows, cols, row_stride, image_stride, _ptr(out), dw, dh,
                                                 float(center[0]), float(center[1]), float(max_radius), flags))
         return out if batch else out[0]
+
+    def warp_affine_f32(self, src, M, dsize_wh, inverse_map=False):
+        """cv2.warpAffine(src, M, dsize_wh, INTER_LINEAR [| WARP_INVERSE_MAP], BORDER_CONSTANT 0) on float32 (roam_warp_affine_f32,
+        warpaffine.hip).  src: (rows, cols) or a batch (n, rows, cols) of one shape; M: (2, 3), or (n, 2, 3) - one matrix per image
+        of the batch, all in one launch; dsize_wh = (dw, dh).  A 2-D float32 view with unit column stride is read in place with its
+        row stride; any other input is made float32-contiguous first.  -> (dh, dw) or (n, dh, dw) float32.
+        OpenCV adds the fixed-point terms of a source coordinate (1/1024 px each) in int32, so the map must keep every source
+        coordinate below 2^20 px in magnitude: checked at the four corners of the output, with the other argument errors, by
+        warp_affine_args (ValueError before any device call)."""
+        a, m, dw, dh = warp_affine_args(src, M, dsize_wh, inverse_map)
+        if not (a.ndim == 2 and a.dtype == np.float32 and a.strides[1] == 4 and a.strides[0] % 4 == 0 and a.strides[0] >= 4 * a.shape[1]):
+            a = np.ascontiguousarray(a, np.float32)
+        batch = a.ndim == 3
+        a3 = a if batch else a[None]
+        n, rows, cols = a3.shape
+        row_stride = a3.strides[1] // 4 if rows > 1 else cols
+        image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+        out = np.empty((n, dh, dw), np.float32)
+        self.check(self.lib.roam_warp_affine_f32(self.h, _ptr(a3), n, rows, cols, row_stride, image_stride, _ptr(m), len(m), _ptr(out),
+                                                 dw, dh, WARP_AFFINE_INVERSE_MAP if inverse_map else 0))
+        return out if batch else out[0]
+
+    def time_warp_affine(self, n, rows, cols, M, reps=20):
+        """milliseconds per launch of warp_affine_kernel on n resident rows x cols images warped by M into the same size, by HIP
+        events after two warm runs (roam_time_warp_affine)"""
+        m = np.ascontiguousarray(M, np.float64).reshape(6)
+        ms = C.c_float(0)
+        self.check(self.lib.roam_time_warp_affine(self.h, int(n), int(rows), int(cols), _ptr(m), int(reps), C.byref(ms)))
+        return float(ms.value)
 
     def pyr_down_u8(self, img):
         img = np.ascontiguousarray(img, np.uint8)
