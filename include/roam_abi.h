@@ -242,6 +242,21 @@ int32_t roam_fmt_rotation(roam_ctx *ctx, const float *src_polar, const float *tg
 int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t batch, int32_t rows, int32_t cols,
                                  int64_t row_stride, int64_t image_stride, int32_t hanning, double *out_dxdy, double *out_response);
 
+/* FMT.getRotationUsingFMT for n pairs in one device pass: the same estimate as roam_fmt_rotation, with the front end batched over the
+ * 2 n images (csrc/fmt_batch.hip) and the correlation through the mixed-radix FFT of roam_phase_correlate_f32, so the plane may be as
+ * large as 4096 x 1350 (downsample 1 or 2).  src / tgt: n float32 polar images each, rows x cols, row_stride / image_stride in
+ * elements.  R = clip / downsample columns after the resize, clip = clip_px (<= 0 or >= cols: cols).  out3 (n, 3) f64
+ * {angle_rad, scale, response}.  logpolar_out: NULL, or (2 n, round(pi R), R) f32: the log-polar images before the window, all sources
+ * first, then all targets (for tests).  A large batch is processed in chunks that keep the device scratch under 2 GB, with one stream
+ * synchronisation per chunk; the result of a pair does not depend on the batch it is in.  ROAM_E_ARG: a null src / tgt / out3, n < 1,
+ * rows outside [8, 16384], cols < 2, downsample < 1, R outside [ROAM_FMT_MIN_R, ROAM_FMT_MAX_R] (round(pi R) must fit the FFT's 4096),
+ * row_stride < cols, image_stride smaller than one image's extent (n > 1). */
+#define ROAM_FMT_MIN_R 4
+#define ROAM_FMT_MAX_R 1303
+int32_t roam_fmt_rotation_batch_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t n, int32_t rows, int32_t cols,
+                                    int64_t row_stride, int64_t image_stride, int32_t clip_px, int32_t downsample, double *out3,
+                                    float *logpolar_out);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous
@@ -342,6 +357,14 @@ int32_t roam_engine_lane_peaks(roam_ctx *ctx, int32_t lane, int32_t *out, int64_
  * (appendNewFeatures(currImgCart, ...) of RawROAMSystem.py:264 without moving image data) */
 int32_t roam_engine_doh_maxima(roam_ctx *ctx, int32_t pool_idx, const double *sigmas, int32_t num_sigma, double threshold,
                                int32_t *out_rcs, double *out_val, int32_t cap, int32_t *n_out);
+/* the Fourier-Mellin rotation prior of Tracker.track (Tracker.py:62-63) on resident scans: roam_fmt_rotation_batch_f32's pass for the
+ * n pairs of pool records (prev_pool_idx[i], curr_pool_idx[i]), read in place as float(u8) / 255.0f (no float32 polar image is
+ * made).  Blocking: waits for the steps enqueued so far and for the uploads of the pool, and leaves the engine's state alone.
+ * The range clip is min(clip_px, cfg.clip), clip_px <= 0: cfg.clip.  out3 (n, 3) f64 {angle_rad, scale, response}.
+ * ROAM_E_ARG: null pointers, n < 1, a pool index out of range, cfg.rows < 8, downsample < 1, R = clip / downsample outside
+ * [ROAM_FMT_MIN_R, ROAM_FMT_MAX_R]. */
+int32_t roam_engine_fmt_rotation(roam_ctx *ctx, int32_t n, const int32_t *prev_pool_idx, const int32_t *curr_pool_idx, int32_t clip_px,
+                                 int32_t downsample, double *out3);
 /* blocking: level `level` (0..3) of the lane's most recent Cartesian u8 pyramid (w*h bytes, row-major) */
 int32_t roam_engine_lane_image(roam_ctx *ctx, int32_t lane, int32_t level, uint8_t *out, int64_t cap);
 /* replace a lane's feature set (retrack append, getFeatures.appendNewFeatures getFeatures.py:98-118) */

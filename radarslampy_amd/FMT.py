@@ -1,6 +1,6 @@
-"""Fourier-Mellin registration with the reference's names (reference FMT.py:10-100): the rotation prior (csrc/fmt.hip), the
-translation by phase correlation (csrc/fft.hip) and the rotation of an image (csrc/warpaffine.hip); the computation runs on the
-MI355X.  SURVEY §8f-f4."""
+"""Fourier-Mellin registration with the reference's names (reference FMT.py:10-100): the rotation prior (csrc/fmt.hip; batches of
+pairs: csrc/fmt_batch.hip), the translation by phase correlation (csrc/fft.hip) and the rotation of an image (csrc/warpaffine.hip);
+the computation runs on the MI355X.  SURVEY §8f-f4."""
 import math
 
 import numpy as np
@@ -21,9 +21,15 @@ def getTranslationUsingPhaseCorrelation(srcImg, targetImg):
 
 
 def getRotationUsingFMT(srcPolarImg, targetPolarImg, downsampleFactor: int = FMT_DOWNSAMPLE_FACTOR, maxRangeClipM=FMT_RANGE_CLIP_M):
-    """-> (angleRad with R(angleRad) @ src = target, scaling factor, response); polar (not log-polar) float32 images"""
+    """-> (angleRad with R(angleRad) @ src = target, scaling factor, response); polar (not log-polar) float32 images.
+    Two 3-D batches of polar images of one shape go through the batched device pass (roam_fmt_rotation_batch_f32) and give three
+    arrays with one entry per pair; argument errors are then ValueError before any device call."""
     assert srcPolarImg.shape == targetPolarImg.shape, "Images need to have the same shape!"
     clip = int(maxRangeClipM / RANGE_RESOLUTION_CART_M) if maxRangeClipM > 0 else 0
+    if np.ndim(srcPolarImg) == 3:
+        _ffi.fmt_rotation_batch_args(srcPolarImg, targetPolarImg, clip, int(downsampleFactor))
+        out = _ffi.default_context().fmt_rotation_batch(srcPolarImg, targetPolarImg, clip_px=clip, downsample=int(downsampleFactor))
+        return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
     return _ffi.default_context().fmt_rotation(srcPolarImg, targetPolarImg, clip_px=clip, downsample=int(downsampleFactor))
 
 

@@ -16,6 +16,8 @@ WARP_AFFINE_MAX_SIDE = 16384    # largest image side of roam_warp_affine_f32
 WARP_AFFINE_MAX_COORD = 2.0 ** 20   # source coordinates (px) the fixed-point sums of roam_warp_affine_f32 hold without overflow
 TIME_FFT_FIVE, TIME_DFT_FIVE, TIME_FFT_ROWS, TIME_FFT_TRANSPOSE, TIME_FFT_COLS = range(5)      # roam_abi.h ROAM_TIME_*
 PHASE_CORRELATE_MAX = 4096      # largest image side of roam_phase_correlate_f32
+FMT_MIN_R, FMT_MAX_R = 4, 1303  # roam_abi.h ROAM_FMT_MIN_R / ROAM_FMT_MAX_R: columns after the resize of the batched rotation prior
+FMT_MAX_ROWS = 16384            # ... and its largest number of polar rows
 MAX_FEATURES = 1024
 STEP_NEW_SEQUENCE = 0x40000000      # roam_abi.h ROAM_STEP_NEW_SEQUENCE: OR into a lane's scan index
 
@@ -107,6 +109,7 @@ _SIGS = {
     "roam_engine_lane_features": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, _P(C.c_int32)]),
     "roam_engine_lane_peaks": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _P(C.c_int64)]),
     "roam_engine_doh_maxima": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, C.c_double, _vp, _vp, C.c_int32, _P(C.c_int32)]),
+    "roam_engine_fmt_rotation": (C.c_int32, [_vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     "roam_engine_lane_image": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, C.c_int64]),
     "roam_engine_set_features": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32]),
     "roam_engine_kernel_avg": (C.c_int32, [_vp, C.c_char_p, C.c_int32, _P(C.c_float), _P(C.c_int32)]),
@@ -121,6 +124,8 @@ _SIGS = {
     "roam_engine_debug_detect": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp]),
     "roam_fmt_rotation": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
     "roam_phase_correlate_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp]),
+    "roam_fmt_rotation_batch_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                _vp, _vp]),
     "roam_debug_fft2_f64": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_time_fft2": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
     "roam_prune_blobs": (C.c_int32, [_vp, C.c_int32, C.c_double, _vp]),
@@ -174,6 +179,39 @@ def phase_correlate_args(src, tgt):
     if not (2 <= rows <= PHASE_CORRELATE_MAX and 2 <= cols <= PHASE_CORRELATE_MAX):
         raise ValueError(f"phase_correlate: image sides in [2, {PHASE_CORRELATE_MAX}], not {rows} x {cols}")
     return a, b
+
+
+def fmt_clip_radius(cols, clip_px, downsample, rows):
+    """The range clip and the width after the resize of the batched rotation prior -> (clip, R), checked as the library checks them:
+    ValueError for rows outside [8, 16384], downsample < 1, or R = clip // downsample outside [4, 1303] (round(pi R) must fit the
+    FFT's 4096)."""
+    clip_px, downsample = int(clip_px), int(downsample)
+    if not 8 <= rows <= FMT_MAX_ROWS:
+        raise ValueError(f"fmt_rotation_batch: polar images of 8 to {FMT_MAX_ROWS} rows, not {rows}")
+    if downsample < 1:
+        raise ValueError(f"fmt_rotation_batch: downsample >= 1, not {downsample}")
+    clip = clip_px if 0 < clip_px < cols else cols
+    R = clip // downsample
+    if not FMT_MIN_R <= R <= FMT_MAX_R:
+        raise ValueError(f"fmt_rotation_batch: clip // downsample in [{FMT_MIN_R}, {FMT_MAX_R}], not {clip} // {downsample} = {R}")
+    return clip, R
+
+
+def fmt_rotation_batch_args(src, tgt, clip_px, downsample):
+    """The argument checks of Context.fmt_rotation_batch, made before any device call -> (src, tgt as arrays, clip, R).  Different
+    shapes: AssertionError (the reference's assert); neither 2-D images nor 3-D batches, an empty batch, or fmt_clip_radius's
+    conditions: ValueError."""
+    a, b = np.asarray(src), np.asarray(tgt)
+    assert a.shape == b.shape, "Images need to have the same shape!"
+    if a.ndim not in (2, 3):
+        raise ValueError(f"fmt_rotation_batch: two 2-D polar images or two 3-D batches, not {a.ndim}-D")
+    if a.ndim == 3 and a.shape[0] < 1:
+        raise ValueError("fmt_rotation_batch: an empty batch")
+    rows, cols = a.shape[-2:]
+    if cols < 2:
+        raise ValueError(f"fmt_rotation_batch: at least 2 columns, not {cols}")
+    clip, R = fmt_clip_radius(cols, clip_px, downsample, rows)
+    return a, b, clip, R
 
 
 def invert_affine(M):
@@ -493,6 +531,26 @@ class Context:
         self.check(self.lib.roam_fmt_rotation(self.h, _ptr(a), _ptr(b), a.shape[0], a.shape[1], int(clip_px), int(downsample),
                                               C.byref(ang), C.byref(sc), C.byref(rs)))
         return ang.value, sc.value, rs.value
+
+    def fmt_rotation_batch(self, src, tgt, clip_px=1012, downsample=10, want_logpolar=False):
+        """FMT.getRotationUsingFMT for a batch of pairs in one device pass (roam_fmt_rotation_batch_f32): two 2-D polar images or two
+        3-D batches of one shape -> (n, 3) float64 rows (angle rad, scale, response); want_logpolar: also the log-polar images before
+        the window, (2 n, round(pi R), R) float32, all sources first, then all targets.  float32 views with unit column stride are
+        read in place, anything else is made float32-contiguous.  Arguments are checked by fmt_rotation_batch_args before any device
+        call."""
+        a, b, clip, R = fmt_rotation_batch_args(src, tgt, clip_px, downsample)
+        a, b = _f32_rows_in_place(a), _f32_rows_in_place(b)
+        a3, b3 = (a, b) if a.ndim == 3 else (a[None], b[None])
+        n, rows, cols = a3.shape
+        if a3.strides[0 if n > 1 else 1:] != b3.strides[0 if n > 1 else 1:]:     # one pair of strides describes both operands
+            a3, b3 = np.ascontiguousarray(a3), np.ascontiguousarray(b3)
+        row_stride = a3.strides[1] // 4
+        image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+        out = np.empty((n, 3), np.float64)
+        lp = np.empty((2 * n, int(np.rint(R * np.pi)), R), np.float32) if want_logpolar else None
+        self.check(self.lib.roam_fmt_rotation_batch_f32(self.h, _ptr(a3), _ptr(b3), n, rows, cols, row_stride, image_stride, int(clip_px),
+                                                        int(downsample), _ptr(out), _ptr(lp)))
+        return (out, lp) if want_logpolar else out
 
     def phase_correlate(self, src, tgt, hanning=True):
         """FMT.getTranslationUsingPhaseCorrelation: cv2.phaseCorrelate(src, tgt[, cv2.createHanningWindow((cols, rows), CV_32F)])

@@ -12,8 +12,11 @@
 //             first use.  A butterfly's twiddle index r k n / (Ns R) is an exact integer below n: no angle is reduced on the device.
 //   inverse:  unscaled (cv2.idft without DFT_SCALE) as swap(FFT(swap(x))), swap = exchange of real and imaginary part: the launcher
 //             exchanges the plane pointers, the kernel is the forward one.
+// The batched rotation prior (roam_fmt_rotation_batch_f32, roam_engine_fmt_rotation) runs the same correlation on planes that the
+// kernels of fmt_batch.hip fill: its driver roam_fmt_batch_run is here because the row pass and the transpose are local to this unit.
 #include "roam_internal.h"
 #include <math.h>
+#include <stdlib.h>
 
 #define FFT_MAX_N 4096
 #define FFT_THREADS 512
@@ -407,6 +410,146 @@ extern "C" int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, con
         }
     }
     return ROAM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batched rotation prior
+// FMT.getRotationUsingFMT for n pairs: the front end of fmt_batch.hip fills the planes, the correlation is the one above.  Per chunk of
+// nb pairs, 7 nb planes: sources' windowed images | work re, im | F1 re, im | F2 re, im - the targets' windowed images wait in the
+// F2 re planes, which nothing touches before their own row pass has consumed them.  One stream synchronisation per chunk.
+int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows, int clip, int R, double *out3, float *logpolar_out)
+{
+    const int W = 2 * R, dw = (int)rint((double)R), dh = (int)rint((double)R * M_PI);
+    const int M = optimal_dft_size(dh), N = optimal_dft_size(dw);
+    ARG_CHECK(ctx, M <= FFT_MAX_N && N <= FFT_MAX_N);
+    const bool host = in.host_src != nullptr;
+    const size_t nmn = (size_t)M * N, nsmall = (size_t)rows * R, ncart = (size_t)W * W, nlp = (size_t)dh * dw;
+    // a host image travels as whole rows when they are contiguous (one copy per image, or one per chunk), else as its first clip columns
+    const bool whole_rows = host && in.row_stride == in.cols;
+    const size_t in_w = whole_rows ? (size_t)in.cols : (size_t)clip, nin = host ? (size_t)rows * in_w : 0;
+    const size_t per_pair = 7 * sizeof(double) * nmn + 2 * sizeof(float) * (nsmall + ncart + (logpolar_out ? nlp : 0) + nin) + 2 * sizeof(int32_t);
+    size_t chunk = ((size_t)2000 << 20) / per_pair;
+    if (chunk < 1) chunk = 1;
+    if (chunk > (size_t)n) chunk = n;
+    if (chunk > 32767) chunk = 32767;                        // 2 chunk images in grid.z
+    if (const char *ce = getenv("ROAM_FMT_BATCH_CHUNK")) {   // tests: a small chunk (read per call)
+        const long c = atol(ce);
+        if (c >= 1 && (size_t)c < chunk) chunk = (size_t)c;
+    }
+    const int per = (int)((nmn + 1023) / 1024) < 1024 ? 1024 : (int)((nmn + 1023) / 1024);
+    const int nblk = (int)((nmn + per - 1) / per);
+    hipStream_t st = ctx->stream;
+    float *d_in = host ? (float *)roam_scratch(ctx, S_IN0, sizeof(float) * nin * 2 * chunk) : nullptr;
+    int32_t *d_idx = host ? nullptr : (int32_t *)roam_scratch(ctx, S_IN1, sizeof(int32_t) * 2 * chunk);
+    float *d_small = (float *)roam_scratch(ctx, S_TMP4, sizeof(float) * nsmall * 2 * chunk);
+    float *d_cart = (float *)roam_scratch(ctx, S_TMP5, sizeof(float) * ncart * 2 * chunk);
+    float *d_lp = logpolar_out ? (float *)roam_scratch(ctx, S_TMP6, sizeof(float) * nlp * 2 * chunk) : nullptr;
+    double *d_f = (double *)roam_scratch(ctx, S_TMP2, sizeof(double) * nmn * 7 * chunk);
+    const size_t tab_bytes = sizeof(double) * (3 * (size_t)dh + dw) + sizeof(float) * dw;
+    unsigned char *d_tab = (unsigned char *)roam_scratch(ctx, S_TMP1, tab_bytes);
+    double *d_pv = (double *)roam_scratch(ctx, S_TMP0, sizeof(double) * (size_t)nblk * chunk);
+    int *d_pi = (int *)roam_scratch(ctx, S_TMP3, sizeof(int) * (size_t)nblk * chunk);
+    double *d_out = (double *)roam_scratch(ctx, S_OUT0, sizeof(double) * 3 * chunk);
+    if ((host && !d_in) || (!host && !d_idx) || !d_small || !d_cart || (logpolar_out && !d_lp) || !d_f || !d_tab || !d_pv || !d_pi || !d_out)
+        return ROAM_E_HIP;
+    // OpenCV's host tables of the forward warpPolar (Kmag and Kangle from the destination size) and createHanningWindow's factors
+    std::vector<unsigned char> tab(tab_bytes);
+    {
+        double *cs = (double *)tab.data(), *wr = cs + 2 * dh, *wc = wr + dh;
+        float *br = (float *)(wc + dw);
+        const double Kangle = 6.283185307179586476925286766559 / dh, Kmag = log((double)W / 2.0) / dw;
+        for (int phi = 0; phi < dh; phi++) {
+            const double KKy = Kangle * phi;
+            cs[2 * phi] = cos(KKy); cs[2 * phi + 1] = sin(KKy);
+            wr[phi] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(dh - 1) * (double)phi));
+        }
+        for (int rho = 0; rho < dw; rho++) {
+            br[rho] = (float)(exp(rho * Kmag) - 1.0);
+            wc[rho] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(dw - 1) * (double)rho));
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
+    const double *d_tabd = (const double *)d_tab;
+    const float *d_br = (const float *)(d_tabd + 3 * (size_t)dh + dw);
+    std::vector<double> o(3 * chunk);
+    const int sz = dh > dw ? dh : dw;
+    const double log_base = exp(log((double)dh / 2.0) / (double)sz);
+    for (size_t b0 = 0; b0 < (size_t)n; b0 += chunk) {
+        const int nb = (int)(((size_t)n - b0) < chunk ? ((size_t)n - b0) : chunk);
+        const size_t pl = nmn * nb;
+        double *a = d_f, *tr = d_f + pl, *ti = d_f + 2 * pl, *F[2][2] = {{d_f + 3 * pl, d_f + 4 * pl}, {d_f + 5 * pl, d_f + 6 * pl}};
+        double *win[2] = {a, F[1][0]};                       // the windowed images: sources, targets
+        FmtBatchSrc src;
+        if (host) {
+            const float *h[2] = {in.host_src, in.host_tgt};
+            for (int k = 0; k < 2; k++) {
+                float *d = d_in + (size_t)k * nb * nin;
+                const float *h0 = h[k] + (int64_t)b0 * in.image_stride;
+                if (whole_rows && (nb == 1 || in.image_stride == (int64_t)nin))
+                    HIP_TRY(ctx, hipMemcpyAsync(d, h0, sizeof(float) * nin * nb, hipMemcpyHostToDevice, st));
+                else
+                    for (int i = 0; i < nb; i++) {
+                        if (whole_rows)
+                            HIP_TRY(ctx, hipMemcpyAsync(d + (size_t)i * nin, h0 + (int64_t)i * in.image_stride, sizeof(float) * nin,
+                                                        hipMemcpyHostToDevice, st));
+                        else
+                            HIP_TRY(ctx, hipMemcpy2DAsync(d + (size_t)i * nin, sizeof(float) * in_w, h0 + (int64_t)i * in.image_stride,
+                                                          sizeof(float) * in.row_stride, sizeof(float) * in_w, rows, hipMemcpyHostToDevice, st));
+                    }
+            }
+            src = {d_in, (int64_t)nin, (int64_t)in_w, 0, 0, nullptr};
+        } else {
+            HIP_TRY(ctx, hipMemcpyAsync(d_idx, in.prev_idx + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_idx + nb, in.curr_idx + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
+            src = {in.pool, in.rec_bytes, in.rec_stride, in.payload_off, 1, d_idx};
+        }
+        HIP_TRY(ctx, launch_fmt_batch_front(st, src, nb, rows, clip, R, dw, dh, M, N, d_tabd, d_br, d_small, d_cart, d_f, (int64_t)4 * nb, d_lp));
+        for (int k = 0; k < 2; k++) {
+            FFT_TRY(fft_rows(ctx, win[k], nullptr, tr, ti, (int64_t)nb * M, N, false));
+            FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, F[k][0], F[k][1]));
+            FFT_TRY(fft_rows(ctx, F[k][0], F[k][1], F[k][0], F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
+        }
+        HIP_TRY(ctx, launch_fmt_cross_power(st, F[0][0], F[0][1], F[1][0], F[1][1], (int)pl, tr, ti));
+        FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
+        FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, F[0][0], F[0][1]));
+        FFT_TRY(fft_rows(ctx, F[0][0], F[0][1], a, nullptr, (int64_t)nb * M, N, true));                  // real part only
+        hipLaunchKernelGGL(pc_peak_partial_kernel, dim3(nblk, nb), dim3(256), 0, st, a, M, N, per, d_pv, d_pi);
+        hipLaunchKernelGGL(pc_peak_final_kernel, dim3(nb), dim3(256), 0, st, a, M, N, nblk, d_pv, d_pi, d_out);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
+        if (logpolar_out) {
+            HIP_TRY(ctx, hipMemcpyAsync(logpolar_out + b0 * nlp, d_lp, sizeof(float) * nlp * nb, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(logpolar_out + ((size_t)n + b0) * nlp, d_lp + (size_t)nb * nlp, sizeof(float) * nlp * nb,
+                                        hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (int i = 0; i < nb; i++) {                       // the final arithmetic of roam_fmt_rotation
+            double ang = -o[3 * i + 1] * 2.0 * M_PI / (double)sz;
+            ang = fmod(ang + M_PI, 2.0 * M_PI);              // utils.normalize_angles: (th + pi) % (2 pi) - pi (Python modulo)
+            if (ang < 0) ang += 2.0 * M_PI;
+            out3[3 * (b0 + i)] = ang - M_PI;
+            out3[3 * (b0 + i) + 1] = pow(log_base, o[3 * i]);
+            out3[3 * (b0 + i) + 2] = o[3 * i + 2];
+        }
+    }
+    return ROAM_OK;
+}
+
+extern "C" int32_t roam_fmt_rotation_batch_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t n, int32_t rows, int32_t cols,
+                                               int64_t row_stride, int64_t image_stride, int32_t clip_px, int32_t downsample, double *out3,
+                                               float *logpolar_out)
+{
+    if (!ctx) return ROAM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ARG_CHECK(ctx, src && tgt && out3 && n >= 1);
+    ARG_CHECK(ctx, rows >= 8 && rows <= 16384 && cols >= 2 && downsample >= 1);
+    ARG_CHECK(ctx, row_stride >= cols && (n == 1 || image_stride >= (int64_t)(rows - 1) * row_stride + cols));
+    const int clip = (clip_px > 0 && clip_px < cols) ? clip_px : cols;
+    const int R = clip / downsample;
+    ARG_CHECK(ctx, R >= ROAM_FMT_MIN_R && R <= ROAM_FMT_MAX_R);
+    FmtBatchIn in;
+    in.host_src = src; in.host_tgt = tgt; in.row_stride = row_stride; in.image_stride = n == 1 ? (int64_t)rows * row_stride : image_stride;
+    in.cols = cols;
+    return roam_fmt_batch_run(ctx, in, n, rows, clip, R, out3, logpolar_out);
 }
 
 // ------------------------------------------------------------------------------------------------ test / measurement entries

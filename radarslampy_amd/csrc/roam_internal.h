@@ -194,3 +194,33 @@ hipError_t launch_fmt_dft2(hipStream_t st, const double *re_in, const double *im
 int optimal_dft_size(int n);
 // fft.hip: free the context's twiddle tables
 void roam_fft_release(roam_ctx *ctx);
+
+// fmt_batch.hip: the batched front end of the rotation prior.  Image z of a launch reads base + (index ? index[z] : z) * image_stride
+// (+ payload_off for u8 records); strides in elements (floats or bytes); base and index are device pointers
+struct FmtBatchSrc {
+    const void *base;
+    int64_t image_stride, row_stride;
+    int32_t payload_off, is_u8;
+    const int32_t *index;
+};
+// 2 nb images (nb sources, then nb targets): resize to rows x R, inverse warpPolar to 2R x 2R (cart), semilog warpPolar to dh x dw,
+// window, zero-padded M x N float64 planes: image z < nb -> planes + z M N, the others -> planes + (z + plane_gap) M N.
+// tab: cos, sin per log-polar row (2 dh doubles) | window per row (dh) | per column (dw); br: radius per column (dw floats);
+// small: 2 nb x rows x R floats, cart: 2 nb x 2R x 2R floats, lp_out (optional): 2 nb x dh x dw floats, the images before the window
+hipError_t launch_fmt_batch_front(hipStream_t st, const FmtBatchSrc &src, int nb, int rows, int clip, int R, int dw, int dh, int M, int N,
+                                  const double *tab, const float *br, float *small, float *cart, double *planes, int64_t plane_gap,
+                                  float *lp_out);
+// fft.hip: FMT.getRotationUsingFMT for n pairs on ctx->stream, blocking (one stream synchronisation per chunk of pairs).  Either
+// host float32 images (host_src / host_tgt, n each, strides in floats, `cols` columns per row) or resident u8 records (pool; pair i is
+// the records prev_idx[i], curr_idx[i], host arrays).  clip = range bins kept, R = columns after the resize.  The caller has checked
+// the arguments.  out3: n x 3 {angle_rad, scale, response}; logpolar_out: optional, 2 n x dh x dw
+struct FmtBatchIn {
+    const float *host_src = nullptr, *host_tgt = nullptr;
+    int64_t row_stride = 0, image_stride = 0;
+    int32_t cols = 0;
+    const uint8_t *pool = nullptr;
+    int64_t rec_bytes = 0, rec_stride = 0;
+    int32_t payload_off = 0;
+    const int32_t *prev_idx = nullptr, *curr_idx = nullptr;
+};
+int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows, int clip, int R, double *out3, float *logpolar_out);

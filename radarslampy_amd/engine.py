@@ -222,6 +222,22 @@ class Engine:
         self.set_features(lane, pts)
         return pts
 
+    def fmt_rotation(self, prev_pool_idx, curr_pool_idx, clip_px=1012, downsample=10):
+        """FMT.getRotationUsingFMT between resident scans (roam_engine_fmt_rotation): pair i is the pool records prev_pool_idx[i],
+        curr_pool_idx[i], read in place -> (n, 3) float64 rows (angle rad, scale, response).  Blocking; the range clip is
+        min(clip_px, the engine's clip).  ValueError before any device call for a bad index list, clip or downsample."""
+        prev = np.ascontiguousarray(prev_pool_idx, np.int32).ravel()
+        curr = np.ascontiguousarray(curr_pool_idx, np.int32).ravel()
+        if len(prev) < 1 or len(prev) != len(curr):
+            raise ValueError(f"fmt_rotation: two index lists of one length >= 1, not {len(prev)} and {len(curr)}")
+        if min(prev.min(), curr.min()) < 0 or max(prev.max(), curr.max()) >= self.pool_scans:
+            raise ValueError(f"fmt_rotation: pool indices in [0, {self.pool_scans})")
+        _ffi.fmt_clip_radius(self.cfg.clip, clip_px, downsample, self.rows)
+        out = np.empty((len(prev), 3), np.float64)
+        self.ctx.check(self.lib.roam_engine_fmt_rotation(self.ctx.h, len(prev), _ffi._ptr(prev), _ffi._ptr(curr), int(clip_px),
+                                                         int(downsample), _ffi._ptr(out)))
+        return out
+
     def lane_image(self, lane: int, level: int = 0):
         W = 2 * (self.cfg.clip // 2)
         for _ in range(level):
