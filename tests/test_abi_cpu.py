@@ -189,6 +189,7 @@ def test_native_blob_bookkeeping_matches_oracle_and_live_scipy():
             assert np.array_equal(got, want[want[:, 2] > 0]), t
         v = rng.choice([5.005, 10.0], size=n) if t % 3 else rng.standard_normal(n)
         assert np.array_equal(gf.argsort_numpy122(v), oracle.argsort_numpy122(v)), t
-    v = np.concatenate([np.arange(3000), np.arange(3000)[::-1]]).astype(float)       # organ pipe: deep recursion
+    # organ pipe: 40 segments of up to 698 keys use up the depth budget and are heapsorted (tests/sort_adversary_cases.py's model)
+    v = np.concatenate([np.arange(3000), np.arange(3000)[::-1]]).astype(float)
     assert np.array_equal(gf.argsort_numpy122(v), oracle.argsort_numpy122(v))
     assert len(gf._prune_blobs(np.zeros((0, 3)), 0.5)) == 0 and len(gf.argsort_numpy122(np.zeros(0))) == 0

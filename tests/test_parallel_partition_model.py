@@ -129,17 +129,33 @@ def test_parallel_partitions_equal_the_sequential_algorithms():
 
 
 # ---------------------------------------------------------------------------------------------- npy_aquicksort, segment by segment
+def aheapsort(v, ts, off, n):
+    """npy_aheapsort on ts[off : off + n]: 1-based sift-down, build phase, then extraction"""
+    def sift(tmp, i, n):
+        j = 2 * i
+        while j <= n:
+            if j < n and v[ts[off + j - 1]] < v[ts[off + j]]: j += 1
+            if not v[tmp] < v[ts[off + j - 1]]: break
+            ts[off + i - 1] = ts[off + j - 1]; i = j; j += j
+        ts[off + i - 1] = tmp
+    for l in range(n >> 1, 0, -1): sift(ts[off + l - 1], l, n)
+    while n > 1:
+        tmp = ts[off + n - 1]; ts[off + n - 1] = ts[off]; n -= 1
+        sift(tmp, 1, n)
+
+
 def aquicksort_par(v):
-    """segments in any order; partition by the list rule; insertion sorts at the end"""
+    """segments in any order; partition by the list rule; a popped segment whose depth budget is used up is heapsorted; insertion
+    sorts at the end"""
     n = len(v); ts = list(range(n))
     if n < 2: return ts
     cdepth = 0; k = n
     while k > 1: k >>= 1; cdepth += 1
     cdepth *= 2
-    work = [(0, n - 1, cdepth, True)]; leaves = []
+    work = [(0, n - 1, cdepth, True)]; leaves = []; del heapsorted[:]
     while work:
         pl, pr, cd, pushed = work.pop(rng_order.randrange(len(work)))       # any order
-        if pushed and cd < 0: raise RuntimeError("heapsort")
+        if pushed and cd < 0: heapsorted.append((pl, pr)); aheapsort(v, ts, pl, pr - pl + 1); continue
         if pr - pl <= 16: leaves.append((pl, pr)); continue
         pm = pl + ((pr - pl) >> 1)
         if v[ts[pm]] < v[ts[pl]]: ts[pm], ts[pl] = ts[pl], ts[pm]
@@ -167,6 +183,8 @@ def aquicksort_par(v):
     return ts
 
 
+heapsorted = []                                                               # the segments the last aquicksort_par call heapsorted
+
 
 def test_aquicksort_segments_in_any_order_with_list_rule_partitions():
     """csrc/retrack_blobs.hip rb_aquicksort_wave: NumPy 1.22's argsort (npy_aquicksort) with its segments processed in ANY order - each with
@@ -187,3 +205,23 @@ def test_aquicksort_segments_in_any_order_with_list_rule_partitions():
             v = [1.0 if rng.random() < f else 2.0 for _ in range(n)]
         want = oracle.argsort_numpy122(np.array(v)).tolist()
         assert aquicksort_par(v) == want, (t, n, nv)
+
+
+def test_aquicksort_segments_in_any_order_on_rows_that_reach_the_heapsort():
+    """the same property where the depth budget runs out (tests/sort_adversary_cases.py: McIlroy's adversary with ties in pairs, organ
+    pipes): whatever order the segments are taken in, the heapsort meets the same segments holding the same elements in the same
+    places, so the permutation is the sequential algorithm's"""
+    import numpy as np
+    import oracle
+    import sort_adversary_cases as sc
+    global rng_order
+    for name, row in sc.key_rows().items():
+        v = [float(k) for k in row.keys]
+        want = oracle.argsort_numpy122(np.array(v)).tolist()
+        reached = None
+        for seed in range(4):
+            rng_order = random.Random(seed)
+            assert aquicksort_par(v) == want, (name, seed)
+            assert reached in (None, sorted(heapsorted)), (name, seed)
+            reached = sorted(heapsorted)
+        assert bool(reached) == (row.kind != sc.CONTROL), (name, reached)
