@@ -257,6 +257,22 @@ int32_t roam_fmt_rotation_batch_f32(roam_ctx *ctx, const float *src, const float
                                     int64_t row_stride, int64_t image_stride, int32_t clip_px, int32_t downsample, double *out3,
                                     float *logpolar_out);
 
+/* Fourier-Mellin registration of n pairs, rotation and then translation, in one device pass (FMT.py:211-250 estimates the rotation;
+ * plotCartPolarWithRotation, FMT.py:134-168, applies it as rotateImg(prevImgCart, rotDeg); the method cited at FMT.py:79 ends with a
+ * second phase correlation, of the de-rotated Cartesian images).  Per pair: {angle_rad, scale, rot_response} exactly as
+ * roam_fmt_rotation_batch_f32 gives them; srcCart, tgtCart = convertPolarImageToCartesian(., downsampleFactor = cart_downsample) of the
+ * full-width polar images (FMT.py:191, 213: 2Rc x 2Rc, Rc = cols / cart_downsample; roam_warp_polar_f32's arithmetic);
+ * srcRot = rotateImg(srcCart, degrees(angle_rad)) (FMT.py:93-100; roam_warp_affine_f32's arithmetic, the matrix made and inverted on
+ * the host in float64); {(dx, dy), trans_response} = cv2.phaseCorrelate(srcRot, tgtCart, Hanning window) (FMT.py:13-33;
+ * roam_phase_correlate_f32's arithmetic), dx, dy in pixels of the 2Rc x 2Rc image.  out6 (n, 6) f64
+ * {angle_rad, scale, rot_response, dx, dy, trans_response}.  cart_out: NULL, or (2 n, 2Rc, 2Rc) f32: the turned sources, then the target
+ * Cartesian images, before the window (for tests).  Chunks as roam_fmt_rotation_batch_f32, two stream synchronisations per chunk
+ * (the angles come to the host, whose libm makes the matrices); the result of a pair does not depend on the batch it is in.
+ * ROAM_E_ARG: whatever roam_fmt_rotation_batch_f32 refuses, cols > 16384, cart_downsample < 1, 2Rc outside [2, 4096]. */
+int32_t roam_fmt_register_batch_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t n, int32_t rows, int32_t cols,
+                                    int64_t row_stride, int64_t image_stride, int32_t clip_px, int32_t downsample,
+                                    int32_t cart_downsample, double *out6, float *cart_out);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous
@@ -365,6 +381,13 @@ int32_t roam_engine_doh_maxima(roam_ctx *ctx, int32_t pool_idx, const double *si
  * [ROAM_FMT_MIN_R, ROAM_FMT_MAX_R]. */
 int32_t roam_engine_fmt_rotation(roam_ctx *ctx, int32_t n, const int32_t *prev_pool_idx, const int32_t *curr_pool_idx, int32_t clip_px,
                                  int32_t downsample, double *out3);
+/* roam_fmt_register_batch_f32's pass (FMT.py:211-250, 134-168, 13-33) for the n pairs of pool records (prev_pool_idx[i],
+ * curr_pool_idx[i]), read in place as float(u8) / 255.0f by both halves.  Blocking and read-only like roam_engine_fmt_rotation.  The
+ * rotation half clips at min(clip_px, cfg.clip); the Cartesian half reads the record's full clipped width, Rc = cfg.clip /
+ * cart_downsample.  out6 (n, 6) f64 {angle_rad, scale, rot_response, dx, dy, trans_response}.  ROAM_E_ARG: whatever
+ * roam_engine_fmt_rotation refuses, cart_downsample < 1, 2Rc outside [2, 4096]. */
+int32_t roam_engine_fmt_register(roam_ctx *ctx, int32_t n, const int32_t *prev_pool_idx, const int32_t *curr_pool_idx, int32_t clip_px,
+                                 int32_t downsample, int32_t cart_downsample, double *out6);
 /* blocking: level `level` (0..3) of the lane's most recent Cartesian u8 pyramid (w*h bytes, row-major) */
 int32_t roam_engine_lane_image(roam_ctx *ctx, int32_t lane, int32_t level, uint8_t *out, int64_t cap);
 /* replace a lane's feature set (retrack append, getFeatures.appendNewFeatures getFeatures.py:98-118) */

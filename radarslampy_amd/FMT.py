@@ -1,5 +1,6 @@
 """Fourier-Mellin registration with the reference's names (reference FMT.py:10-100): the rotation prior (csrc/fmt.hip; batches of
-pairs: csrc/fmt_batch.hip), the translation by phase correlation (csrc/fft.hip) and the rotation of an image (csrc/warpaffine.hip);
+pairs: csrc/fmt_batch.hip), the translation by phase correlation (csrc/fft.hip), the rotation of an image (csrc/warpaffine.hip) and the chain of the three in one
+device pass (getTransformUsingFMT, csrc/fmt_register.hip);
 the computation runs on the MI355X.  SURVEY §8f-f4."""
 import math
 
@@ -10,6 +11,7 @@ from .parseData import RANGE_RESOLUTION_CART_M
 
 FMT_DOWNSAMPLE_FACTOR = 10      # FMT.py:10
 FMT_RANGE_CLIP_M = 87.5         # FMT.py:11
+FMT_CART_DOWNSAMPLE_FACTOR = 20 # FMT.py:191, 213: the Cartesian images of the script
 
 
 def getTranslationUsingPhaseCorrelation(srcImg, targetImg):
@@ -31,6 +33,26 @@ def getRotationUsingFMT(srcPolarImg, targetPolarImg, downsampleFactor: int = FMT
         out = _ffi.default_context().fmt_rotation_batch(srcPolarImg, targetPolarImg, clip_px=clip, downsample=int(downsampleFactor))
         return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
     return _ffi.default_context().fmt_rotation(srcPolarImg, targetPolarImg, clip_px=clip, downsample=int(downsampleFactor))
+
+
+def getTransformUsingFMT(srcPolarImg, targetPolarImg, downsampleFactor: int = FMT_DOWNSAMPLE_FACTOR, maxRangeClipM=FMT_RANGE_CLIP_M,
+                         cartDownsampleFactor: int = FMT_CART_DOWNSAMPLE_FACTOR):
+    """The whole registration in one device pass (roam_fmt_register_batch_f32) -> (angleRad, (dx, dy), scale, rotResponse,
+    transResponse): getRotationUsingFMT's estimate (FMT.py:211-250), then rotateImg(srcCart, degrees(angleRad)) on the Cartesian
+    images at cartDownsampleFactor (FMT.py:134-168, 191) and getTranslationUsingPhaseCorrelation(srcRot, targetCart).  (dx, dy) are
+    pixels of that Cartesian image (metres: px * RANGE_RESOLUTION_M * cartDownsampleFactor); they come out as minus the ego motion
+    in the source frame.  2-D polar images give scalars, 3-D batches arrays with one entry per pair, (dx, dy) of shape (n, 2).
+    Different shapes: AssertionError; other argument errors ValueError (TypeError for a cartDownsampleFactor that is no integer)
+    before any device call."""
+    assert np.shape(srcPolarImg) == np.shape(targetPolarImg), "Images need to have the same shape!"
+    clip = int(maxRangeClipM / RANGE_RESOLUTION_CART_M) if maxRangeClipM > 0 else 0
+    _ffi.fmt_register_batch_args(srcPolarImg, targetPolarImg, clip, int(downsampleFactor), cartDownsampleFactor)
+    out = _ffi.default_context().fmt_register_batch(srcPolarImg, targetPolarImg, clip_px=clip, downsample=int(downsampleFactor),
+                                                    cart_downsample=cartDownsampleFactor)
+    if np.ndim(srcPolarImg) == 3:
+        return out[:, 0].copy(), out[:, 3:5].copy(), out[:, 1].copy(), out[:, 2].copy(), out[:, 5].copy()
+    angle, scale, rot_resp, dx, dy, trans_resp = (float(v) for v in out[0])
+    return angle, (dx, dy), scale, rot_resp, trans_resp
 
 
 def getRotationMatrix2D(center, angle, scale):

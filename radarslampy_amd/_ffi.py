@@ -1,6 +1,7 @@
 """ctypes binding of libroam_hip.so (include/roam_abi.h).  No torch, no CPU fallback: if
 the HIP library or a gfx950 device is missing every compute call raises RoamError."""
 import ctypes as C
+import numbers
 import os
 import threading
 
@@ -18,6 +19,7 @@ TIME_FFT_FIVE, TIME_DFT_FIVE, TIME_FFT_ROWS, TIME_FFT_TRANSPOSE, TIME_FFT_COLS =
 PHASE_CORRELATE_MAX = 4096      # largest image side of roam_phase_correlate_f32
 FMT_MIN_R, FMT_MAX_R = 4, 1303  # roam_abi.h ROAM_FMT_MIN_R / ROAM_FMT_MAX_R: columns after the resize of the batched rotation prior
 FMT_MAX_ROWS = 16384            # ... and its largest number of polar rows
+FMT_MAX_COLS = 16384            # widest polar image the Cartesian half of the registration reads (roam_fmt_register_batch_f32)
 MAX_FEATURES = 1024
 STEP_NEW_SEQUENCE = 0x40000000      # roam_abi.h ROAM_STEP_NEW_SEQUENCE: OR into a lane's scan index
 
@@ -110,6 +112,7 @@ _SIGS = {
     "roam_engine_lane_peaks": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int64, _P(C.c_int64)]),
     "roam_engine_doh_maxima": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, C.c_double, _vp, _vp, C.c_int32, _P(C.c_int32)]),
     "roam_engine_fmt_rotation": (C.c_int32, [_vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "roam_engine_fmt_register": (C.c_int32, [_vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "roam_engine_lane_image": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, C.c_int64]),
     "roam_engine_set_features": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32]),
     "roam_engine_kernel_avg": (C.c_int32, [_vp, C.c_char_p, C.c_int32, _P(C.c_float), _P(C.c_int32)]),
@@ -126,6 +129,8 @@ _SIGS = {
     "roam_phase_correlate_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp]),
     "roam_fmt_rotation_batch_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                                 _vp, _vp]),
+    "roam_fmt_register_batch_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                C.c_int32, _vp, _vp]),
     "roam_debug_fft2_f64": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_time_fft2": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
     "roam_prune_blobs": (C.c_int32, [_vp, C.c_int32, C.c_double, _vp]),
@@ -212,6 +217,31 @@ def fmt_rotation_batch_args(src, tgt, clip_px, downsample):
         raise ValueError(f"fmt_rotation_batch: at least 2 columns, not {cols}")
     clip, R = fmt_clip_radius(cols, clip_px, downsample, rows)
     return a, b, clip, R
+
+
+def fmt_cart_radius(cols, cart_downsample):
+    """The Cartesian half of the registration: Rc = cols // cart_downsample, checked as the library checks it.  TypeError for a
+    cart_downsample that is no integer (as convertPolarImageToCartesian); ValueError for one below 1, for more than 16384 columns,
+    or for a side 2 Rc outside [2, 4096], the phase correlation's limit."""
+    if not isinstance(cart_downsample, numbers.Integral):
+        raise TypeError(f"fmt_register: cart_downsample must be an integer, not {type(cart_downsample).__name__}")
+    cart_downsample = int(cart_downsample)
+    if cart_downsample < 1:
+        raise ValueError(f"fmt_register: cart_downsample >= 1, not {cart_downsample}")
+    if cols > FMT_MAX_COLS:
+        raise ValueError(f"fmt_register: at most {FMT_MAX_COLS} columns, not {cols}")
+    Rc = cols // cart_downsample
+    if not 2 <= 2 * Rc <= PHASE_CORRELATE_MAX:
+        raise ValueError(f"fmt_register: a Cartesian side 2 * (cols // cart_downsample) in [2, {PHASE_CORRELATE_MAX}], not "
+                         f"2 * ({cols} // {cart_downsample}) = {2 * Rc}")
+    return Rc
+
+
+def fmt_register_batch_args(src, tgt, clip_px, downsample, cart_downsample):
+    """The argument checks of Context.fmt_register_batch, made before any device call -> (src, tgt as arrays, clip, R, Rc):
+    fmt_rotation_batch_args's (AssertionError for different shapes, else ValueError), then fmt_cart_radius's."""
+    a, b, clip, R = fmt_rotation_batch_args(src, tgt, clip_px, downsample)
+    return a, b, clip, R, fmt_cart_radius(a.shape[-1], cart_downsample)
 
 
 def invert_affine(M):
@@ -551,6 +581,28 @@ class Context:
         self.check(self.lib.roam_fmt_rotation_batch_f32(self.h, _ptr(a3), _ptr(b3), n, rows, cols, row_stride, image_stride, int(clip_px),
                                                         int(downsample), _ptr(out), _ptr(lp)))
         return (out, lp) if want_logpolar else out
+
+    def fmt_register_batch(self, src, tgt, clip_px=1012, downsample=10, cart_downsample=20, want_images=False):
+        """Fourier-Mellin registration of a batch of pairs in one device pass (roam_fmt_register_batch_f32): two 2-D polar images or
+        two 3-D batches of one shape -> (n, 6) float64 rows (angle rad, scale, rotation response, dx, dy, translation response);
+        columns 0-2 are fmt_rotation_batch's, (dx, dy) = phaseCorrelate(rotateImg(srcCart, degrees(angle)), tgtCart) in pixels of the
+        Cartesian image at cart_downsample (metres: px * RANGE_RESOLUTION_M * cart_downsample).  want_images: also the Cartesian images
+        before the window, (2 n, 2 Rc, 2 Rc) float32, Rc = cols // cart_downsample: the turned sources first, then the targets.
+        float32 views with unit column stride are read in place, anything else is made float32-contiguous.  Arguments are checked by
+        fmt_register_batch_args before any device call."""
+        a, b, clip, R, Rc = fmt_register_batch_args(src, tgt, clip_px, downsample, cart_downsample)
+        a, b = _f32_rows_in_place(a), _f32_rows_in_place(b)
+        a3, b3 = (a, b) if a.ndim == 3 else (a[None], b[None])
+        n, rows, cols = a3.shape
+        if a3.strides[0 if n > 1 else 1:] != b3.strides[0 if n > 1 else 1:]:     # one pair of strides describes both operands
+            a3, b3 = np.ascontiguousarray(a3), np.ascontiguousarray(b3)
+        row_stride = a3.strides[1] // 4
+        image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+        out = np.empty((n, 6), np.float64)
+        imgs = np.empty((2 * n, 2 * Rc, 2 * Rc), np.float32) if want_images else None
+        self.check(self.lib.roam_fmt_register_batch_f32(self.h, _ptr(a3), _ptr(b3), n, rows, cols, row_stride, image_stride, int(clip_px),
+                                                        int(downsample), int(cart_downsample), _ptr(out), _ptr(imgs)))
+        return (out, imgs) if want_images else out
 
     def phase_correlate(self, src, tgt, hanning=True):
         """FMT.getTranslationUsingPhaseCorrelation: cv2.phaseCorrelate(src, tgt[, cv2.createHanningWindow((cols, rows), CV_32F)])

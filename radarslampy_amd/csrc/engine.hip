@@ -1562,6 +1562,25 @@ int32_t roam_engine_fmt_rotation(roam_ctx *ctx, int32_t n, const int32_t *prev_p
     return roam_fmt_batch_run(ctx, in, n, e->cfg.rows, clip, R, out3, nullptr);
 }
 
+int32_t roam_engine_fmt_register(roam_ctx *ctx, int32_t n, const int32_t *prev_pool_idx, const int32_t *curr_pool_idx, int32_t clip_px,
+                                 int32_t downsample, int32_t cart_downsample, double *out6)
+{
+    ENGINE();
+    ARG_CHECK(ctx, n >= 1 && prev_pool_idx && curr_pool_idx && out6 && downsample >= 1 && cart_downsample >= 1 && e->cfg.rows >= 8);
+    for (int i = 0; i < n; i++)
+        ARG_CHECK(ctx, prev_pool_idx[i] >= 0 && prev_pool_idx[i] < e->cfg.pool_scans && curr_pool_idx[i] >= 0 && curr_pool_idx[i] < e->cfg.pool_scans);
+    const int clip = (clip_px > 0 && clip_px < e->cfg.clip) ? clip_px : e->cfg.clip;
+    const int R = clip / downsample, Rc = e->cfg.clip / cart_downsample;
+    ARG_CHECK(ctx, R >= ROAM_FMT_MIN_R && R <= ROAM_FMT_MAX_R && Rc >= 1 && 2 * Rc <= 4096 && e->cfg.clip <= 16384);
+    // as roam_engine_fmt_rotation: behind every step enqueued so far and the uploads of the pool, the engine's bookkeeping untouched
+    if (e->uploads_pending) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_up, 0));
+    FmtBatchIn in;
+    in.pool = e->pool; in.rec_bytes = (int64_t)e->rec_bytes; in.rec_stride = e->cfg.stride; in.payload_off = e->cfg.payload_off;
+    in.prev_idx = prev_pool_idx; in.curr_idx = curr_pool_idx;
+    in.cols = e->cfg.clip;                                   // the Cartesian half reads the record's full clipped width
+    return roam_fmt_register_run(ctx, in, n, e->cfg.rows, clip, R, Rc, out6, nullptr);
+}
+
 int32_t roam_engine_lane_image(roam_ctx *ctx, int32_t lane, int32_t level, uint8_t *out, int64_t cap)
 {
     ENGINE();

@@ -14,6 +14,8 @@
 //             exchanges the plane pointers, the kernel is the forward one.
 // The batched rotation prior (roam_fmt_rotation_batch_f32, roam_engine_fmt_rotation) runs the same correlation on planes that the
 // kernels of fmt_batch.hip fill: its driver roam_fmt_batch_run is here because the row pass and the transpose are local to this unit.
+// The registration (roam_fmt_register_batch_f32, roam_engine_fmt_register) adds a second correlation, on the Cartesian images that the
+// kernels of fmt_register.hip make and turn by the angle of the first: roam_fmt_register_run.
 #include "roam_internal.h"
 #include <math.h>
 #include <stdlib.h>
@@ -500,7 +502,7 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
         } else {
             HIP_TRY(ctx, hipMemcpyAsync(d_idx, in.prev_idx + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
             HIP_TRY(ctx, hipMemcpyAsync(d_idx + nb, in.curr_idx + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
-            src = {in.pool, in.rec_bytes, in.rec_stride, in.payload_off, 1, d_idx};
+            src = {in.pool, in.rec_bytes, in.rec_stride, in.payload_off, in.pool_f32 ? 0 : 1, d_idx};
         }
         HIP_TRY(ctx, launch_fmt_batch_front(st, src, nb, rows, clip, R, dw, dh, M, N, d_tabd, d_br, d_small, d_cart, d_f, (int64_t)4 * nb, d_lp));
         for (int k = 0; k < 2; k++) {
@@ -550,6 +552,141 @@ extern "C" int32_t roam_fmt_rotation_batch_f32(roam_ctx *ctx, const float *src, 
     in.host_src = src; in.host_tgt = tgt; in.row_stride = row_stride; in.image_stride = n == 1 ? (int64_t)rows * row_stride : image_stride;
     in.cols = cols;
     return roam_fmt_batch_run(ctx, in, n, rows, clip, R, out3, logpolar_out);
+}
+
+// ------------------------------------------------------------------------------------------------ batched registration
+// Rotation, then translation, for n pairs (FMT.py:211-250, then rotateImg(prevImgCart, rotDeg) and a phase correlation of the turned
+// source with the target).  Per chunk of nb pairs: roam_fmt_batch_run gives the angles and brings them to the host (first
+// synchronisation); the host makes the nb inverse rotation matrices with its libm, as roam_warp_affine_f32 does; the kernels of
+// fmt_register.hip make the 2 nb Cartesian images and fill the planes, laid out as in roam_fmt_batch_run; the correlation and the peak
+// search are the ones above (second synchronisation).  Host images go up once, whole, and both halves read them on the device.
+// The halves share S_TMP0 .. S_TMP3 and S_OUT0, one after the other: the second takes them (again) only after the first has returned,
+// its results on the host.  What only this pass uses lies in slots that roam_fmt_batch_run does not touch.
+int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows, int clip, int R, int Rc, double *out6, float *cart_out)
+{
+    const int S = 2 * Rc;
+    ARG_CHECK(ctx, S >= 2 && S <= FFT_MAX_N);
+    const int M = optimal_dft_size(S), N = M;
+    const bool host = in.host_src != nullptr;
+    const size_t nmn = (size_t)M * N, ncart = (size_t)S * S, nin = host ? (size_t)rows * in.cols : 0;
+    // the rotation half per pair, as roam_fmt_batch_run counts it for resident images, and this half (the shared planes count twice):
+    // a chunk of this size is one chunk there too
+    const int Wr = 2 * R, dwr = (int)rint((double)R), dhr = (int)rint((double)R * M_PI);
+    const size_t per_rot = 7 * sizeof(double) * (size_t)optimal_dft_size(dhr) * optimal_dft_size(dwr)
+                           + 2 * sizeof(float) * ((size_t)rows * R + (size_t)Wr * Wr) + 2 * sizeof(int32_t);
+    const size_t per_reg = 7 * sizeof(double) * nmn + sizeof(float) * (2 * ncart + (cart_out ? ncart : 0) + 2 * nin) + 6 * sizeof(double)
+                           + 2 * sizeof(int32_t);
+    size_t chunk = ((size_t)2000 << 20) / (per_rot + per_reg);
+    if (chunk < 1) chunk = 1;
+    if (chunk > (size_t)n) chunk = n;
+    if (chunk > 32767) chunk = 32767;                        // 2 chunk images in grid.z
+    if (const char *ce = getenv("ROAM_FMT_BATCH_CHUNK")) {   // tests: a small chunk (read per call)
+        const long c = atol(ce);
+        if (c >= 1 && (size_t)c < chunk) chunk = (size_t)c;
+    }
+    const int per = (int)((nmn + 1023) / 1024) < 1024 ? 1024 : (int)((nmn + 1023) / 1024);
+    const int nblk = (int)((nmn + per - 1) / per);
+    hipStream_t st = ctx->stream;
+    float *d_img = host ? (float *)roam_scratch(ctx, S_IN2, sizeof(float) * nin * 2 * chunk) : nullptr;
+    int32_t *d_idx = host ? nullptr : (int32_t *)roam_scratch(ctx, S_IN3, sizeof(int32_t) * 2 * chunk);
+    float *d_cart = (float *)roam_scratch(ctx, S_TMP7, sizeof(float) * ncart * 2 * chunk);
+    float *d_rot = cart_out ? (float *)roam_scratch(ctx, S_OUT1, sizeof(float) * ncart * chunk) : nullptr;
+    double *d_M = (double *)roam_scratch(ctx, S_OUT2, sizeof(double) * 6 * chunk);
+    if ((host && !d_img) || (!host && !d_idx) || !d_cart || (cart_out && !d_rot) || !d_M) return ROAM_E_HIP;
+    std::vector<double> win(2 * (size_t)S), o3(3 * chunk), o(3 * chunk), Mh(6 * chunk);
+    for (int k = 0; k < S; k++) win[k] = win[S + k] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(S - 1) * (double)k));
+    std::vector<int32_t> iota;
+    if (host) {
+        iota.resize(2 * chunk);
+        for (size_t i = 0; i < 2 * chunk; i++) iota[i] = (int32_t)i;
+    }
+    for (size_t b0 = 0; b0 < (size_t)n; b0 += chunk) {
+        const int nb = (int)(((size_t)n - b0) < chunk ? ((size_t)n - b0) : chunk);
+        FmtBatchIn rin = in;
+        FmtBatchSrc src;
+        if (host) {
+            const float *h[2] = {in.host_src, in.host_tgt};
+            for (int k = 0; k < 2; k++) {
+                float *d = d_img + (size_t)k * nb * nin;
+                const float *h0 = h[k] + (int64_t)b0 * in.image_stride;
+                if (in.row_stride == in.cols && (nb == 1 || in.image_stride == (int64_t)nin))
+                    HIP_TRY(ctx, hipMemcpyAsync(d, h0, sizeof(float) * nin * nb, hipMemcpyHostToDevice, st));
+                else
+                    for (int i = 0; i < nb; i++)
+                        HIP_TRY(ctx, hipMemcpy2DAsync(d + (size_t)i * nin, sizeof(float) * in.cols, h0 + (int64_t)i * in.image_stride,
+                                                      sizeof(float) * in.row_stride, sizeof(float) * in.cols, rows, hipMemcpyHostToDevice, st));
+            }
+            rin = FmtBatchIn();
+            rin.pool = (const uint8_t *)d_img; rin.rec_bytes = (int64_t)nin; rin.rec_stride = in.cols; rin.pool_f32 = 1;
+            rin.prev_idx = iota.data(); rin.curr_idx = iota.data() + nb;
+            src = {d_img, (int64_t)nin, (int64_t)in.cols, 0, 0, nullptr};
+        } else {
+            rin.prev_idx = in.prev_idx + b0; rin.curr_idx = in.curr_idx + b0;
+            HIP_TRY(ctx, hipMemcpyAsync(d_idx, in.prev_idx + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_idx + nb, in.curr_idx + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
+            src = {in.pool, in.rec_bytes, in.rec_stride, in.payload_off, 1, d_idx};
+        }
+        FFT_TRY(roam_fmt_batch_run(ctx, rin, nb, rows, clip, R, o3.data(), nullptr));            // synchronises: the angles are here
+        const double c = (double)(float)Rc;                  // getRotationMatrix2D's centre (w / 2, h / 2) as a cv::Point2f
+        for (int i = 0; i < nb; i++) roam_rotation_inverse_map(c, c, o3[3 * i] * (180.0 / M_PI), &Mh[6 * (size_t)i]);
+        double *d_f = (double *)roam_scratch(ctx, S_TMP2, sizeof(double) * nmn * 7 * chunk);
+        double *d_win = (double *)roam_scratch(ctx, S_TMP1, sizeof(double) * win.size());
+        double *d_pv = (double *)roam_scratch(ctx, S_TMP0, sizeof(double) * (size_t)nblk * chunk);
+        int *d_pi = (int *)roam_scratch(ctx, S_TMP3, sizeof(int) * (size_t)nblk * chunk);
+        double *d_out = (double *)roam_scratch(ctx, S_OUT0, sizeof(double) * 3 * chunk);
+        if (!d_f || !d_win || !d_pv || !d_pi || !d_out) return ROAM_E_HIP;
+        const size_t pl = nmn * nb;
+        double *a = d_f, *tr = d_f + pl, *ti = d_f + 2 * pl, *F[2][2] = {{d_f + 3 * pl, d_f + 4 * pl}, {d_f + 5 * pl, d_f + 6 * pl}};
+        double *wpl[2] = {a, F[1][0]};                       // the windowed images: turned sources, targets
+        HIP_TRY(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(double) * win.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d_M, Mh.data(), sizeof(double) * 6 * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, launch_fmtr_cart(st, src, 2 * nb, rows, in.cols, Rc, d_cart));
+        HIP_TRY(ctx, launch_fmtr_rotate_window(st, d_cart, S, M, N, nb, (int64_t)4 * nb, d_M, d_win, d_f, d_rot));
+        for (int k = 0; k < 2; k++) {
+            FFT_TRY(fft_rows(ctx, wpl[k], nullptr, tr, ti, (int64_t)nb * M, N, false));
+            FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, F[k][0], F[k][1]));
+            FFT_TRY(fft_rows(ctx, F[k][0], F[k][1], F[k][0], F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
+        }
+        HIP_TRY(ctx, launch_fmt_cross_power(st, F[0][0], F[0][1], F[1][0], F[1][1], (int)pl, tr, ti));
+        FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
+        FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, F[0][0], F[0][1]));
+        FFT_TRY(fft_rows(ctx, F[0][0], F[0][1], a, nullptr, (int64_t)nb * M, N, true));                  // real part only
+        hipLaunchKernelGGL(pc_peak_partial_kernel, dim3(nblk, nb), dim3(256), 0, st, a, M, N, per, d_pv, d_pi);
+        hipLaunchKernelGGL(pc_peak_final_kernel, dim3(nb), dim3(256), 0, st, a, M, N, nblk, d_pv, d_pi, d_out);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
+        if (cart_out) {
+            HIP_TRY(ctx, hipMemcpyAsync(cart_out + b0 * ncart, d_rot, sizeof(float) * ncart * nb, hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipMemcpyAsync(cart_out + ((size_t)n + b0) * ncart, d_cart + (size_t)nb * ncart, sizeof(float) * ncart * nb,
+                                        hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (int i = 0; i < nb; i++) {
+            double *q = out6 + 6 * (b0 + i);
+            q[0] = o3[3 * i]; q[1] = o3[3 * i + 1]; q[2] = o3[3 * i + 2];
+            q[3] = o[3 * i]; q[4] = o[3 * i + 1]; q[5] = o[3 * i + 2];
+        }
+    }
+    return ROAM_OK;
+}
+
+extern "C" int32_t roam_fmt_register_batch_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t n, int32_t rows, int32_t cols,
+                                               int64_t row_stride, int64_t image_stride, int32_t clip_px, int32_t downsample,
+                                               int32_t cart_downsample, double *out6, float *cart_out)
+{
+    if (!ctx) return ROAM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ARG_CHECK(ctx, src && tgt && out6 && n >= 1);
+    ARG_CHECK(ctx, rows >= 8 && rows <= 16384 && cols >= 2 && cols <= 16384 && downsample >= 1 && cart_downsample >= 1);
+    ARG_CHECK(ctx, row_stride >= cols && (n == 1 || image_stride >= (int64_t)(rows - 1) * row_stride + cols));
+    const int clip = (clip_px > 0 && clip_px < cols) ? clip_px : cols;
+    const int R = clip / downsample, Rc = cols / cart_downsample;
+    ARG_CHECK(ctx, R >= ROAM_FMT_MIN_R && R <= ROAM_FMT_MAX_R);
+    ARG_CHECK(ctx, 2 * Rc >= 2 && 2 * Rc <= FFT_MAX_N);
+    FmtBatchIn in;
+    in.host_src = src; in.host_tgt = tgt; in.row_stride = row_stride; in.image_stride = n == 1 ? (int64_t)rows * row_stride : image_stride;
+    in.cols = cols;
+    return roam_fmt_register_run(ctx, in, n, rows, clip, R, Rc, out6, cart_out);
 }
 
 // ------------------------------------------------------------------------------------------------ test / measurement entries

@@ -222,5 +222,22 @@ struct FmtBatchIn {
     int64_t rec_bytes = 0, rec_stride = 0;
     int32_t payload_off = 0;
     const int32_t *prev_idx = nullptr, *curr_idx = nullptr;
+    int32_t pool_f32 = 0;     // the pool holds float32 images on the device (rec_bytes / rec_stride in floats), not u8 records
 };
 int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows, int clip, int R, double *out3, float *logpolar_out);
+
+// fmt_register.hip: the front end of the translation half of the Fourier-Mellin registration.  launch_fmtr_cart: nimg polar images
+// (FmtBatchSrc, rows x cols, read in place) -> cart (nimg x 2Rc x 2Rc floats), the inverse linear warpPolar with centre (Rc, Rc) and
+// maxRadius Rc.  launch_fmtr_rotate_window: cart = nb sources, then nb targets, S x S each; source z is turned by Minv + 6 z
+// (destination -> source), [stored to rot_out, nb x S x S,] windowed (win: S row factors, then S column factors) and zero-padded into
+// plane z of M x N doubles, target z into plane z + plane_gap.
+hipError_t launch_fmtr_cart(hipStream_t st, const FmtBatchSrc &src, int nimg, int rows, int cols, int Rc, float *cart);
+hipError_t launch_fmtr_rotate_window(hipStream_t st, const float *cart, int S, int M, int N, int nb, int64_t plane_gap, const double *Minv,
+                                     const double *win, double *planes, float *rot_out);
+// warpaffine.hip: the inverse (destination -> source) of cv2.getRotationMatrix2D((cx, cy), angle_deg, 1.0), host float64
+void roam_rotation_inverse_map(double cx, double cy, double angle_deg, double *Minv);
+// fft.hip: the registration of n pairs on ctx->stream, blocking: per chunk of pairs roam_fmt_batch_run (one synchronisation: the
+// angles come to the host, which makes the matrices), then the Cartesian images, the turn, the window and the second correlation (one
+// more).  `in` as for roam_fmt_batch_run, in.cols = the polar width the Cartesian half reads (all of it); Rc = in.cols / cart_downsample.
+// out6: n x 6 {angle_rad, scale, rot_response, dx, dy, trans_response}; cart_out: optional, 2 n x 2Rc x 2Rc (turned sources, targets)
+int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows, int clip, int R, int Rc, double *out6, float *cart_out);

@@ -72,6 +72,16 @@ static void wa_invert(const double *in, double *M)
     M[2] = b1; M[5] = b2;
 }
 
+// rotateImg's matrix (FMT.py:93-100) as warpAffine applies it: cv2.getRotationMatrix2D((cx, cy), angle_deg, 1.0) in float64 - the centre is
+// a cv::Point2f, the caller passes float32 values - inverted by wa_invert -> Minv[6], destination -> source
+void roam_rotation_inverse_map(double cx, double cy, double angle_deg, double *Minv)
+{
+    const double rad = angle_deg * M_PI / 180.0;
+    const double a = cos(rad), b = sin(rad);
+    const double M[6] = {a, b, (1 - a) * cx - b * cy, -b, a, b * cx + (1 - a) * cy};
+    wa_invert(M, Minv);
+}
+
 static void wa_launch(hipStream_t st, const float *d_in, int n, int rows, int cols, const double *d_M, int m_count, float *d_out, int dw,
                       int dh)
 {

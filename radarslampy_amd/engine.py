@@ -238,6 +238,25 @@ class Engine:
                                                          int(downsample), _ffi._ptr(out)))
         return out
 
+    def fmt_register(self, prev_pool_idx, curr_pool_idx, clip_px=1012, downsample=10, cart_downsample=20):
+        """Fourier-Mellin registration between resident scans (roam_engine_fmt_register): pair i is the pool records prev_pool_idx[i],
+        curr_pool_idx[i], read in place -> (n, 6) float64 rows (angle rad, scale, rotation response, dx, dy, translation response) as
+        Context.fmt_register_batch gives them for the decoded images.  Blocking and read-only; the rotation half clips at
+        min(clip_px, the engine's clip), the Cartesian half reads the record's full clipped width.  ValueError (TypeError for a
+        cart_downsample that is no integer) before any device call for a bad index list, clip or downsample."""
+        prev = np.ascontiguousarray(prev_pool_idx, np.int32).ravel()
+        curr = np.ascontiguousarray(curr_pool_idx, np.int32).ravel()
+        if len(prev) < 1 or len(prev) != len(curr):
+            raise ValueError(f"fmt_register: two index lists of one length >= 1, not {len(prev)} and {len(curr)}")
+        if min(prev.min(), curr.min()) < 0 or max(prev.max(), curr.max()) >= self.pool_scans:
+            raise ValueError(f"fmt_register: pool indices in [0, {self.pool_scans})")
+        _ffi.fmt_clip_radius(self.cfg.clip, clip_px, downsample, self.rows)
+        _ffi.fmt_cart_radius(self.cfg.clip, cart_downsample)
+        out = np.empty((len(prev), 6), np.float64)
+        self.ctx.check(self.lib.roam_engine_fmt_register(self.ctx.h, len(prev), _ffi._ptr(prev), _ffi._ptr(curr), int(clip_px),
+                                                         int(downsample), int(cart_downsample), _ffi._ptr(out)))
+        return out
+
     def lane_image(self, lane: int, level: int = 0):
         W = 2 * (self.cfg.clip // 2)
         for _ in range(level):
