@@ -150,6 +150,11 @@ _SIGS = {
     "roam_remote_map_get": (C.c_int32, [_vp, C.c_int32, _P(KeyframeHdr), _P(C.c_int32), _vp, C.c_int32, _vp, C.c_int64]),
 }
 ABI_SYMBOLS = tuple(_SIGS)
+# entry points for the tests only: exported by the library, not declared in include/roam_abi.h
+_INTERNAL_SIGS = {
+    "roam_pyr_down2_u8": (C.c_int32, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                      _P(C.c_int32)]),
+}
 
 
 def peak_conditions(distance=None, prominence=None):
@@ -306,7 +311,7 @@ def load_library():
             raise RoamError(ROAM_E_NODEVICE, f"{LIB_PATH} not built - run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(LIB_PATH)
         partial = bool(os.environ.get("ROAM_LIB_PARTIAL"))      # a host-only build (profiles/asan_cpu.sh): the symbols it has
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_INTERNAL_SIGS.items()):
             if partial and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
@@ -474,6 +479,15 @@ class Context:
         out = np.empty(((h + 1) // 2, (w + 1) // 2), np.uint8)
         self.check(self.lib.roam_pyr_down_u8(self.h, _ptr(img), w, h, _ptr(out)))
         return out
+
+    def pyr_down2_u8(self, buf, w, h, lanes, lane_stride, offs):
+        """levels 2 and 3 of `lanes` pyramids from their w x h level 1, in place in `buf` (u8, the whole pyramid storage: level l of lane
+        b at b * lane_stride + offs[l - 1]), by the two-level branch of the pyramid builder -> "rows" or "wave", the kernel it took"""
+        assert buf.dtype == np.uint8 and buf.flags.c_contiguous and buf.ndim == 1
+        k = C.c_int32(0)
+        self.check(self.lib.roam_pyr_down2_u8(self.h, _ptr(buf), buf.size, int(w), int(h), int(lanes), int(lane_stride),
+                                              int(offs[0]), int(offs[1]), int(offs[2]), C.byref(k)))
+        return {1: "rows", 2: "wave"}[k.value]
 
     def klt_track(self, prev_img, next_img, pts):
         pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)

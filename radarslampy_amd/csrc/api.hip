@@ -283,6 +283,30 @@ extern "C" int32_t roam_pyr_down_u8(roam_ctx *ctx, const uint8_t *src, int32_t w
     return ROAM_OK;
 }
 
+// internal (tests; not part of include/roam_abi.h): levels 2 and 3 of a pyramid whose level 1 the caller supplies, through
+// launch_build_pyramid's two-level branch.  buf: the whole pyramid storage of `lanes` lanes as the caller laid it out (level 1 of lane b
+// at b * lane_stride + off1, w x h; levels 2 and 3 at off2, off3), `bytes` long; it goes to the device and comes back as a whole, so
+// that the caller sees every byte the kernels wrote.  *kernel: 1 = pyr_down2_rows_kernel, 2 = pyr_down2_wave_kernel.
+extern "C" int32_t roam_pyr_down2_u8(roam_ctx *ctx, uint8_t *buf, int64_t bytes, int32_t w, int32_t h, int32_t lanes,
+                                     int64_t lane_stride, int64_t off1, int64_t off2, int64_t off3, int32_t *kernel)
+{
+    ENTER();
+    ARG_CHECK(ctx, buf && kernel && w >= 2 && h >= 2 && lanes >= 1 && lane_stride > 0 && off1 >= 0 && off2 >= 0 && off3 >= 0);
+    PyrDesc d;
+    pyr_desc_init(&d, 2 * w, 2 * h);                  // level 0 is not there: only its shape is
+    d.off[0] = 0; d.off[1] = off1; d.off[2] = off2; d.off[3] = off3; d.lane_stride = lane_stride;
+    for (int l = 1; l < ROAM_PYR_LEVELS; l++)
+        ARG_CHECK(ctx, (lanes - 1) * lane_stride + d.off[l] + (int64_t)d.w[l] * d.h[l] <= bytes);
+    SCRATCH(dp, uint8_t, S_PYR_A, (size_t)bytes);
+    *kernel = pyr_two_level_kernel(dp, d, 1);
+    ARG_CHECK(ctx, *kernel != 0);
+    H2D(dp, buf, (size_t)bytes);
+    HIP_TRY(ctx, launch_build_pyramid(ctx->stream, dp, d, lanes, nullptr, 1));
+    D2H(buf, dp, (size_t)bytes);
+    SYNC();
+    return ROAM_OK;
+}
+
 static int32_t klt_common(roam_ctx *ctx, uint8_t *pyrA, uint8_t *pyrB, const PyrDesc &d, const float *pts, int K,
                           float *next_pts, uint8_t *status, float *err)
 {

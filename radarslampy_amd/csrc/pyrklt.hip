@@ -6,8 +6,8 @@
 // what is (un)pinned: oracle/c/warp_klt.c.  Integer window sums are exact (int64), every
 // float operation is an explicit round-to-nearest intrinsic => bit-identical to the oracle.
 //
-// pyr_down: the live shapes stream whole rows - pyr_down_rows_kernel (2024 -> 1012) and
-//   pyr_down2_rows_kernel (1012 -> 506 -> 253 in one pass), see the comments at those kernels;
+// pyr_down: the live shapes stream whole rows, one wavefront per band - pyr_down_wave_kernel (2024 -> 1012) and
+//   pyr_down2_wave_kernel (1012 -> 506 -> 253 in one pass), see the comments at those kernels;
 //   other shapes use the tiled kernel: 256-thread block -> 64x16 output tile, the (131 x 35) u8
 //   input tile staged in LDS with REFLECT_101 addressing, filtered horizontally into LDS (u16),
 //   then vertically.
@@ -438,6 +438,161 @@ __global__ __launch_bounds__(256) void pyr_down2_rows_kernel(const uint8_t *__re
     }
 }
 
+// ---- the same two levels without LDS and without barriers (512 ... 1024 wide inputs; the live 1012 -> 506 -> 253): ONE WAVEFRONT per
+// band of PG_CC rows of the SECOND output level, the scheme of pyr_down_wave_kernel applied twice.
+//   level in -> first: a lane owns 4 consecutive pixel dwords (16 pixels, one 16-byte load) of every input row, the neighbours' edge
+//     dwords come through DPP wave shifts, the REFLECT_101 pads are synthesised in the edge lanes; the five latest horizontally filtered
+//     rows sit in a register ring (5 x 4 packed u16 pairs), every second input row gives one first-level row: 8 pixels (2 dwords) per
+//     lane, stored at once (8 bytes per lane) when the band owns the row.
+//   first -> second: those 2 dwords are filtered horizontally again with the same DPP scheme (2 packed pairs per lane) into a second
+//     register ring (5 x 2), every second first-level row gives one row of the second level: one dword (4 pixels) per lane.
+// The band streams first-level rows vb0 = 2 c0 - 2 ... 2 (c0 + nc) (ring index k = vb - vb0) and for those the input rows
+// 2 vb0 - 2 ... (index i; first-level row k is complete at i = 2 k + 4), both in ONE loop unrolled by ten, so that every index of both
+// rings and of the prefetch buffer is static.  The halo rows (3 first-level rows, 9 input rows) are recomputed by the neighbouring
+// band; rows outside the first level are REFLECT_101 copies inside the second ring: row dh is row dh - 2 (k - 2), row dh + 1 is
+// dh - 3 (k - 4), both still in the ring; rows -2 and -1 of the top band are rows 2 and 1, copied when row 2 arrives (k = 4), before
+// the first output row reads them.  What the loop computes for such rows from reflected input rows is discarded.
+// PG_AHEAD input rows are in flight ahead of the one being filtered.
+// Band height: not bounded by registers (the loop streams; rings and prefetch are 20 + 10 + 8 registers whatever the height), it
+// trades halo reads ((4 PG_CC + 9) / (4 PG_CC) input rows per owned row: 1.14 at 16) against waves per scan (16 bands of a 253-row level).
+// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): 68 VGPRs, no scratch, 7 waves per SIMD with PG_AHEAD 2 and PG_WAVES 6.
+// Left to itself the allocator takes 92 VGPRs (5 waves), 132 with five rows in flight (3 waves); asked for 8 waves it spills.
+#define PG_CC 16              // second-level rows per wavefront
+#ifndef PG_AHEAD
+#define PG_AHEAD 2            // input rows in flight (divides the unroll of ten)
+#endif
+#ifndef PG_WAVES
+#define PG_WAVES 6            // waves per SIMD asked of the register allocator
+#endif
+#define PG_MINW 512
+#define PG_MAXW 1024          // 64 lanes x 4 dwords x 4 pixels
+typedef uint32_t u32x2_a2 __attribute__((ext_vector_type(2), aligned(2)));
+typedef uint32_t u32_a2 __attribute__((aligned(2)));
+typedef uint32_t u32_a1 __attribute__((aligned(1)));
+
+__device__ __forceinline__ void pg_load(const uint8_t *__restrict__ s, int w, int h, int wq, int sy, int b0, uint32_t (&r)[4])
+{
+    const uint32_t *rp = reinterpret_cast<const uint32_t *>(s + (int64_t)sy * w) + b0;
+    r[0] = r[1] = r[2] = r[3] = 0u;
+    if (b0 < wq) {
+        if (sy < h - 1) {                                // the (at most 12) bytes read past the row end are the next row's
+            const u32x4_a4 a = *reinterpret_cast<const u32x4_a4 *>(rp);
+            r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) if (b0 + j < wq) r[j] = rp[j];
+        }
+    }
+}
+
+// horizontal 5-tap of N pixel dwords per lane -> N packed output pairs.  jstar: local index of the row's last pixel dword (when it is
+// in this lane), half: that dword holds two pixels only (row length = 2 mod 4)
+template <int N>
+__device__ __forceinline__ void pg_hfilter(const uint32_t (&r)[N], int lane, int jstar, bool half, uint32_t (&out)[N])
+{
+    uint32_t D[N + 2];
+    D[0] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r[N - 1], 0x138, 0xf, 0xf, false);          // lane - 1
+    D[N + 1] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r[0], 0x130, 0xf, 0xf, false);          // lane + 1
+#pragma unroll
+    for (int j = 0; j < N; j++) D[1 + j] = r[j];
+    if (lane == 0) D[0] = (((r[0] >> 16) & 255u) << 16) | (((r[0] >> 8) & 255u) << 24);               // px[-2] = px[2], px[-1] = px[1]
+#pragma unroll
+    for (int j = 0; j < N; j++)
+        if (j == jstar) {
+            if (half) D[1 + j] = (D[1 + j] & 0xffffu) | ((D[1 + j] & 255u) << 16);                    // px[w] = px[w-2] (px[w+1] is not used)
+            else D[2 + j] = ((D[1 + j] >> 16) & 255u) | (((D[1 + j] >> 8) & 255u) << 8);              // px[w] = px[w-2], px[w+1] = px[w-3]
+        }
+#pragma unroll
+    for (int j = 0; j < N; j++) out[j] = pyr_hpair(D[j], D[1 + j], D[2 + j]);
+}
+
+__device__ __forceinline__ uint32_t pg_vsum(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t r4)
+{
+    return (r0 + r4) + 4u * (r1 + r3) + 6u * r2 + 0x00800080u;
+}
+
+__global__ __launch_bounds__(256, PG_WAVES) void pyr_down2_wave_kernel(const uint8_t *__restrict__ src, int64_t src_lane_stride,
+                                                             int w, int h, uint8_t *__restrict__ dst,
+                                                             int64_t dst_lane_stride, int dw, int dh,
+                                                             uint8_t *__restrict__ dst2, int64_t dst2_lane_stride,
+                                                             int dw2, int dh2, int bands)
+{
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int band = blockIdx.x * 4 + wv;
+    if (band >= bands) return;
+    const int b = blockIdx.y;
+    const int c0 = band * PG_CC;
+    const int nc = min(PG_CC, dh2 - c0);
+    const int vb0 = 2 * c0 - 2;                           // first-level row of ring index k = 0 (virtual: -2 in the top band)
+    const int nb = 2 * nc + 3;                            // first-level rows streamed
+    const int nin = 2 * nb + 3;                           // input rows streamed
+    const int ay0 = 2 * vb0 - 2;                          // input row of index i = 0 (virtual)
+    const int own0 = 2 * c0, own1 = min(2 * (c0 + nc), dh);   // first-level rows written by this band
+    const uint8_t *s = src + (int64_t)b * src_lane_stride;
+    uint8_t *d = dst + (int64_t)b * dst_lane_stride;
+    uint8_t *d2 = dst2 + (int64_t)b * dst2_lane_stride;
+    const int wq = w >> 2;
+    const int b0 = lane * 4;
+    const int jstar = wq - 1 - b0;                        // last pixel dword of an input row, local index
+    const int jstar2 = ((dw - 1) >> 2) - 2 * lane;        // last pixel dword of a first-level row, local index
+    const bool half2 = (dw & 2) != 0;                     // dw = 2 mod 4: that dword holds the row's last two pixels only
+    const int n1 = dw - 8 * lane, n2 = dw2 - 4 * lane;    // pixels of this lane's segment inside the first / second level row
+    uint32_t R[5][4], Q[5][2], pre[PG_AHEAD][4];
+#pragma unroll
+    for (int k = 0; k < PG_AHEAD; k++) pg_load(s, w, h, wq, reflect101(ay0 + k, h), b0, pre[k]);      // nin >= 13 > PG_AHEAD
+
+    // ring slots: input row i in R[i % 5] = R[K % 5]; first-level row k = (i - 4) / 2 = 5 (i0 / 10) + (K - 4) / 2 in Q[k % 5] = Q[PG_S(K)]
+#define PG_S(K) ((((K) + 6) / 2) % 5)
+#define PG_STEP(K)                                                                                              \
+    if (i0 + (K) < nin) {                                                                                       \
+        const int i = i0 + (K);                                                                                 \
+        pg_hfilter<4>(pre[(K) % PG_AHEAD], lane, jstar, false, R[(K) % 5]);                                     \
+        if (i + PG_AHEAD < nin) pg_load(s, w, h, wq, reflect101(ay0 + i + PG_AHEAD, h), b0, pre[(K) % PG_AHEAD]); \
+        if (i >= 4 && !((K) & 1)) {                                                                             \
+            const int k = (i - 4) >> 1, vb = vb0 + k;                                                           \
+            constexpr int S = PG_S(K);                                                                          \
+            uint32_t sv[4], B[2];                                                                               \
+            _Pragma("unroll") for (int m = 0; m < 4; m++)                                                       \
+                sv[m] = pg_vsum(R[((K) + 1) % 5][m], R[((K) + 2) % 5][m], R[((K) + 3) % 5][m], R[((K) + 4) % 5][m], R[(K) % 5][m]); \
+            B[0] = __builtin_amdgcn_perm(sv[1], sv[0], 0x07050301u);                                            \
+            B[1] = __builtin_amdgcn_perm(sv[3], sv[2], 0x07050301u);                                            \
+            if (vb >= own0 && vb < own1) {                                                                      \
+                uint8_t *orow = d + (int64_t)vb * dw + 8 * lane;                                                \
+                if (n1 >= 8) *reinterpret_cast<u32x2_a2 *>(orow) = u32x2_a2{B[0], B[1]};                        \
+                else if (n1 >= 4) {                                                                             \
+                    *reinterpret_cast<u32_a2 *>(orow) = B[0];                                                   \
+                    if (n1 >= 6) *reinterpret_cast<uint16_t *>(orow + 4) = (uint16_t)B[1];                      \
+                } else if (n1 >= 2) *reinterpret_cast<uint16_t *>(orow) = (uint16_t)B[0];                       \
+            }                                                                                                   \
+            pg_hfilter<2>(B, lane, jstar2, half2, Q[S]);                                                        \
+            if (vb == dh) { Q[S][0] = Q[(S + 3) % 5][0]; Q[S][1] = Q[(S + 3) % 5][1]; }                         \
+            else if (vb > dh) { Q[S][0] = Q[(S + 1) % 5][0]; Q[S][1] = Q[(S + 1) % 5][1]; }                     \
+            if (vb == 2 && k == 4) {                                                                            \
+                Q[(S + 1) % 5][0] = Q[S][0]; Q[(S + 1) % 5][1] = Q[S][1];                                       \
+                Q[(S + 2) % 5][0] = Q[(S + 4) % 5][0]; Q[(S + 2) % 5][1] = Q[(S + 4) % 5][1];                   \
+            }                                                                                                   \
+            if (k >= 4 && !(k & 1)) {                                                                           \
+                const uint32_t s0 = pg_vsum(Q[(S + 1) % 5][0], Q[(S + 2) % 5][0], Q[(S + 3) % 5][0], Q[(S + 4) % 5][0], Q[S][0]); \
+                const uint32_t s1 = pg_vsum(Q[(S + 1) % 5][1], Q[(S + 2) % 5][1], Q[(S + 3) % 5][1], Q[(S + 4) % 5][1], Q[S][1]); \
+                const uint32_t o = __builtin_amdgcn_perm(s1, s0, 0x07050301u);                                  \
+                uint8_t *orow = d2 + (int64_t)(c0 + ((k - 4) >> 1)) * dw2 + 4 * lane;                           \
+                if (n2 >= 4) *reinterpret_cast<u32_a1 *>(orow) = o;                                             \
+                else {                                                                                          \
+                    if (n2 >= 1) orow[0] = (uint8_t)o;                                                          \
+                    if (n2 >= 2) orow[1] = (uint8_t)(o >> 8);                                                   \
+                    if (n2 >= 3) orow[2] = (uint8_t)(o >> 16);                                                  \
+                }                                                                                               \
+            }                                                                                                   \
+        }                                                                                                       \
+    }
+    for (int i0 = 0; i0 < nin; i0 += 10) {
+        PG_STEP(0) PG_STEP(1) PG_STEP(2) PG_STEP(3) PG_STEP(4) PG_STEP(5) PG_STEP(6) PG_STEP(7) PG_STEP(8) PG_STEP(9)
+    }
+#undef PG_STEP
+#undef PG_S
+}
+
 hipError_t launch_pyr_down(hipStream_t st, const uint8_t *src, int64_t src_lane_stride, int w, int h,
                            uint8_t *dst, int64_t dst_lane_stride, int B, const unsigned long long *dark)
 {
@@ -474,17 +629,34 @@ void pyr_desc_init(PyrDesc *d, int w, int h)
     d->lane_stride = off;
 }
 
-hipError_t launch_build_pyramid(hipStream_t st, uint8_t *pyr, const PyrDesc &d, int B, const unsigned long long *dark_l0)
+// which kernel launch_build_pyramid uses for levels l + 1 and l + 2: 0 = one level at a time, 1 = pyr_down2_rows_kernel,
+// 2 = pyr_down2_wave_kernel (for the tests that must know which of them they have compared)
+int pyr_two_level_kernel(const uint8_t *pyr, const PyrDesc &d, int l)
 {
-    for (int l = 0; l + 1 < ROAM_PYR_LEVELS; l++) {
+    const int w = d.w[l], h = d.h[l];
+    if (!(l + 2 < ROAM_PYR_LEVELS && (w & 3) == 0 && w >= 64 && w <= PF_MAXW && (d.w[l + 1] & 1) == 0 && h >= 16 && d.h[l + 1] >= 8 &&
+          (d.lane_stride & 3) == 0 && (d.off[l] & 3) == 0 && (d.off[l + 1] & 1) == 0 && (reinterpret_cast<uintptr_t>(pyr) & 3) == 0))
+        return 0;
+    return (w >= PG_MINW && w <= PG_MAXW) ? 2 : 1;
+}
+
+hipError_t launch_build_pyramid(hipStream_t st, uint8_t *pyr, const PyrDesc &d, int B, const unsigned long long *dark_l0, int first_level)
+{
+    for (int l = first_level; l + 1 < ROAM_PYR_LEVELS; l++) {
         const int w = d.w[l], h = d.h[l], dw = d.w[l + 1], dh = d.h[l + 1];
         // the last two levels in one pass when the shapes allow it (1012 -> 506 -> 253)
         if (l + 2 < ROAM_PYR_LEVELS && (w & 3) == 0 && w >= 64 && w <= PF_MAXW && (dw & 1) == 0 && h >= 16 && dh >= 8 &&
             (d.lane_stride & 3) == 0 && (d.off[l] & 3) == 0 && (d.off[l + 1] & 1) == 0 && (reinterpret_cast<uintptr_t>(pyr) & 3) == 0) {
             const int dw2 = d.w[l + 2], dh2 = d.h[l + 2];
-            dim3 grid((dh2 + PF_CC - 1) / PF_CC, B);
-            hipLaunchKernelGGL(pyr_down2_rows_kernel, grid, dim3(256), 0, st, pyr + d.off[l], d.lane_stride, w, h,
-                               pyr + d.off[l + 1], d.lane_stride, dw, dh, pyr + d.off[l + 2], d.lane_stride, dw2, dh2);
+            if (w >= PG_MINW && w <= PG_MAXW) {           // a row fits one wavefront at 4 dwords per lane, and fills half of it
+                const int bands = (dh2 + PG_CC - 1) / PG_CC;
+                hipLaunchKernelGGL(pyr_down2_wave_kernel, dim3((bands + 3) / 4, B), dim3(256), 0, st, pyr + d.off[l], d.lane_stride, w, h,
+                                   pyr + d.off[l + 1], d.lane_stride, dw, dh, pyr + d.off[l + 2], d.lane_stride, dw2, dh2, bands);
+            } else {
+                dim3 grid((dh2 + PF_CC - 1) / PF_CC, B);
+                hipLaunchKernelGGL(pyr_down2_rows_kernel, grid, dim3(256), 0, st, pyr + d.off[l], d.lane_stride, w, h,
+                                   pyr + d.off[l + 1], d.lane_stride, dw, dh, pyr + d.off[l + 2], d.lane_stride, dw2, dh2);
+            }
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return e;
             l++;

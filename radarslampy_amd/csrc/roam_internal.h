@@ -124,7 +124,10 @@ hipError_t launch_pyr_down(hipStream_t st, const uint8_t *src, int64_t src_lane_
                            uint8_t *dst, int64_t dst_lane_stride, int B, const unsigned long long *dark = nullptr);
 // dark_l0 (optional, launch_pyr_dark): the lanes of the 2024 -> 1012 kernel whose pixels lie beyond the maximum range neither load nor
 // store - for pyramids that were zero-filled once and whose level 0 comes from launch_warp_gather(..., dark_stays_zero)
-hipError_t launch_build_pyramid(hipStream_t st, uint8_t *pyr, const PyrDesc &d, int B, const unsigned long long *dark_l0 = nullptr);
+// first_level: the level taken as given (levels first_level + 1 ... are built from it)
+hipError_t launch_build_pyramid(hipStream_t st, uint8_t *pyr, const PyrDesc &d, int B, const unsigned long long *dark_l0 = nullptr,
+                                int first_level = 0);
+int pyr_two_level_kernel(const uint8_t *pyr, const PyrDesc &d, int l);
 size_t pyr_dark_words(int h);
 hipError_t launch_pyr_dark(hipStream_t st, const uint32_t *map, int w, int h, int cols, unsigned long long *dark);
 
