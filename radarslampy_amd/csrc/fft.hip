@@ -16,7 +16,7 @@
 // kernels of fmt_batch.hip fill: its driver roam_fmt_batch_run is here because the row pass and the transpose are local to this unit.
 // The registration (roam_fmt_register_batch_f32, roam_engine_fmt_register) adds a second correlation, on the Cartesian images that the
 // kernels of fmt_register.hip make and turn by the angle of the first: roam_fmt_register_run.
-#include "roam_internal.h"
+#include "cvmap.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void pc_window_kernel(const float *__restrict_
     double val = 0.0;
     if (x < cols && y < rows) {
         const float v = img[((int64_t)b * rows + y) * cols + x];
-        val = wr ? (double)__fmul_rn(rn_sqrtf((float)(wr[y] * wc[x])), v) : (double)v;
+        val = (double)(wr ? cv_hanning_product(wr[y], wc[x], v) : v);
     }
     out[((int64_t)b * M + y) * N + x] = val;
 }
@@ -342,6 +342,74 @@ static bool fft_smooth(int n)
     return fft_plan(n, &p);
 }
 
+// cv2.createHanningWindow's float64 factor per row or column of a side of n
+void roam_hanning_factors(int n, double *w)
+{
+    for (int i = 0; i < n; i++) w[i] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(n - 1) * (double)i));
+}
+
+// the 7 nb planes of a chunk of nb correlations, pl = nb M N doubles each: windowed image | work re, im | F1 re, im | F2 re, im
+struct PcPlanes {
+    double *a, *tr, *ti, *F[2][2];
+};
+static PcPlanes pc_planes(double *base, size_t pl)
+{
+    return {base, base + pl, base + 2 * pl, {{base + 3 * pl, base + 4 * pl}, {base + 5 * pl, base + 6 * pl}}};
+}
+
+// the grid of pc_peak_partial_kernel: indices per block, blocks per plane (at most 1024)
+struct PcPeakGrid {
+    int per, nblk;
+};
+static PcPeakGrid pc_peak_grid(size_t nmn)
+{
+    const int per = (int)((nmn + 1023) / 1024) < 1024 ? 1024 : (int)((nmn + 1023) / 1024);
+    return {per, (int)((nmn + per - 1) / per)};
+}
+
+// pairs per chunk: 2000 MiB of scratch at bytes_per_pair, at least one, at most n and cap (the grid's z extent).  env: the tests' smaller
+// chunk from ROAM_FMT_BATCH_CHUNK (read per call)
+static size_t pc_chunk(size_t bytes_per_pair, size_t n, size_t cap, bool env)
+{
+    size_t chunk = ((size_t)2000 << 20) / bytes_per_pair;
+    if (chunk < 1) chunk = 1;
+    if (chunk > n) chunk = n;
+    if (chunk > cap) chunk = cap;
+    if (const char *ce = env ? getenv("ROAM_FMT_BATCH_CHUNK") : nullptr) {
+        const long c = atol(ce);
+        if (c >= 1 && (size_t)c < chunk) chunk = (size_t)c;
+    }
+    return chunk;
+}
+
+// The correlation of nb pairs, 12 launches on ctx->stream: win[0] / win[1] hold the nb windowed, zero-padded M x N sources / targets
+// (planes of `base`: a, and F2 re - which nothing touches before its own row pass has consumed it).  Per image set a row pass, a
+// transpose and a row pass (the spectrum stays transposed, N x M); the cross-power spectrum; the three inverse passes; the peak search
+// -> d_out[3 b] = {dx, dy, response}.  d_pv, d_pi: nb x pc_peak_grid(M N).nblk partial maxima
+static int32_t pc_correlate(roam_ctx *ctx, int nb, int M, int N, double *base, const double *win0, const double *win1, double *d_pv,
+                            int *d_pi, double *d_out)
+{
+    const size_t pl = (size_t)M * N * nb;
+    const PcPlanes p = pc_planes(base, pl);
+    const PcPeakGrid g = pc_peak_grid((size_t)M * N);
+    double *const a = p.a, *const tr = p.tr, *const ti = p.ti;
+    const double *win[2] = {win0, win1};
+    hipStream_t st = ctx->stream;
+    for (int k = 0; k < 2; k++) {
+        FFT_TRY(fft_rows(ctx, win[k], nullptr, tr, ti, (int64_t)nb * M, N, false));
+        FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, p.F[k][0], p.F[k][1]));
+        FFT_TRY(fft_rows(ctx, p.F[k][0], p.F[k][1], p.F[k][0], p.F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
+    }
+    HIP_TRY(ctx, launch_fmt_cross_power(st, p.F[0][0], p.F[0][1], p.F[1][0], p.F[1][1], (int)pl, tr, ti));
+    FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
+    FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, p.F[0][0], p.F[0][1]));
+    FFT_TRY(fft_rows(ctx, p.F[0][0], p.F[0][1], a, nullptr, (int64_t)nb * M, N, true));                      // real part only
+    hipLaunchKernelGGL(pc_peak_partial_kernel, dim3(g.nblk, nb), dim3(256), 0, st, a, M, N, g.per, d_pv, d_pi);
+    hipLaunchKernelGGL(pc_peak_final_kernel, dim3(nb), dim3(256), 0, st, a, M, N, g.nblk, d_pv, d_pi, d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return ROAM_OK;
+}
+
 extern "C" int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t batch, int32_t rows, int32_t cols,
                                             int64_t row_stride, int64_t image_stride, int32_t hanning, double *out_dxdy, double *out_response)
 {
@@ -352,14 +420,9 @@ extern "C" int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, con
     ARG_CHECK(ctx, row_stride >= cols && (batch == 1 || image_stride >= (int64_t)(rows - 1) * row_stride + cols));
     const int M = optimal_dft_size(rows), N = optimal_dft_size(cols);
     const size_t nmn = (size_t)M * N, nimg = (size_t)rows * cols;
-    // per pair: 7 float64 planes (windowed image | work re, im | F1 re, im | F2 re, im) and the two float32 images
-    const size_t per_pair = 7 * sizeof(double) * nmn + 2 * sizeof(float) * nimg;
-    size_t chunk = ((size_t)2000 << 20) / per_pair;
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)batch) chunk = batch;
-    if (chunk > 32768) chunk = 32768;
-    const int per = (int)((nmn + 1023) / 1024) < 1024 ? 1024 : (int)((nmn + 1023) / 1024);     // indices per stage-1 block: at most 1024 blocks
-    const int nblk = (int)((nmn + per - 1) / per);
+    // per pair: the 7 float64 planes and the two float32 images
+    const size_t chunk = pc_chunk(7 * sizeof(double) * nmn + 2 * sizeof(float) * nimg, batch, 32768, false);
+    const int nblk = pc_peak_grid(nmn).nblk;
     hipStream_t st = ctx->stream;
     float *d_src = (float *)roam_scratch(ctx, S_IN0, sizeof(float) * nimg * chunk);
     float *d_tgt = (float *)roam_scratch(ctx, S_IN1, sizeof(float) * nimg * chunk);
@@ -371,39 +434,23 @@ extern "C" int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, con
     if (!d_src || !d_tgt || !d_f || !d_win || !d_pv || !d_pi || !d_out) return ROAM_E_HIP;
     std::vector<double> win((size_t)rows + cols), o(3 * chunk);
     if (hanning) {
-        for (int y = 0; y < rows; y++) win[y] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(rows - 1) * (double)y));
-        for (int x = 0; x < cols; x++) win[rows + x] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(cols - 1) * (double)x));
+        roam_hanning_factors(rows, win.data());
+        roam_hanning_factors(cols, win.data() + rows);
         HIP_TRY(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(double) * win.size(), hipMemcpyHostToDevice, st));
     }
     for (size_t b0 = 0; b0 < (size_t)batch; b0 += chunk) {
         const int nb = (int)(((size_t)batch - b0) < chunk ? ((size_t)batch - b0) : chunk);
-        const size_t pl = nmn * nb;                          // one plane of the chunk
-        double *a = d_f, *tr = d_f + pl, *ti = d_f + 2 * pl, *F[2][2] = {{d_f + 3 * pl, d_f + 4 * pl}, {d_f + 5 * pl, d_f + 6 * pl}};
+        const PcPlanes p = pc_planes(d_f, nmn * nb);
+        double *wpl[2] = {p.a, p.F[1][0]};                   // the windowed images: sources, targets
         const float *host[2] = {src, tgt};
         float *dev[2] = {d_src, d_tgt};
         for (int k = 0; k < 2; k++) {
-            for (int i = 0; i < nb; i++) {
-                const float *h = host[k] + (int64_t)(b0 + i) * image_stride;
-                if (row_stride == cols)                      // a 2-D copy moves the rows one by one
-                    HIP_TRY(ctx, hipMemcpyAsync(dev[k] + (size_t)i * nimg, h, sizeof(float) * nimg, hipMemcpyHostToDevice, st));
-                else
-                    HIP_TRY(ctx, hipMemcpy2DAsync(dev[k] + (size_t)i * nimg, sizeof(float) * cols, h, sizeof(float) * row_stride,
-                                                  sizeof(float) * cols, rows, hipMemcpyHostToDevice, st));
-            }
+            HIP_TRY(ctx, roam_upload_packed_f32(st, dev[k], host[k] + (int64_t)b0 * image_stride, nb, cols, rows, row_stride, image_stride));
             hipLaunchKernelGGL(pc_window_kernel, dim3((N + 255) / 256, M, nb), dim3(256), 0, st, dev[k], rows, cols,
-                               hanning ? d_win : (const double *)nullptr, d_win + rows, M, N, a);
+                               hanning ? d_win : (const double *)nullptr, d_win + rows, M, N, wpl[k]);
             HIP_TRY(ctx, hipGetLastError());
-            FFT_TRY(fft_rows(ctx, a, nullptr, tr, ti, (int64_t)nb * M, N, false));
-            FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, F[k][0], F[k][1]));
-            FFT_TRY(fft_rows(ctx, F[k][0], F[k][1], F[k][0], F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
         }
-        HIP_TRY(ctx, launch_fmt_cross_power(st, F[0][0], F[0][1], F[1][0], F[1][1], (int)pl, tr, ti));
-        FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
-        FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, F[0][0], F[0][1]));
-        FFT_TRY(fft_rows(ctx, F[0][0], F[0][1], a, nullptr, (int64_t)nb * M, N, true));                  // real part only
-        hipLaunchKernelGGL(pc_peak_partial_kernel, dim3(nblk, nb), dim3(256), 0, st, a, M, N, per, d_pv, d_pi);
-        hipLaunchKernelGGL(pc_peak_final_kernel, dim3(nb), dim3(256), 0, st, a, M, N, nblk, d_pv, d_pi, d_out);
-        HIP_TRY(ctx, hipGetLastError());
+        FFT_TRY(pc_correlate(ctx, nb, M, N, d_f, wpl[0], wpl[1], d_pv, d_pi, d_out));
         HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
         for (int i = 0; i < nb; i++) {
@@ -429,16 +476,8 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
     const bool whole_rows = host && in.row_stride == in.cols;
     const size_t in_w = whole_rows ? (size_t)in.cols : (size_t)clip, nin = host ? (size_t)rows * in_w : 0;
     const size_t per_pair = 7 * sizeof(double) * nmn + 2 * sizeof(float) * (nsmall + ncart + (logpolar_out ? nlp : 0) + nin) + 2 * sizeof(int32_t);
-    size_t chunk = ((size_t)2000 << 20) / per_pair;
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)n) chunk = n;
-    if (chunk > 32767) chunk = 32767;                        // 2 chunk images in grid.z
-    if (const char *ce = getenv("ROAM_FMT_BATCH_CHUNK")) {   // tests: a small chunk (read per call)
-        const long c = atol(ce);
-        if (c >= 1 && (size_t)c < chunk) chunk = (size_t)c;
-    }
-    const int per = (int)((nmn + 1023) / 1024) < 1024 ? 1024 : (int)((nmn + 1023) / 1024);
-    const int nblk = (int)((nmn + per - 1) / per);
+    const size_t chunk = pc_chunk(per_pair, n, 32767, true);                 // 2 chunk images in grid.z
+    const int nblk = pc_peak_grid(nmn).nblk;
     hipStream_t st = ctx->stream;
     float *d_in = host ? (float *)roam_scratch(ctx, S_IN0, sizeof(float) * nin * 2 * chunk) : nullptr;
     int32_t *d_idx = host ? nullptr : (int32_t *)roam_scratch(ctx, S_IN1, sizeof(int32_t) * 2 * chunk);
@@ -457,17 +496,9 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
     std::vector<unsigned char> tab(tab_bytes);
     {
         double *cs = (double *)tab.data(), *wr = cs + 2 * dh, *wc = wr + dh;
-        float *br = (float *)(wc + dw);
-        const double Kangle = 6.283185307179586476925286766559 / dh, Kmag = log((double)W / 2.0) / dw;
-        for (int phi = 0; phi < dh; phi++) {
-            const double KKy = Kangle * phi;
-            cs[2 * phi] = cos(KKy); cs[2 * phi + 1] = sin(KKy);
-            wr[phi] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(dh - 1) * (double)phi));
-        }
-        for (int rho = 0; rho < dw; rho++) {
-            br[rho] = (float)(exp(rho * Kmag) - 1.0);
-            wc[rho] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(dw - 1) * (double)rho));
-        }
+        roam_warp_polar_tables(dw, dh, (double)W / 2.0, true, (float *)(wc + dw), cs);
+        roam_hanning_factors(dh, wr);
+        roam_hanning_factors(dw, wc);
     }
     HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
     const double *d_tabd = (const double *)d_tab;
@@ -477,27 +508,13 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
     const double log_base = exp(log((double)dh / 2.0) / (double)sz);
     for (size_t b0 = 0; b0 < (size_t)n; b0 += chunk) {
         const int nb = (int)(((size_t)n - b0) < chunk ? ((size_t)n - b0) : chunk);
-        const size_t pl = nmn * nb;
-        double *a = d_f, *tr = d_f + pl, *ti = d_f + 2 * pl, *F[2][2] = {{d_f + 3 * pl, d_f + 4 * pl}, {d_f + 5 * pl, d_f + 6 * pl}};
-        double *win[2] = {a, F[1][0]};                       // the windowed images: sources, targets
+        const PcPlanes p = pc_planes(d_f, nmn * nb);
         FmtBatchSrc src;
         if (host) {
             const float *h[2] = {in.host_src, in.host_tgt};
-            for (int k = 0; k < 2; k++) {
-                float *d = d_in + (size_t)k * nb * nin;
-                const float *h0 = h[k] + (int64_t)b0 * in.image_stride;
-                if (whole_rows && (nb == 1 || in.image_stride == (int64_t)nin))
-                    HIP_TRY(ctx, hipMemcpyAsync(d, h0, sizeof(float) * nin * nb, hipMemcpyHostToDevice, st));
-                else
-                    for (int i = 0; i < nb; i++) {
-                        if (whole_rows)
-                            HIP_TRY(ctx, hipMemcpyAsync(d + (size_t)i * nin, h0 + (int64_t)i * in.image_stride, sizeof(float) * nin,
-                                                        hipMemcpyHostToDevice, st));
-                        else
-                            HIP_TRY(ctx, hipMemcpy2DAsync(d + (size_t)i * nin, sizeof(float) * in_w, h0 + (int64_t)i * in.image_stride,
-                                                          sizeof(float) * in.row_stride, sizeof(float) * in_w, rows, hipMemcpyHostToDevice, st));
-                    }
-            }
+            for (int k = 0; k < 2; k++)
+                HIP_TRY(ctx, roam_upload_packed_f32(st, d_in + (size_t)k * nb * nin, h[k] + (int64_t)b0 * in.image_stride, nb, (int)in_w, rows,
+                                                    in.row_stride, in.image_stride));
             src = {d_in, (int64_t)nin, (int64_t)in_w, 0, 0, nullptr};
         } else {
             HIP_TRY(ctx, hipMemcpyAsync(d_idx, in.prev_idx + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
@@ -505,18 +522,7 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
             src = {in.pool, in.rec_bytes, in.rec_stride, in.payload_off, in.pool_f32 ? 0 : 1, d_idx};
         }
         HIP_TRY(ctx, launch_fmt_batch_front(st, src, nb, rows, clip, R, dw, dh, M, N, d_tabd, d_br, d_small, d_cart, d_f, (int64_t)4 * nb, d_lp));
-        for (int k = 0; k < 2; k++) {
-            FFT_TRY(fft_rows(ctx, win[k], nullptr, tr, ti, (int64_t)nb * M, N, false));
-            FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, F[k][0], F[k][1]));
-            FFT_TRY(fft_rows(ctx, F[k][0], F[k][1], F[k][0], F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
-        }
-        HIP_TRY(ctx, launch_fmt_cross_power(st, F[0][0], F[0][1], F[1][0], F[1][1], (int)pl, tr, ti));
-        FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
-        FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, F[0][0], F[0][1]));
-        FFT_TRY(fft_rows(ctx, F[0][0], F[0][1], a, nullptr, (int64_t)nb * M, N, true));                  // real part only
-        hipLaunchKernelGGL(pc_peak_partial_kernel, dim3(nblk, nb), dim3(256), 0, st, a, M, N, per, d_pv, d_pi);
-        hipLaunchKernelGGL(pc_peak_final_kernel, dim3(nb), dim3(256), 0, st, a, M, N, nblk, d_pv, d_pi, d_out);
-        HIP_TRY(ctx, hipGetLastError());
+        FFT_TRY(pc_correlate(ctx, nb, M, N, d_f, p.a, p.F[1][0], d_pv, d_pi, d_out));       // the windowed images: sources, targets
         HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
         if (logpolar_out) {
             HIP_TRY(ctx, hipMemcpyAsync(logpolar_out + b0 * nlp, d_lp, sizeof(float) * nlp * nb, hipMemcpyDeviceToHost, st));
@@ -525,10 +531,7 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
         }
         HIP_TRY(ctx, hipStreamSynchronize(st));
         for (int i = 0; i < nb; i++) {                       // the final arithmetic of roam_fmt_rotation
-            double ang = -o[3 * i + 1] * 2.0 * M_PI / (double)sz;
-            ang = fmod(ang + M_PI, 2.0 * M_PI);              // utils.normalize_angles: (th + pi) % (2 pi) - pi (Python modulo)
-            if (ang < 0) ang += 2.0 * M_PI;
-            out3[3 * (b0 + i)] = ang - M_PI;
+            out3[3 * (b0 + i)] = roam_normalize_angle(-o[3 * i + 1] * 2.0 * M_PI / (double)sz);
             out3[3 * (b0 + i) + 1] = pow(log_base, o[3 * i]);
             out3[3 * (b0 + i) + 2] = o[3 * i + 2];
         }
@@ -576,16 +579,8 @@ int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int ro
                            + 2 * sizeof(float) * ((size_t)rows * R + (size_t)Wr * Wr) + 2 * sizeof(int32_t);
     const size_t per_reg = 7 * sizeof(double) * nmn + sizeof(float) * (2 * ncart + (cart_out ? ncart : 0) + 2 * nin) + 6 * sizeof(double)
                            + 2 * sizeof(int32_t);
-    size_t chunk = ((size_t)2000 << 20) / (per_rot + per_reg);
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)n) chunk = n;
-    if (chunk > 32767) chunk = 32767;                        // 2 chunk images in grid.z
-    if (const char *ce = getenv("ROAM_FMT_BATCH_CHUNK")) {   // tests: a small chunk (read per call)
-        const long c = atol(ce);
-        if (c >= 1 && (size_t)c < chunk) chunk = (size_t)c;
-    }
-    const int per = (int)((nmn + 1023) / 1024) < 1024 ? 1024 : (int)((nmn + 1023) / 1024);
-    const int nblk = (int)((nmn + per - 1) / per);
+    const size_t chunk = pc_chunk(per_rot + per_reg, n, 32767, true);        // 2 chunk images in grid.z
+    const int nblk = pc_peak_grid(nmn).nblk;
     hipStream_t st = ctx->stream;
     float *d_img = host ? (float *)roam_scratch(ctx, S_IN2, sizeof(float) * nin * 2 * chunk) : nullptr;
     int32_t *d_idx = host ? nullptr : (int32_t *)roam_scratch(ctx, S_IN3, sizeof(int32_t) * 2 * chunk);
@@ -594,7 +589,8 @@ int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int ro
     double *d_M = (double *)roam_scratch(ctx, S_OUT2, sizeof(double) * 6 * chunk);
     if ((host && !d_img) || (!host && !d_idx) || !d_cart || (cart_out && !d_rot) || !d_M) return ROAM_E_HIP;
     std::vector<double> win(2 * (size_t)S), o3(3 * chunk), o(3 * chunk), Mh(6 * chunk);
-    for (int k = 0; k < S; k++) win[k] = win[S + k] = 0.5 * (1.0 - cos(2.0 * M_PI / (double)(S - 1) * (double)k));
+    roam_hanning_factors(S, win.data());
+    roam_hanning_factors(S, win.data() + S);
     std::vector<int32_t> iota;
     if (host) {
         iota.resize(2 * chunk);
@@ -606,16 +602,9 @@ int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int ro
         FmtBatchSrc src;
         if (host) {
             const float *h[2] = {in.host_src, in.host_tgt};
-            for (int k = 0; k < 2; k++) {
-                float *d = d_img + (size_t)k * nb * nin;
-                const float *h0 = h[k] + (int64_t)b0 * in.image_stride;
-                if (in.row_stride == in.cols && (nb == 1 || in.image_stride == (int64_t)nin))
-                    HIP_TRY(ctx, hipMemcpyAsync(d, h0, sizeof(float) * nin * nb, hipMemcpyHostToDevice, st));
-                else
-                    for (int i = 0; i < nb; i++)
-                        HIP_TRY(ctx, hipMemcpy2DAsync(d + (size_t)i * nin, sizeof(float) * in.cols, h0 + (int64_t)i * in.image_stride,
-                                                      sizeof(float) * in.row_stride, sizeof(float) * in.cols, rows, hipMemcpyHostToDevice, st));
-            }
+            for (int k = 0; k < 2; k++)
+                HIP_TRY(ctx, roam_upload_packed_f32(st, d_img + (size_t)k * nb * nin, h[k] + (int64_t)b0 * in.image_stride, nb, in.cols, rows,
+                                                    in.row_stride, in.image_stride));
             rin = FmtBatchIn();
             rin.pool = (const uint8_t *)d_img; rin.rec_bytes = (int64_t)nin; rin.rec_stride = in.cols; rin.pool_f32 = 1;
             rin.prev_idx = iota.data(); rin.curr_idx = iota.data() + nb;
@@ -635,25 +624,12 @@ int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int ro
         int *d_pi = (int *)roam_scratch(ctx, S_TMP3, sizeof(int) * (size_t)nblk * chunk);
         double *d_out = (double *)roam_scratch(ctx, S_OUT0, sizeof(double) * 3 * chunk);
         if (!d_f || !d_win || !d_pv || !d_pi || !d_out) return ROAM_E_HIP;
-        const size_t pl = nmn * nb;
-        double *a = d_f, *tr = d_f + pl, *ti = d_f + 2 * pl, *F[2][2] = {{d_f + 3 * pl, d_f + 4 * pl}, {d_f + 5 * pl, d_f + 6 * pl}};
-        double *wpl[2] = {a, F[1][0]};                       // the windowed images: turned sources, targets
+        const PcPlanes p = pc_planes(d_f, nmn * nb);
         HIP_TRY(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(double) * win.size(), hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(d_M, Mh.data(), sizeof(double) * 6 * nb, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, launch_fmtr_cart(st, src, 2 * nb, rows, in.cols, Rc, d_cart));
         HIP_TRY(ctx, launch_fmtr_rotate_window(st, d_cart, S, M, N, nb, (int64_t)4 * nb, d_M, d_win, d_f, d_rot));
-        for (int k = 0; k < 2; k++) {
-            FFT_TRY(fft_rows(ctx, wpl[k], nullptr, tr, ti, (int64_t)nb * M, N, false));
-            FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, F[k][0], F[k][1]));
-            FFT_TRY(fft_rows(ctx, F[k][0], F[k][1], F[k][0], F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
-        }
-        HIP_TRY(ctx, launch_fmt_cross_power(st, F[0][0], F[0][1], F[1][0], F[1][1], (int)pl, tr, ti));
-        FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
-        FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, F[0][0], F[0][1]));
-        FFT_TRY(fft_rows(ctx, F[0][0], F[0][1], a, nullptr, (int64_t)nb * M, N, true));                  // real part only
-        hipLaunchKernelGGL(pc_peak_partial_kernel, dim3(nblk, nb), dim3(256), 0, st, a, M, N, per, d_pv, d_pi);
-        hipLaunchKernelGGL(pc_peak_final_kernel, dim3(nb), dim3(256), 0, st, a, M, N, nblk, d_pv, d_pi, d_out);
-        HIP_TRY(ctx, hipGetLastError());
+        FFT_TRY(pc_correlate(ctx, nb, M, N, d_f, p.a, p.F[1][0], d_pv, d_pi, d_out));           // the windowed images: turned sources, targets
         HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
         if (cart_out) {
             HIP_TRY(ctx, hipMemcpyAsync(cart_out + b0 * ncart, d_rot, sizeof(float) * ncart * nb, hipMemcpyDeviceToHost, st));
@@ -729,7 +705,7 @@ extern "C" int32_t roam_time_fft2(roam_ctx *ctx, int32_t rows, int32_t cols, int
     if (!d) return ROAM_E_HIP;
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipMemsetAsync(d, 0, sizeof(double) * nmn * 7, st));
-    double *a = d, *tr = d + nmn, *ti = d + 2 * nmn, *F[2][2] = {{d + 3 * nmn, d + 4 * nmn}, {d + 5 * nmn, d + 6 * nmn}};
+    const PcPlanes p = pc_planes(d, nmn);
     hipEvent_t e0, e1;
     HIP_TRY(ctx, hipEventCreate(&e0));
     if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); ROAM_SET_ERR(ctx, "hipEventCreate failed"); return ROAM_E_HIP; }
@@ -738,22 +714,22 @@ extern "C" int32_t roam_time_fft2(roam_ctx *ctx, int32_t rows, int32_t cols, int
         if (rep == 0) (void)hipEventRecord(e0, st);
         if (what == ROAM_TIME_FFT_FIVE) {
             for (int k = 0; k < 2 && rc == ROAM_OK; k++) {
-                rc = fft_rows(ctx, a, nullptr, tr, ti, M, N, false);
-                if (rc == ROAM_OK) rc = fft_transpose(ctx, tr, ti, 1, M, N, F[k][0], F[k][1]);
-                if (rc == ROAM_OK) rc = fft_rows(ctx, F[k][0], F[k][1], F[k][0], F[k][1], N, M, false);
+                rc = fft_rows(ctx, p.a, nullptr, p.tr, p.ti, M, N, false);
+                if (rc == ROAM_OK) rc = fft_transpose(ctx, p.tr, p.ti, 1, M, N, p.F[k][0], p.F[k][1]);
+                if (rc == ROAM_OK) rc = fft_rows(ctx, p.F[k][0], p.F[k][1], p.F[k][0], p.F[k][1], N, M, false);
             }
-            if (rc == ROAM_OK) rc = fft_rows(ctx, tr, ti, tr, ti, N, M, true);
-            if (rc == ROAM_OK) rc = fft_transpose(ctx, tr, ti, 1, N, M, F[0][0], F[0][1]);
-            if (rc == ROAM_OK) rc = fft_rows(ctx, F[0][0], F[0][1], a, nullptr, M, N, true);
+            if (rc == ROAM_OK) rc = fft_rows(ctx, p.tr, p.ti, p.tr, p.ti, N, M, true);
+            if (rc == ROAM_OK) rc = fft_transpose(ctx, p.tr, p.ti, 1, N, M, p.F[0][0], p.F[0][1]);
+            if (rc == ROAM_OK) rc = fft_rows(ctx, p.F[0][0], p.F[0][1], p.a, nullptr, M, N, true);
         } else if (what == ROAM_TIME_DFT_FIVE) {
-            for (int k = 0; k < 2; k++) (void)launch_fmt_dft2(st, a, nullptr, M, N, -1.0, tr, ti, F[k][0], F[k][1]);
-            (void)launch_fmt_dft2(st, tr, ti, M, N, 1.0, F[0][0], F[0][1], a, nullptr);
+            for (int k = 0; k < 2; k++) (void)launch_fmt_dft2(st, p.a, nullptr, M, N, -1.0, p.tr, p.ti, p.F[k][0], p.F[k][1]);
+            (void)launch_fmt_dft2(st, p.tr, p.ti, M, N, 1.0, p.F[0][0], p.F[0][1], p.a, nullptr);
         } else if (what == ROAM_TIME_FFT_ROWS) {
-            rc = fft_rows(ctx, tr, ti, tr, ti, M, N, false);
+            rc = fft_rows(ctx, p.tr, p.ti, p.tr, p.ti, M, N, false);
         } else if (what == ROAM_TIME_FFT_TRANSPOSE) {
-            rc = fft_transpose(ctx, tr, ti, 1, M, N, F[0][0], F[0][1]);
+            rc = fft_transpose(ctx, p.tr, p.ti, 1, M, N, p.F[0][0], p.F[0][1]);
         } else {
-            rc = fft_rows(ctx, tr, ti, tr, ti, N, M, false);
+            rc = fft_rows(ctx, p.tr, p.ti, p.tr, p.ti, N, M, false);
         }
     }
     (void)hipEventRecord(e1, st);

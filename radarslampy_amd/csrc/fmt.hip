@@ -10,28 +10,9 @@
 // accumulation (14 M complex multiply-adds per image, tens of microseconds) instead of an FFT library; twiddles come from
 // sincospi on (k mod n) / n.  OpenCV is absent and the reference keeps no output of this path: parity is against the
 // oracle's numpy restatement (tolerance 1e-5 rad), PARITY UNPINNED like the oracle itself.
-#include "roam_internal.h"
+#include "cvmap.h"
 
-#define FMT_PI 3.14159265358979323846
-
-__device__ __forceinline__ float fmt_fast_atan2_deg(float y, float x)
-{
-    const float sc = (float)(180 / FMT_PI);
-    const float p1 = __fmul_rn(0.9997878412794807f, sc), p3 = __fmul_rn(-0.3258083974640975f, sc);
-    const float p5 = __fmul_rn(0.1555786518463281f, sc), p7 = __fmul_rn(-0.04432655554792128f, sc);
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = __fdiv_rn(ay, __fadd_rn(ax, (float)2.220446049250313e-16)); c2 = __fmul_rn(c, c);
-        a = __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c);
-    } else {
-        c = __fdiv_rn(ax, __fadd_rn(ay, (float)2.220446049250313e-16)); c2 = __fmul_rn(c, c);
-        a = __fsub_rn(90.f, __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c));
-    }
-    if (x < 0) a = __fsub_rn(180.f, a);
-    if (y < 0) a = __fsub_rn(360.f, a);
-    return a;
-}
+#define FMT_PI CVM_PI
 
 // cv2.resize(img[:, :clip], (nw, rows)), INTER_LINEAR, float32: two taps per output column, rows untouched
 __global__ void fmt_resize_kernel(const float *__restrict__ polar, int rows, int64_t stride, int clip, int nw, float *__restrict__ out)
@@ -49,14 +30,6 @@ __global__ void fmt_resize_kernel(const float *__restrict__ polar, int rows, int
     out[(int64_t)r * nw + dx] = __fadd_rn(__fmul_rn(s0, __fsub_rn(1.f, fx)), __fmul_rn(s1, fx));
 }
 
-__device__ __forceinline__ float fmt_polar_tap(const float *p, int rows, int cols, int py, int px)
-{
-    if (px < 0 || px >= cols || py < 0 || py >= rows + 2) return 0.f;
-    int r = py - 1;
-    if (r < 0) r += rows; else if (r >= rows) r -= rows;
-    return p[(int64_t)r * cols + px];
-}
-
 // inverse linear warpPolar, maxRadius = cols, centre (cols, cols): (rows x cols) -> (2 cols x 2 cols)
 __global__ void fmt_cart_kernel(const float *__restrict__ polar, int rows, int cols, float *__restrict__ cart)
 {
@@ -64,22 +37,11 @@ __global__ void fmt_cart_kernel(const float *__restrict__ polar, int rows, int c
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= W) return;
     const double Kangle = 2 * FMT_PI / (double)rows, Kmag = (double)cols / (double)cols;
-    const float fx = __fsub_rn((float)x, (float)cols), fy = __fsub_rn((float)y, (float)cols);
-    const float mag = rn_sqrtf(__fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fy, fy)));
-    const float ang = __fmul_rn(fmt_fast_atan2_deg(fy, fx), (float)(FMT_PI / 180.0));
-    const float mx = (float)__ddiv_rn((double)mag, Kmag), my = __fadd_rn((float)__ddiv_rn((double)ang, Kangle), 1.f);
-    const int sx = __float2int_rn(__fmul_rn(mx, 32.f)), sy = __float2int_rn(__fmul_rn(my, 32.f));
-    const int ix = sx >> 5, iy = sy >> 5;
-    const float wx1 = __fmul_rn((float)(sx & 31), 1.f / 32.f), wx0 = __fsub_rn(1.f, wx1);
-    const float wy1 = __fmul_rn((float)(sy & 31), 1.f / 32.f), wy0 = __fsub_rn(1.f, wy1);
-    float v = __fmul_rn(fmt_polar_tap(polar, rows, cols, iy, ix), __fmul_rn(wy0, wx0));
-    v = __fadd_rn(v, __fmul_rn(fmt_polar_tap(polar, rows, cols, iy, ix + 1), __fmul_rn(wy0, wx1)));
-    v = __fadd_rn(v, __fmul_rn(fmt_polar_tap(polar, rows, cols, iy + 1, ix), __fmul_rn(wy1, wx0)));
-    v = __fadd_rn(v, __fmul_rn(fmt_polar_tap(polar, rows, cols, iy + 1, ix + 1), __fmul_rn(wy1, wx1)));
-    cart[(int64_t)y * W + x] = v;
+    float mx, my;
+    cv_polar_inverse_map<false>(x, y, (float)cols, (float)cols, Kmag, Kangle, mx, my);
+    const CvPolarTap<false> tap = {polar, rows, cols, (int64_t)cols, 0};
+    cart[(int64_t)y * W + x] = cv_remap(tap, mx, my);
 }
-
-__device__ __forceinline__ float fmt_cart_tap(const float *c, int W, int y, int x) { return (x < 0 || x >= W || y < 0 || y >= W) ? 0.f : c[(int64_t)y * W + x]; }
 
 // forward semilog warpPolar of the W x W Cartesian image (centre, maxRadius = W / 2) to dw x dh, multiplied by the Hanning
 // window sqrt(wr * wc) of cv2.createHanningWindow and zero-padded into the M x N DFT input (float64)
@@ -93,19 +55,13 @@ __global__ void fmt_logpolar_window_kernel(const float *__restrict__ cart, int W
         const double Kangle = 2 * FMT_PI / (double)dh, Kmag = log(R) / (double)dw;
         const double KKy = Kangle * (double)phi, cp = cos(KKy), sp = sin(KKy);
         const float br = (float)(exp((double)rho * Kmag) - 1.0);
-        const float mx = (float)((double)br * cp + R), my = (float)((double)br * sp + R);
-        const int sx = __float2int_rn(__fmul_rn(mx, 32.f)), sy = __float2int_rn(__fmul_rn(my, 32.f));
-        const int ix = sx >> 5, iy = sy >> 5;
-        const float wx1 = __fmul_rn((float)(sx & 31), 1.f / 32.f), wx0 = __fsub_rn(1.f, wx1);
-        const float wy1 = __fmul_rn((float)(sy & 31), 1.f / 32.f), wy0 = __fsub_rn(1.f, wy1);
-        float v = __fmul_rn(fmt_cart_tap(cart, W, iy, ix), __fmul_rn(wy0, wx0));
-        v = __fadd_rn(v, __fmul_rn(fmt_cart_tap(cart, W, iy, ix + 1), __fmul_rn(wy0, wx1)));
-        v = __fadd_rn(v, __fmul_rn(fmt_cart_tap(cart, W, iy + 1, ix), __fmul_rn(wy1, wx0)));
-        v = __fadd_rn(v, __fmul_rn(fmt_cart_tap(cart, W, iy + 1, ix + 1), __fmul_rn(wy1, wx1)));
+        float mx, my;
+        cv_polar_forward_map((double)br, cp, sp, R, R, mx, my);
+        const CvCartTap tap = {cart, W, W, (int64_t)W};
+        const float v = cv_remap(tap, mx, my);
         const double wc = 0.5 * (1.0 - cos(2.0 * FMT_PI / (double)(dw - 1) * (double)rho));
         const double wr = 0.5 * (1.0 - cos(2.0 * FMT_PI / (double)(dh - 1) * (double)phi));
-        const float win = rn_sqrtf((float)(wr * wc));
-        val = (double)__fmul_rn(win, v);
+        val = (double)cv_hanning_product(wr, wc, v);
     }
     out[(int64_t)phi * N + rho] = val;
 }
@@ -214,6 +170,14 @@ int optimal_dft_size(int n)
     return best;
 }
 
+// utils.normalize_angles: (th + pi) % (2 pi) - pi (Python modulo)
+double roam_normalize_angle(double th)
+{
+    th = fmod(th + FMT_PI, 2.0 * FMT_PI);
+    if (th < 0) th += 2.0 * FMT_PI;
+    return th - FMT_PI;
+}
+
 extern "C" int32_t roam_fmt_rotation(roam_ctx *ctx, const float *src_polar, const float *tgt_polar, int32_t rows, int32_t cols,
                                      int32_t clip_px, int32_t downsample, double *angle_rad, double *scale, double *response)
 {
@@ -254,10 +218,7 @@ extern "C" int32_t roam_fmt_rotation(roam_ctx *ctx, const float *src_polar, cons
     HIP_TRY(ctx, hipMemcpyAsync(o, d_out, sizeof(o), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const int sz = dh > dw ? dh : dw;
-    double ang = -o[1] * 2.0 * FMT_PI / (double)sz;
-    ang = fmod(ang + FMT_PI, 2.0 * FMT_PI);                  // utils.normalize_angles: (th + pi) % (2 pi) - pi (Python modulo)
-    if (ang < 0) ang += 2.0 * FMT_PI;
-    *angle_rad = ang - FMT_PI;
+    *angle_rad = roam_normalize_angle(-o[1] * 2.0 * FMT_PI / (double)sz);
     if (scale) *scale = pow(exp(log((double)dh / 2.0) / (double)sz), o[0]);
     if (response) *response = o[2];
     return ROAM_OK;

@@ -6,66 +6,11 @@
 //   fmtb_cart_kernel      inverse linear warpPolar to 2R x 2R, centre (R, R), maxRadius R (convertPolarImgToLogPolar, parseData.py:138-160)
 //   fmtb_logpolar_kernel  forward semilog warpPolar to round(R) x round(pi R), [the image before the window -> lp_out,] times the
 //                         cv2.createHanningWindow factor, rounded to float32, zero-padded into the float64 M x N plane of the FFT
-// The arithmetic is warppolar.hip's and fmt.hip's operation for operation (explicit __f*_rn, no contraction); like warppolar.hip the
+// The maps, the remap and the window product are cvmap.h's, the same definitions warppolar.hip and fmt.hip call; like warppolar.hip the
 // radius, cos / sin and window tables come from the host's libm, so that the log-polar image equals the oracle's bit for bit.
 // The correlation behind it is fft.hip's (roam_fmt_batch_run): these kernels only fill its planes.  No atomics: every output element
 // has one writer, and an image's result does not depend on its place in the batch.
-#include "roam_internal.h"
-
-#define FMTB_PI 3.14159265358979323846
-
-// (the helpers below restate wp_fast_atan2_deg / wp_tap_index / wp_remap of warppolar.hip, which are local to that unit)
-__device__ __forceinline__ float fmtb_fast_atan2_deg(float y, float x)
-{
-    const float sc = (float)(180 / FMTB_PI);
-    const float p1 = __fmul_rn(0.9997878412794807f, sc), p3 = __fmul_rn(-0.3258083974640975f, sc);
-    const float p5 = __fmul_rn(0.1555786518463281f, sc), p7 = __fmul_rn(-0.04432655554792128f, sc);
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = __fdiv_rn(ay, __fadd_rn(ax, (float)2.220446049250313e-16)); c2 = __fmul_rn(c, c);
-        a = __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c);
-    } else {
-        c = __fdiv_rn(ax, __fadd_rn(ay, (float)2.220446049250313e-16)); c2 = __fmul_rn(c, c);
-        a = __fsub_rn(90.f, __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c));
-    }
-    if (x < 0) a = __fsub_rn(180.f, a);
-    if (y < 0) a = __fsub_rn(360.f, a);
-    return a;
-}
-
-__device__ __forceinline__ int fmtb_tap_index(int s) { return min(max(s >> 5, -32768), 32767); }
-
-// the resized polar image with its wrapped border rows: py indexes the padded image (rows + 2)
-struct FmtbPolarTap {
-    const float *p; int rows, cols;
-    __device__ float operator()(int py, int px) const
-    {
-        if (px < 0 || px >= cols || py < 0 || py >= rows + 2) return 0.f;
-        int r = py - 1;
-        if (r < 0) r += rows; else if (r >= rows) r -= rows;
-        return p[(int64_t)r * cols + px];
-    }
-};
-
-struct FmtbCartTap {
-    const float *p; int W;
-    __device__ float operator()(int y, int x) const { return (x < 0 || x >= W || y < 0 || y >= W) ? 0.f : p[(int64_t)y * W + x]; }
-};
-
-template <class Tap>
-__device__ __forceinline__ float fmtb_remap(const Tap &tap, float mx, float my)
-{
-    const int sx = __float2int_rn(__fmul_rn(mx, 32.f)), sy = __float2int_rn(__fmul_rn(my, 32.f));
-    const int ix = fmtb_tap_index(sx), iy = fmtb_tap_index(sy);
-    const float wx1 = __fmul_rn((float)(sx & 31), 1.f / 32.f), wx0 = __fsub_rn(1.f, wx1);
-    const float wy1 = __fmul_rn((float)(sy & 31), 1.f / 32.f), wy0 = __fsub_rn(1.f, wy1);
-    float v = __fmul_rn(tap(iy, ix), __fmul_rn(wy0, wx0));
-    v = __fadd_rn(v, __fmul_rn(tap(iy, ix + 1), __fmul_rn(wy0, wx1)));
-    v = __fadd_rn(v, __fmul_rn(tap(iy + 1, ix), __fmul_rn(wy1, wx0)));
-    v = __fadd_rn(v, __fmul_rn(tap(iy + 1, ix + 1), __fmul_rn(wy1, wx1)));
-    return v;
-}
+#include "cvmap.h"
 
 // grid (ceil(nw / 64), rows, images): out[z] = rows x nw, two taps per output column, rows untouched
 template <bool U8>
@@ -100,13 +45,10 @@ __global__ __launch_bounds__(64) void fmtb_cart_kernel(const float *__restrict__
     if (x >= W) return;
     const int64_t z = blockIdx.z;
     const double Kangle = 6.283185307179586476925286766559 / (double)rows, Kmag = (double)R / (double)R;
-    const float c = (float)R;
-    const float fx = __fsub_rn((float)x, c), fy = __fsub_rn((float)y, c);
-    const float mag = rn_sqrtf(__fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fy, fy)));
-    const float ang = __fmul_rn(fmtb_fast_atan2_deg(fy, fx), (float)(FMTB_PI / 180.0));
-    const float mx = (float)__ddiv_rn((double)mag, Kmag), my = __fadd_rn((float)__ddiv_rn((double)ang, Kangle), 1.f);
-    const FmtbPolarTap tap = {small + z * rows * R, rows, R};
-    cart[(z * W + y) * W + x] = fmtb_remap(tap, mx, my);
+    float mx, my;
+    cv_polar_inverse_map<false>(x, y, (float)R, (float)R, Kmag, Kangle, mx, my);
+    const CvPolarTap<false> tap = {small + z * rows * R, rows, R, (int64_t)R, 0};
+    cart[(z * W + y) * W + x] = cv_remap(tap, mx, my);
 }
 
 // grid (ceil(N / 64), M, images): cart[z] -> the M x N plane of image z (zero outside dh x dw).  Image z < nb writes plane z, the others
@@ -123,13 +65,12 @@ __global__ __launch_bounds__(64) void fmtb_logpolar_kernel(const float *__restri
     double val = 0.0;
     if (rho < dw && phi < dh) {
         const double *cs = tab, *wr = tab + 2 * dh, *wc = wr + dh;
-        const double b = (double)br[rho], cp = cs[2 * phi], sp = cs[2 * phi + 1];
-        const float c = (float)R;
-        const float mx = (float)__dadd_rn(__dmul_rn(b, cp), (double)c), my = (float)__dadd_rn(__dmul_rn(b, sp), (double)c);
-        const FmtbCartTap tap = {cart + z * W * W, W};
-        const float v = fmtb_remap(tap, mx, my);
+        float mx, my;
+        cv_polar_forward_map((double)br[rho], cs[2 * phi], cs[2 * phi + 1], (double)(float)R, (double)(float)R, mx, my);
+        const CvCartTap tap = {cart + z * W * W, W, W, (int64_t)W};
+        const float v = cv_remap(tap, mx, my);
         if (lp_out) lp_out[(z * dh + phi) * dw + rho] = v;
-        val = (double)__fmul_rn(rn_sqrtf((float)(wr[phi] * wc[rho])), v);
+        val = (double)cv_hanning_product(wr[phi], wc[rho], v);
     }
     const int64_t plane = z < nb ? z : z + plane_gap;
     planes[(plane * M + phi) * N + rho] = val;

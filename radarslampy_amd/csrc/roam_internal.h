@@ -198,6 +198,19 @@ int optimal_dft_size(int n);
 // fft.hip: free the context's twiddle tables
 void roam_fft_release(roam_ctx *ctx);
 
+// host helpers of the OpenCV-shaped units, each defined once (the device side of the same arithmetic is cvmap.h)
+// fft.hip: cv2.createHanningWindow's float64 factors for a side of n
+void roam_hanning_factors(int n, double *w);
+// warppolar.hip: the forward warpPolar's host tables, linear or semilog: br = the radius per destination column (dw floats), cs = cos,
+// sin per destination row (2 dh doubles)
+void roam_warp_polar_tables(int dw, int dh, double max_radius, bool semilog, float *br, double *cs);
+// warppolar.hip: n strided host images (rows x width floats; strides in floats) -> a tight device array, asynchronous on st, in as few
+// copies as the layout allows
+hipError_t roam_upload_packed_f32(hipStream_t st, float *dst, const float *src, int n, int width, int rows, int64_t row_stride,
+                                  int64_t image_stride);
+// fmt.hip: utils.normalize_angles, (th + pi) % (2 pi) - pi with Python's modulo
+double roam_normalize_angle(double th);
+
 // fmt_batch.hip: the batched front end of the rotation prior.  Image z of a launch reads base + (index ? index[z] : z) * image_stride
 // (+ payload_off for u8 records); strides in elements (floats or bytes); base and index are device pointers
 struct FmtBatchSrc {
@@ -208,7 +221,7 @@ struct FmtBatchSrc {
 };
 // 2 nb images (nb sources, then nb targets): resize to rows x R, inverse warpPolar to 2R x 2R (cart), semilog warpPolar to dh x dw,
 // window, zero-padded M x N float64 planes: image z < nb -> planes + z M N, the others -> planes + (z + plane_gap) M N.
-// tab: cos, sin per log-polar row (2 dh doubles) | window per row (dh) | per column (dw); br: radius per column (dw floats);
+// tab: roam_warp_polar_tables' cs (2 dh doubles) | roam_hanning_factors per row (dh) | per column (dw); br: its radius per column;
 // small: 2 nb x rows x R floats, cart: 2 nb x 2R x 2R floats, lp_out (optional): 2 nb x dh x dw floats, the images before the window
 hipError_t launch_fmt_batch_front(hipStream_t st, const FmtBatchSrc &src, int nb, int rows, int clip, int R, int dw, int dh, int M, int N,
                                   const double *tab, const float *br, float *small, float *cart, double *planes, int64_t plane_gap,

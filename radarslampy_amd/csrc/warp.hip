@@ -5,7 +5,7 @@
 // and the (img*255).astype(uint8) of getTransformKLT.py:356-357, fused: the f32 Cartesian
 // image (16.4 MB) is only materialised when the caller asks for it.
 //
-// Arithmetic follows the published OpenCV pipeline operation by operation (see
+// Arithmetic follows the published OpenCV pipeline operation by operation (cvmap.h has the map and the remap; see
 // oracle/c/warp_klt.c for the statement of what is and is not pinned): float maps from
 // sqrt + the degree-7 fastAtan polynomial, double-precision scale, 1/32-pixel coordinate
 // rounding (round-half-even), table-equivalent bilinear weights, zero fill in range, wrap
@@ -15,78 +15,17 @@
 // Layout: one thread produces 4 consecutive output pixels of one row and stores them as a
 // single 32-bit word (u8) / 128-bit vector (f32): 256-thread blocks, grid = (ceil(W/4/256),
 // W, lanes).  The polar source (0.8 MB u8 per scan) is gathered through L2.
-#include "roam_internal.h"
-
-__device__ __forceinline__ float fast_atan2_deg(float y, float x)
-{
-    const float R2D = (float)(180 / 3.14159265358979323846);
-    const float p1 = 0.9997878412794807f * R2D;
-    const float p3 = -0.3258083974640975f * R2D;
-    const float p5 = 0.1555786518463281f * R2D;
-    const float p7 = -0.04432655554792128f * R2D;
-    const float DE = (float)2.220446049250313e-16;
-    float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = __fdiv_rn(ay, __fadd_rn(ax, DE));
-        c2 = __fmul_rn(c, c);
-        a = __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c);
-    } else {
-        c = __fdiv_rn(ax, __fadd_rn(ay, DE));
-        c2 = __fmul_rn(c, c);
-        a = __fsub_rn(90.f, __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c));
-    }
-    if (x < 0) a = __fsub_rn(180.f, a);
-    if (y < 0) a = __fsub_rn(360.f, a);
-    return a;
-}
-
-template <bool U8>
-__device__ __forceinline__ float polar_tap(const void *base, int64_t row_stride, int payload_off,
-                                           int rows, int cols, int py, int px)
-{
-    if (px < 0 || px >= cols || py < 0 || py >= rows + 2) return 0.f;
-    int r = py - 1;
-    if (r < 0) r += rows;
-    else if (r >= rows) r -= rows;
-    if (U8) {
-        const uint8_t *p = reinterpret_cast<const uint8_t *>(base) + (int64_t)r * row_stride + payload_off;
-        return __fdiv_rn((float)p[px], 255.f);
-    } else {
-        const float *p = reinterpret_cast<const float *>(base) + (int64_t)r * row_stride;
-        return p[px];
-    }
-}
+#include "cvmap.h"
 
 template <bool U8>
 __device__ __forceinline__ float warp_pixel(const void *base, int64_t row_stride, int payload_off,
                                             int rows, int cols, int R, double Kangle, double Kmag,
                                             int x, int y)
 {
-    const float fx = __fsub_rn((float)x, (float)R);
-    const float fy = __fsub_rn((float)y, (float)R);
-    const float mag = rn_sqrtf(__fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fy, fy)));
-    const float ang = __fmul_rn(fast_atan2_deg(fy, fx), (float)(3.14159265358979323846 / 180.0));
-    const double rho = __ddiv_rn((double)mag, Kmag);
-    const double phi = __ddiv_rn((double)ang, Kangle);
-    const float mx = (float)rho;
-    const float my = __fadd_rn((float)phi, 1.f);
-    const int sx = __float2int_rn(__fmul_rn(mx, 32.f));
-    const int sy = __float2int_rn(__fmul_rn(my, 32.f));
-    const int ix = sx >> 5, iy = sy >> 5;
-    const float wx1 = __fmul_rn((float)(sx & 31), 1.f / 32.f), wx0 = __fsub_rn(1.f, wx1);
-    const float wy1 = __fmul_rn((float)(sy & 31), 1.f / 32.f), wy0 = __fsub_rn(1.f, wy1);
-    const float w00 = __fmul_rn(wy0, wx0), w01 = __fmul_rn(wy0, wx1);
-    const float w10 = __fmul_rn(wy1, wx0), w11 = __fmul_rn(wy1, wx1);
-    const float s00 = polar_tap<U8>(base, row_stride, payload_off, rows, cols, iy, ix);
-    const float s01 = polar_tap<U8>(base, row_stride, payload_off, rows, cols, iy, ix + 1);
-    const float s10 = polar_tap<U8>(base, row_stride, payload_off, rows, cols, iy + 1, ix);
-    const float s11 = polar_tap<U8>(base, row_stride, payload_off, rows, cols, iy + 1, ix + 1);
-    float v = __fmul_rn(s00, w00);
-    v = __fadd_rn(v, __fmul_rn(s01, w01));
-    v = __fadd_rn(v, __fmul_rn(s10, w10));
-    v = __fadd_rn(v, __fmul_rn(s11, w11));
-    return v;
+    float mx, my;
+    cv_polar_inverse_map<false>(x, y, (float)R, (float)R, Kmag, Kangle, mx, my);
+    const CvPolarTap<U8> tap = {base, rows, cols, row_stride, payload_off};
+    return cv_remap(tap, mx, my);
 }
 
 __device__ __forceinline__ uint32_t quant_u8(float v)
@@ -159,17 +98,10 @@ __global__ __launch_bounds__(256) void warp_map_kernel(int rows, int cols, int R
     if (x >= W) return;
     const double Kangle = 6.283185307179586476925286766559 / (double)rows;
     const double Kmag = (double)R / (double)cols;
-    const float fx = __fsub_rn((float)x, (float)R);
-    const float fy = __fsub_rn((float)y, (float)R);
-    const float mag = rn_sqrtf(__fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fy, fy)));
-    const float ang = __fmul_rn(fast_atan2_deg(fy, fx), (float)(3.14159265358979323846 / 180.0));
-    const double rho = __ddiv_rn((double)mag, Kmag);
-    const double phi = __ddiv_rn((double)ang, Kangle);
-    const float mx = (float)rho;
-    const float my = __fadd_rn((float)phi, 1.f);
-    const int sx = __float2int_rn(__fmul_rn(mx, 32.f));
-    const int sy = __float2int_rn(__fmul_rn(my, 32.f));
-    int ix = sx >> 5, iy = sy >> 5;
+    float mx, my;
+    cv_polar_inverse_map<false>(x, y, (float)R, (float)R, Kmag, Kangle, mx, my);
+    const int sx = cv_fixed32(mx), sy = cv_fixed32(my);
+    int ix = cv_tap_index(sx), iy = cv_tap_index(sy);
     if (ix > 4095) ix = 4095;                   // >= cols: both taps read zero anyway
     if (ix < 0) ix = 4095;
     if (iy < 0) iy = 0;

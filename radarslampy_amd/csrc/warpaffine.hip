@@ -7,28 +7,18 @@
 //     adelta = cvRound(M0 x 1024), bdelta = cvRound(M3 x 1024), X0 = cvRound((M1 y + M2) 1024) + 16, Y0 = cvRound((M4 y + M5) 1024) + 16,
 //     X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5 in (wrapping) int32: 1/32-px coordinates; tap index saturate<int16>(X >> 5),
 //     fraction X & 31.
-//   remap: warppolar.hip's - weights wy * wx from (frac / 32, 1 - frac / 32), taps outside the source read 0, sum in OpenCV's order.
+//   remap: cvmap.h's - weights wy * wx from (frac / 32, 1 - frac / 32), taps outside the source read 0, sum in OpenCV's order.
+// The fixed-point block and the remap are cv_affine_fixed32 and cv_remap of cvmap.h, shared with fmt_register.hip.
 // One thread per output pixel in a 32 x 8 tile of the destination, blockIdx.z = image.  A 256-wide row strip of the destination walks
 // a slanted line through the source (at 45 degrees 181 source rows, one 128-byte line or two from each); the 32 x 8 tile's footprint is a
 // 32 x 8 rectangle of the source turned by the angle - inside a 34 x 34 box at any angle - so a line fetched for one wave serves the
 // other three from the CU's L1 and neighbouring tiles from the L2.  Stores: a wave writes two full 128-byte row segments.
-#include "roam_internal.h"
+#include "cvmap.h"
 #include <cmath>
 
 #define WA_MAX_SIDE 16384
 #define WA_TILE_X 32
 #define WA_TILE_Y 8
-
-// saturate_cast<int>(double): nearest-even, saturated (the clamp is explicit: a float-to-int conversion out of range is undefined)
-__device__ __forceinline__ unsigned wa_round(double v) { return (unsigned)(int)fmin(fmax(rint(v), -2147483648.0), 2147483647.0); }
-
-// saturate_cast<short>(s >> INTER_BITS)
-__device__ __forceinline__ int wa_tap_index(int s) { return min(max(s >> 5, -32768), 32767); }
-
-__device__ __forceinline__ float wa_tap(const float *__restrict__ p, int rows, int cols, int64_t stride, int y, int x)
-{
-    return (x < 0 || x >= cols || y < 0 || y >= rows) ? 0.f : p[(int64_t)y * stride + x];
-}
 
 // M: the INVERSE maps (destination -> source), 6 doubles per matrix; m_stride = 0 (one for all images) or 6
 __global__ __launch_bounds__(WA_TILE_X * WA_TILE_Y) void warp_affine_kernel(const float *__restrict__ src, int rows, int cols,
@@ -39,23 +29,10 @@ __global__ __launch_bounds__(WA_TILE_X * WA_TILE_Y) void warp_affine_kernel(cons
     const int x = blockIdx.x * WA_TILE_X + threadIdx.x, y = blockIdx.y * WA_TILE_Y + threadIdx.y;
     if (x >= dw || y >= dh) return;
     const int64_t img = blockIdx.z;
-    const double *m = M + img * m_stride;
-    const double dx = (double)x, dy = (double)y;
-    // the int32 sums wrap (unsigned arithmetic)
-    const unsigned adelta = wa_round(__dmul_rn(__dmul_rn(m[0], dx), 1024.0));
-    const unsigned bdelta = wa_round(__dmul_rn(__dmul_rn(m[3], dx), 1024.0));
-    const unsigned X0 = wa_round(__dmul_rn(__dadd_rn(__dmul_rn(m[1], dy), m[2]), 1024.0)) + 16u;
-    const unsigned Y0 = wa_round(__dmul_rn(__dadd_rn(__dmul_rn(m[4], dy), m[5]), 1024.0)) + 16u;
-    const int X = (int)(X0 + adelta) >> 5, Y = (int)(Y0 + bdelta) >> 5;
-    const int ix = wa_tap_index(X), iy = wa_tap_index(Y);
-    const float wx1 = __fmul_rn((float)(X & 31), 1.f / 32.f), wx0 = __fsub_rn(1.f, wx1);
-    const float wy1 = __fmul_rn((float)(Y & 31), 1.f / 32.f), wy0 = __fsub_rn(1.f, wy1);
-    const float *p = src + img * image_stride;
-    float v = __fmul_rn(wa_tap(p, rows, cols, row_stride, iy, ix), __fmul_rn(wy0, wx0));
-    v = __fadd_rn(v, __fmul_rn(wa_tap(p, rows, cols, row_stride, iy, ix + 1), __fmul_rn(wy0, wx1)));
-    v = __fadd_rn(v, __fmul_rn(wa_tap(p, rows, cols, row_stride, iy + 1, ix), __fmul_rn(wy1, wx0)));
-    v = __fadd_rn(v, __fmul_rn(wa_tap(p, rows, cols, row_stride, iy + 1, ix + 1), __fmul_rn(wy1, wx1)));
-    dst[(img * dh + y) * dw + x] = v;
+    int X, Y;
+    cv_affine_fixed32(M + img * m_stride, x, y, X, Y);
+    const CvCartTap tap = {src + img * image_stride, rows, cols, row_stride};
+    dst[(img * dh + y) * dw + x] = cv_remap(tap, X, Y);
 }
 
 // OpenCV's invertAffineTransform as warpAffine applies it in place (no fused multiply-add: roam_internal.h)
@@ -124,14 +101,7 @@ extern "C" int32_t roam_warp_affine_f32(roam_ctx *ctx, const float *src, int32_t
     float *d_in = (float *)roam_scratch(ctx, S_IN0, sizeof(float) * nin * n);
     float *d_out = (float *)roam_scratch(ctx, S_OUT0, sizeof(float) * nout * n);
     if (!d_in || !d_out) return ROAM_E_HIP;
-    // pack the images tightly on the way up, as roam_warp_polar_f32 does
-    if (n == 1 || src_image_stride == (int64_t)rows * src_row_stride)
-        HIP_TRY(ctx, hipMemcpy2DAsync(d_in, sizeof(float) * cols, src, sizeof(float) * src_row_stride, sizeof(float) * cols,
-                                      (size_t)rows * n, hipMemcpyHostToDevice, st));
-    else
-        for (int i = 0; i < n; i++)
-            HIP_TRY(ctx, hipMemcpy2DAsync(d_in + i * nin, sizeof(float) * cols, src + i * src_image_stride, sizeof(float) * src_row_stride,
-                                          sizeof(float) * cols, rows, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, roam_upload_packed_f32(st, d_in, src, n, cols, rows, src_row_stride, src_image_stride));
     std::vector<double> inv;
     const double *d_M = nullptr;
     const int32_t rc = wa_upload_matrices(ctx, M, m_count, flags, inv, &d_M);

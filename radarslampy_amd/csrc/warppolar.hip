@@ -6,69 +6,17 @@
 //     mx = p / Kmag, my = ang / Kangle + 1 with Kmag = maxRadius / cols (or log(maxRadius) / cols), Kangle = 2 pi / rows.
 //   forward (Cartesian -> polar): dh rows of angle, dw columns of radius; the radius table br (dw floats) and cos / sin per row
 //     (2 dh doubles) come from the HOST's libm, as OpenCV computes them, so that they equal what the oracle's C computes.
+//   The maps and the remap are cvmap.h's, the definitions every unit that samples as OpenCV does calls; the host tables and the packed
+//   upload defined here (roam_warp_polar_tables, roam_upload_packed_f32) serve fft.hip and warpaffine.hip too.
 //   remap: coordinates rounded to 1/32 px (cvRound, half to even), tap index saturated to int16, bilinear weights
 //     wy * wx from the 32-entry tables, taps outside the (padded) source read 0, sum in OpenCV's order.
 // The inverse semilog mode takes (float)log((double)(mag + 1)) where OpenCV uses hal::log32f: parity with OpenCV is unpinned there
 // (docs/PARITY.md).  One thread per output pixel, 256 along a destination row, blockIdx.y = row, blockIdx.z = image: coalesced
 // stores, gathers through the L2.
-#include "roam_internal.h"
+#include "cvmap.h"
 #include <cmath>
 
-#define WP_PI 3.14159265358979323846
 #define WP_MAX_SIDE 16384
-
-__device__ __forceinline__ float wp_fast_atan2_deg(float y, float x)
-{
-    const float sc = (float)(180 / WP_PI);
-    const float p1 = __fmul_rn(0.9997878412794807f, sc), p3 = __fmul_rn(-0.3258083974640975f, sc);
-    const float p5 = __fmul_rn(0.1555786518463281f, sc), p7 = __fmul_rn(-0.04432655554792128f, sc);
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = __fdiv_rn(ay, __fadd_rn(ax, (float)2.220446049250313e-16)); c2 = __fmul_rn(c, c);
-        a = __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c);
-    } else {
-        c = __fdiv_rn(ax, __fadd_rn(ay, (float)2.220446049250313e-16)); c2 = __fmul_rn(c, c);
-        a = __fsub_rn(90.f, __fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p7, c2), p5), c2), p3), c2), p1), c));
-    }
-    if (x < 0) a = __fsub_rn(180.f, a);
-    if (y < 0) a = __fsub_rn(360.f, a);
-    return a;
-}
-
-// saturate_cast<short>(s >> INTER_BITS)
-__device__ __forceinline__ int wp_tap_index(int s) { return min(max(s >> 5, -32768), 32767); }
-
-// polar source with its wrapped border rows: py indexes the padded image (rows + 2), 0 -> row rows - 1, rows + 1 -> row 0
-struct WpPolarTap {
-    const float *p; int rows, cols; int64_t stride;
-    __device__ float operator()(int py, int px) const
-    {
-        if (px < 0 || px >= cols || py < 0 || py >= rows + 2) return 0.f;
-        int r = py - 1;
-        if (r < 0) r += rows; else if (r >= rows) r -= rows;
-        return p[(int64_t)r * stride + px];
-    }
-};
-
-struct WpCartTap {
-    const float *p; int rows, cols; int64_t stride;
-    __device__ float operator()(int y, int x) const { return (x < 0 || x >= cols || y < 0 || y >= rows) ? 0.f : p[(int64_t)y * stride + x]; }
-};
-
-template <class Tap>
-__device__ __forceinline__ float wp_remap(const Tap &tap, float mx, float my)
-{
-    const int sx = __float2int_rn(__fmul_rn(mx, 32.f)), sy = __float2int_rn(__fmul_rn(my, 32.f));
-    const int ix = wp_tap_index(sx), iy = wp_tap_index(sy);
-    const float wx1 = __fmul_rn((float)(sx & 31), 1.f / 32.f), wx0 = __fsub_rn(1.f, wx1);
-    const float wy1 = __fmul_rn((float)(sy & 31), 1.f / 32.f), wy0 = __fsub_rn(1.f, wy1);
-    float v = __fmul_rn(tap(iy, ix), __fmul_rn(wy0, wx0));
-    v = __fadd_rn(v, __fmul_rn(tap(iy, ix + 1), __fmul_rn(wy0, wx1)));
-    v = __fadd_rn(v, __fmul_rn(tap(iy + 1, ix), __fmul_rn(wy1, wx0)));
-    v = __fadd_rn(v, __fmul_rn(tap(iy + 1, ix + 1), __fmul_rn(wy1, wx1)));
-    return v;
-}
 
 // polar (rows x cols per image, image_stride floats apart) -> dh x dw Cartesian per image
 template <bool LOG>
@@ -79,13 +27,10 @@ __global__ __launch_bounds__(256) void warp_polar_inverse_kernel(const float *__
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= dw) return;
     const int64_t img = blockIdx.z;
-    const float fx = __fsub_rn((float)x, cx), fy = __fsub_rn((float)y, cy);
-    const float mag = rn_sqrtf(__fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fy, fy)));
-    const float ang = __fmul_rn(wp_fast_atan2_deg(fy, fx), (float)(WP_PI / 180.0));
-    const float p = LOG ? (float)log((double)__fadd_rn(mag, 1.f)) : mag;
-    const float mx = (float)__ddiv_rn((double)p, Kmag), my = __fadd_rn((float)__ddiv_rn((double)ang, Kangle), 1.f);
-    const WpPolarTap tap = {src + img * image_stride, rows, cols, row_stride};
-    dst[(img * dh + y) * dw + x] = wp_remap(tap, mx, my);
+    float mx, my;
+    cv_polar_inverse_map<LOG>(x, y, cx, cy, Kmag, Kangle, mx, my);
+    const CvPolarTap<false> tap = {src + img * image_stride, rows, cols, row_stride, 0};
+    dst[(img * dh + y) * dw + x] = cv_remap(tap, mx, my);
 }
 
 // Cartesian (rows x cols per image) -> dh x dw polar per image; br[rho] the radius, cs[2 phi], cs[2 phi + 1] = cos, sin of the angle
@@ -96,10 +41,52 @@ __global__ __launch_bounds__(256) void warp_polar_forward_kernel(const float *__
     const int rho = blockIdx.x * blockDim.x + threadIdx.x, phi = blockIdx.y;
     if (rho >= dw) return;
     const int64_t img = blockIdx.z;
-    const double b = (double)br[rho], cp = cs[2 * phi], sp = cs[2 * phi + 1];
-    const float mx = (float)__dadd_rn(__dmul_rn(b, cp), (double)cx), my = (float)__dadd_rn(__dmul_rn(b, sp), (double)cy);
-    const WpCartTap tap = {src + img * image_stride, rows, cols, row_stride};
-    dst[(img * dh + phi) * dw + rho] = wp_remap(tap, mx, my);
+    float mx, my;
+    cv_polar_forward_map((double)br[rho], cs[2 * phi], cs[2 * phi + 1], (double)cx, (double)cy, mx, my);
+    const CvCartTap tap = {src + img * image_stride, rows, cols, row_stride};
+    dst[(img * dh + phi) * dw + rho] = cv_remap(tap, mx, my);
+}
+
+// OpenCV's host tables of the forward warpPolar (imgwarp.cpp): Kmag and Kangle from the DESTINATION size, the host's libm.
+// br: the radius per destination column (dw floats); cs: cos, sin of the angle per destination row (2 dh doubles)
+void roam_warp_polar_tables(int dw, int dh, double max_radius, bool semilog, float *br, double *cs)
+{
+    const double Kangle = 6.283185307179586476925286766559 / dh;
+    if (semilog) {
+        const double Kmag = std::log(max_radius) / dw;
+        for (int rho = 0; rho < dw; rho++) br[rho] = (float)(std::exp(rho * Kmag) - 1.0);
+    } else {
+        const double Kmag = max_radius / dw;
+        for (int rho = 0; rho < dw; rho++) br[rho] = (float)(rho * Kmag);
+    }
+    for (int phi = 0; phi < dh; phi++) {
+        const double KKy = Kangle * phi;
+        cs[2 * phi] = std::cos(KKy);
+        cs[2 * phi + 1] = std::sin(KKy);
+    }
+}
+
+// n host images (rows x width floats of rows row_stride apart, images image_stride apart; one image: image_stride is not read) -> a
+// tight n x rows x width device array, asynchronous on st.  One copy when the images are contiguous, one per image when only the rows
+// are (a 2-D copy moves the rows one by one), one 2-D copy when the images' rows follow each other at the row stride, else one per image
+hipError_t roam_upload_packed_f32(hipStream_t st, float *dst, const float *src, int n, int width, int rows, int64_t row_stride,
+                                  int64_t image_stride)
+{
+    const size_t nimg = (size_t)rows * width;
+    const bool rows_follow = n == 1 || image_stride == (int64_t)rows * row_stride;
+    if (row_stride == width && rows_follow) return hipMemcpyAsync(dst, src, sizeof(float) * nimg * n, hipMemcpyHostToDevice, st);
+    if (rows_follow)
+        return hipMemcpy2DAsync(dst, sizeof(float) * width, src, sizeof(float) * row_stride, sizeof(float) * width, (size_t)rows * n,
+                                hipMemcpyHostToDevice, st);
+    for (int i = 0; i < n; i++) {
+        const float *h = src + (int64_t)i * image_stride;
+        const hipError_t e = row_stride == width
+                                 ? hipMemcpyAsync(dst + (size_t)i * nimg, h, sizeof(float) * nimg, hipMemcpyHostToDevice, st)
+                                 : hipMemcpy2DAsync(dst + (size_t)i * nimg, sizeof(float) * width, h, sizeof(float) * row_stride,
+                                                    sizeof(float) * width, rows, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 extern "C" int32_t roam_warp_polar_f32(roam_ctx *ctx, const float *src, int32_t n, int32_t rows, int32_t cols, int64_t src_row_stride,
@@ -119,35 +106,14 @@ extern "C" int32_t roam_warp_polar_f32(roam_ctx *ctx, const float *src, int32_t 
     float *d_in = (float *)roam_scratch(ctx, S_IN0, sizeof(float) * nin * n);
     float *d_out = (float *)roam_scratch(ctx, S_OUT0, sizeof(float) * nout * n);
     if (!d_in || !d_out) return ROAM_E_HIP;
-    // pack the images tightly on the way up (a column slice of a wider record travels without its unused columns)
-    if (n == 1 || src_image_stride == (int64_t)rows * src_row_stride)
-        HIP_TRY(ctx, hipMemcpy2DAsync(d_in, sizeof(float) * cols, src, sizeof(float) * src_row_stride, sizeof(float) * cols,
-                                      (size_t)rows * n, hipMemcpyHostToDevice, st));
-    else
-        for (int i = 0; i < n; i++)
-            HIP_TRY(ctx, hipMemcpy2DAsync(d_in + i * nin, sizeof(float) * cols, src + i * src_image_stride, sizeof(float) * src_row_stride,
-                                          sizeof(float) * cols, rows, hipMemcpyHostToDevice, st));
+    // (a column slice of a wider record travels without its unused columns)
+    HIP_TRY(ctx, roam_upload_packed_f32(st, d_in, src, n, cols, rows, src_row_stride, src_image_stride));
     std::vector<unsigned char> tab;
     const float *d_br = nullptr;
     const double *d_cs = nullptr;
     if (!inverse) {
-        // OpenCV's host tables (imgwarp.cpp, warpPolar): Kmag and Kangle from the DESTINATION size
         tab.resize(sizeof(double) * 2 * dh + sizeof(float) * dw);
-        double *cs = (double *)tab.data();
-        float *br = (float *)(cs + 2 * dh);
-        const double Kangle = 6.283185307179586476925286766559 / dh;
-        if (semilog) {
-            const double Kmag = std::log(max_radius) / dw;
-            for (int rho = 0; rho < dw; rho++) br[rho] = (float)(std::exp(rho * Kmag) - 1.0);
-        } else {
-            const double Kmag = max_radius / dw;
-            for (int rho = 0; rho < dw; rho++) br[rho] = (float)(rho * Kmag);
-        }
-        for (int phi = 0; phi < dh; phi++) {
-            const double KKy = Kangle * phi;
-            cs[2 * phi] = std::cos(KKy);
-            cs[2 * phi + 1] = std::sin(KKy);
-        }
+        roam_warp_polar_tables(dw, dh, max_radius, semilog, (float *)((double *)tab.data() + 2 * dh), (double *)tab.data());
         unsigned char *d_tab = (unsigned char *)roam_scratch(ctx, S_TMP0, tab.size());
         if (!d_tab) return ROAM_E_HIP;
         HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
