@@ -227,9 +227,12 @@ int32_t roam_prune_blobs(const double *blobs, int32_t n, double overlap, uint8_t
 int32_t roam_argsort_np122(const double *keys, int32_t n, int32_t *order_out);
 
 /* ---- f4: FMT.getRotationUsingFMT (FMT.py:36-90; called first by Tracker.track, Tracker.py:62-63) ---------------------
- * Fourier-Mellin rotation prior between two polar images (rows x cols float32): range clip (clip_px bins, <= 0: none),
- * cv2.resize to clip / downsample columns, polar -> Cartesian -> log-polar, Hanning-windowed phase correlation.
- * angle_rad: R(angle) src = target; scale and response are optional. */
+ * Fourier-Mellin rotation prior between two contiguous polar images (rows x cols float32): range clip (clip_px bins, <= 0 or >= cols:
+ * none), cv2.resize to R = clip / downsample columns, polar -> Cartesian -> log-polar, Hanning-windowed phase correlation.
+ * angle_rad: R(angle) src = target; scale and response are optional.  This is n = 1 of roam_fmt_rotation_batch_f32 below
+ * (row_stride = cols), the same pass and the same numbers bit for bit.  ROAM_E_ARG, before any device call: a null src_polar /
+ * tgt_polar / angle_rad, rows outside [8, 16384], cols < 2, downsample < 1, R outside [ROAM_FMT_MIN_R, ROAM_FMT_MAX_R] = [4, 1303].
+ * (The separate direct-DFT implementation this entry had before took any rows >= 8 and R up to 2048.) */
 int32_t roam_fmt_rotation(roam_ctx *ctx, const float *src_polar, const float *tgt_polar, int32_t rows, int32_t cols,
                           int32_t clip_px, int32_t downsample, double *angle_rad, double *scale, double *response);
 
@@ -242,7 +245,7 @@ int32_t roam_fmt_rotation(roam_ctx *ctx, const float *src_polar, const float *tg
 int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t batch, int32_t rows, int32_t cols,
                                  int64_t row_stride, int64_t image_stride, int32_t hanning, double *out_dxdy, double *out_response);
 
-/* FMT.getRotationUsingFMT for n pairs in one device pass: the same estimate as roam_fmt_rotation, with the front end batched over the
+/* FMT.getRotationUsingFMT for n pairs in one device pass, the one implementation of the estimate: the front end batched over the
  * 2 n images (csrc/fmt_batch.hip) and the correlation through the mixed-radix FFT of roam_phase_correlate_f32, so the plane may be as
  * large as 4096 x 1350 (downsample 1 or 2).  src / tgt: n float32 polar images each, rows x cols, row_stride / image_stride in
  * elements.  R = clip / downsample columns after the resize, clip = clip_px (<= 0 or >= cols: cols).  out3 (n, 3) f64
@@ -510,7 +513,7 @@ int32_t roam_debug_keyframe_append(roam_ctx *ctx, const uint8_t *recv, int32_t w
 int32_t roam_debug_fft2_f64(roam_ctx *ctx, const double *re_in, const double *im_in, int32_t rows, int32_t cols, int32_t inverse,
                             double *re_out, double *im_out);
 #define ROAM_TIME_FFT_FIVE      0   /* the five 2-D transforms of one phase correlation (two real forward, one inverse), transposes included */
-#define ROAM_TIME_DFT_FIVE      1   /* the same five as roam_fmt_rotation's direct DFTs (rows * cols <= 131072) */
+#define ROAM_TIME_DFT_FIVE      1   /* the same five as direct DFTs, a baseline only (rows * cols <= 131072) */
 #define ROAM_TIME_FFT_ROWS      2   /* one row pass: `rows` transforms of length cols, in place */
 #define ROAM_TIME_FFT_TRANSPOSE 3   /* one transpose rows x cols -> cols x rows */
 #define ROAM_TIME_FFT_COLS      4   /* one column pass on the transposed plane: `cols` transforms of length rows, in place */

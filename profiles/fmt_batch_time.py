@@ -1,6 +1,6 @@
 """Per-pair time of the Fourier-Mellin rotation prior at the live shape (400 x 2025, clip 1012, downsample 10), three ways in one
 process: Engine.fmt_rotation on resident pool records (8 records, indices cycling), Context.fmt_rotation_batch from host memory, and
-one Context.fmt_rotation call per pair (the single-pair path with its direct DFTs).  Wall clock around the blocking calls, two warm
+one Context.fmt_rotation call per pair (roam_fmt_rotation: n = 1 of the batched pass, from host memory).  Wall clock around the blocking calls, two warm
 runs, best of three.  The figures of docs/KERNELS.md "Batched rotation prior" come from
 
     python profiles/fmt_batch_time.py --pairs 1024 --host-pairs 256

@@ -1,5 +1,5 @@
-"""Fourier-Mellin registration with the reference's names (reference FMT.py:10-100): the rotation prior (csrc/fmt.hip; batches of
-pairs: csrc/fmt_batch.hip), the translation by phase correlation (csrc/fft.hip), the rotation of an image (csrc/warpaffine.hip) and the chain of the three in one
+"""Fourier-Mellin registration with the reference's names (reference FMT.py:10-100): the rotation prior (csrc/fmt_batch.hip, one pair
+or a batch of pairs in the same pass), the translation by phase correlation (csrc/fft.hip), the rotation of an image (csrc/warpaffine.hip) and the chain of the three in one
 device pass (getTransformUsingFMT, csrc/fmt_register.hip);
 the computation runs on the MI355X.  SURVEY §8f-f4."""
 import math
@@ -25,7 +25,8 @@ def getTranslationUsingPhaseCorrelation(srcImg, targetImg):
 def getRotationUsingFMT(srcPolarImg, targetPolarImg, downsampleFactor: int = FMT_DOWNSAMPLE_FACTOR, maxRangeClipM=FMT_RANGE_CLIP_M):
     """-> (angleRad with R(angleRad) @ src = target, scaling factor, response); polar (not log-polar) float32 images.
     Two 3-D batches of polar images of one shape go through the batched device pass (roam_fmt_rotation_batch_f32) and give three
-    arrays with one entry per pair; argument errors are then ValueError before any device call."""
+    arrays with one entry per pair; argument errors are then ValueError before any device call.  Two 2-D images go through
+    roam_fmt_rotation, which is n = 1 of that pass and refuses what it refuses (RoamError)."""
     assert srcPolarImg.shape == targetPolarImg.shape, "Images need to have the same shape!"
     clip = int(maxRangeClipM / RANGE_RESOLUTION_CART_M) if maxRangeClipM > 0 else 0
     if np.ndim(srcPolarImg) == 3:

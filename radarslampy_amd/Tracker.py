@@ -2,7 +2,8 @@
 track()/getTransform() signatures, return orders and dtypes; the arithmetic runs on the MI355X.
 
 The Fourier-Mellin rotation estimate that track() computes first and returns in slot 3 (Tracker.py:62-63; the reference
-only prints it, RawROAMSystem.py:187-188) runs on the GPU as well (FMT.getRotationUsingFMT, csrc/fmt.hip).
+only prints it, RawROAMSystem.py:187-188) runs on the GPU as well (FMT.getRotationUsingFMT: csrc/fmt_batch.hip and the
+correlation of csrc/fft.hip).
 One documented difference: paramFlags["rejectOutliers"]=False returns an all-ones pruning mask where the reference raises
 NameError (Tracker.py:93-104)."""
 import time

@@ -125,7 +125,7 @@ _SIGS = {
     "roam_engine_set_stage_events": (C.c_int32, [_vp, C.c_int32]),
     "roam_engine_time_kernel": (C.c_int32, [_vp, C.c_char_p, C.c_int32, _P(C.c_float), _P(C.c_double)]),
     "roam_engine_debug_detect": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp]),
-    "roam_fmt_rotation": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
+    "roam_fmt_rotation": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "roam_phase_correlate_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp]),
     "roam_fmt_rotation_batch_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                                 _vp, _vp]),
@@ -298,6 +298,19 @@ def _f32_rows_in_place(a):
     if ok and a.ndim == 3:
         ok = a.strides[0] % 4 == 0 and a.strides[0] >= (a.shape[1] - 1) * a.strides[1] + 4 * a.shape[2]
     return a if ok else np.ascontiguousarray(a, np.float32)
+
+
+def _batch_operands(a, b):
+    """two images or two batches of one shape as the batched entries take them -> (a3, b3, n, rows, cols, row_stride, image_stride),
+    strides in floats: _f32_rows_in_place on each, 2-D promoted to a batch of one"""
+    a, b = _f32_rows_in_place(a), _f32_rows_in_place(b)
+    a3, b3 = (a, b) if a.ndim == 3 else (a[None], b[None])
+    n, rows, cols = a3.shape
+    if a3.strides[0 if n > 1 else 1:] != b3.strides[0 if n > 1 else 1:]:     # one pair of strides describes both operands
+        a3, b3 = np.ascontiguousarray(a3), np.ascontiguousarray(b3)
+    row_stride = a3.strides[1] // 4
+    image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+    return a3, b3, n, rows, cols, row_stride, image_stride
 
 
 _lib = None
@@ -583,13 +596,7 @@ class Context:
         read in place, anything else is made float32-contiguous.  Arguments are checked by fmt_rotation_batch_args before any device
         call."""
         a, b, clip, R = fmt_rotation_batch_args(src, tgt, clip_px, downsample)
-        a, b = _f32_rows_in_place(a), _f32_rows_in_place(b)
-        a3, b3 = (a, b) if a.ndim == 3 else (a[None], b[None])
-        n, rows, cols = a3.shape
-        if a3.strides[0 if n > 1 else 1:] != b3.strides[0 if n > 1 else 1:]:     # one pair of strides describes both operands
-            a3, b3 = np.ascontiguousarray(a3), np.ascontiguousarray(b3)
-        row_stride = a3.strides[1] // 4
-        image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+        a3, b3, n, rows, cols, row_stride, image_stride = _batch_operands(a, b)
         out = np.empty((n, 3), np.float64)
         lp = np.empty((2 * n, int(np.rint(R * np.pi)), R), np.float32) if want_logpolar else None
         self.check(self.lib.roam_fmt_rotation_batch_f32(self.h, _ptr(a3), _ptr(b3), n, rows, cols, row_stride, image_stride, int(clip_px),
@@ -605,13 +612,7 @@ class Context:
         float32 views with unit column stride are read in place, anything else is made float32-contiguous.  Arguments are checked by
         fmt_register_batch_args before any device call."""
         a, b, clip, R, Rc = fmt_register_batch_args(src, tgt, clip_px, downsample, cart_downsample)
-        a, b = _f32_rows_in_place(a), _f32_rows_in_place(b)
-        a3, b3 = (a, b) if a.ndim == 3 else (a[None], b[None])
-        n, rows, cols = a3.shape
-        if a3.strides[0 if n > 1 else 1:] != b3.strides[0 if n > 1 else 1:]:     # one pair of strides describes both operands
-            a3, b3 = np.ascontiguousarray(a3), np.ascontiguousarray(b3)
-        row_stride = a3.strides[1] // 4
-        image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+        a3, b3, n, rows, cols, row_stride, image_stride = _batch_operands(a, b)
         out = np.empty((n, 6), np.float64)
         imgs = np.empty((2 * n, 2 * Rc, 2 * Rc), np.float32) if want_images else None
         self.check(self.lib.roam_fmt_register_batch_f32(self.h, _ptr(a3), _ptr(b3), n, rows, cols, row_stride, image_stride, int(clip_px),
@@ -623,14 +624,8 @@ class Context:
         (roam_phase_correlate_f32).  Two 2-D images -> ((dx, dy), response); two 3-D batches of one shape -> (dxdy (n, 2),
         response (n,)).  float32 views with unit column stride are read in place, anything else is made float32-contiguous."""
         a, b = phase_correlate_args(src, tgt)
-        a, b = _f32_rows_in_place(a), _f32_rows_in_place(b)
         batch = a.ndim == 3
-        a3, b3 = (a, b) if batch else (a[None], b[None])
-        n, rows, cols = a3.shape
-        if a3.strides[0 if n > 1 else 1:] != b3.strides[0 if n > 1 else 1:]:     # one pair of strides describes both operands
-            a3, b3 = np.ascontiguousarray(a3), np.ascontiguousarray(b3)
-        row_stride = a3.strides[1] // 4
-        image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+        a3, b3, n, rows, cols, row_stride, image_stride = _batch_operands(a, b)
         dxdy = np.empty((n, 2), np.float64)
         resp = np.empty(n, np.float64)
         self.check(self.lib.roam_phase_correlate_f32(self.h, _ptr(a3), _ptr(b3), n, rows, cols, row_stride, image_stride,

@@ -12,8 +12,9 @@
 //             first use.  A butterfly's twiddle index r k n / (Ns R) is an exact integer below n: no angle is reduced on the device.
 //   inverse:  unscaled (cv2.idft without DFT_SCALE) as swap(FFT(swap(x))), swap = exchange of real and imaginary part: the launcher
 //             exchanges the plane pointers, the kernel is the forward one.
-// The batched rotation prior (roam_fmt_rotation_batch_f32, roam_engine_fmt_rotation) runs the same correlation on planes that the
-// kernels of fmt_batch.hip fill: its driver roam_fmt_batch_run is here because the row pass and the transpose are local to this unit.
+// The rotation prior (roam_fmt_rotation, roam_fmt_rotation_batch_f32, roam_engine_fmt_rotation) runs the same correlation on planes that
+// the kernels of fmt_batch.hip fill: its driver roam_fmt_batch_run is here because the row pass and the transpose are local to this unit.
+// roam_fmt_rotation is n = 1 of it.
 // The registration (roam_fmt_register_batch_f32, roam_engine_fmt_register) adds a second correlation, on the Cartesian images that the
 // kernels of fmt_register.hip make and turn by the angle of the first: roam_fmt_register_run.
 #include "cvmap.h"
@@ -264,6 +265,17 @@ __global__ __launch_bounds__(256) void pc_window_kernel(const float *__restrict_
     out[((int64_t)b * M + y) * N + x] = val;
 }
 
+// normalised cross-power spectrum: mulSpectrums(F1, F2, conjB) then divSpectrums by its magnitude: P |P| / (|P|^2 + FLT_EPSILON)
+static __global__ void fmt_cross_power_kernel(const double *__restrict__ r1, const double *__restrict__ i1, const double *__restrict__ r2,
+                                              const double *__restrict__ i2, int n, double *__restrict__ cr, double *__restrict__ ci)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const double pr = r1[k] * r2[k] + i1[k] * i2[k], pi = i1[k] * r2[k] - r1[k] * i2[k];
+    const double mag = sqrt(pr * pr + pi * pi), den = mag * mag + 1.1920928955078125e-07;
+    cr[k] = pr * mag / den; ci[k] = pi * mag / den;
+}
+
 // np.fft.fftshift: shifted[i] = plane[(i + n - n / 2) mod n]
 __device__ __forceinline__ double pc_shifted(const double *__restrict__ c, int M, int N, int y, int x)
 {
@@ -342,6 +354,25 @@ static bool fft_smooth(int n)
     return fft_plan(n, &p);
 }
 
+// cv2.getOptimalDFTSize: the smallest 2^a 3^b 5^c >= n
+static int optimal_dft_size(int n)
+{
+    int best = 0;
+    for (long p2 = 1; p2 < 2L * n; p2 *= 2)
+        for (long p3 = p2; p3 < 2L * n; p3 *= 3)
+            for (long p5 = p3; p5 < 2L * n; p5 *= 5)
+                if (p5 >= n && (best == 0 || p5 < best)) best = (int)p5;
+    return best;
+}
+
+// utils.normalize_angles: (th + pi) % (2 pi) - pi (Python modulo)
+static double normalize_angle(double th)
+{
+    th = fmod(th + M_PI, 2.0 * M_PI);
+    if (th < 0) th += 2.0 * M_PI;
+    return th - M_PI;
+}
+
 // cv2.createHanningWindow's float64 factor per row or column of a side of n
 void roam_hanning_factors(int n, double *w)
 {
@@ -400,7 +431,9 @@ static int32_t pc_correlate(roam_ctx *ctx, int nb, int M, int N, double *base, c
         FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, p.F[k][0], p.F[k][1]));
         FFT_TRY(fft_rows(ctx, p.F[k][0], p.F[k][1], p.F[k][0], p.F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
     }
-    HIP_TRY(ctx, launch_fmt_cross_power(st, p.F[0][0], p.F[0][1], p.F[1][0], p.F[1][1], (int)pl, tr, ti));
+    hipLaunchKernelGGL(fmt_cross_power_kernel, dim3((unsigned)((pl + 255) / 256)), dim3(256), 0, st, p.F[0][0], p.F[0][1], p.F[1][0], p.F[1][1],
+                       (int)pl, tr, ti);
+    HIP_TRY(ctx, hipGetLastError());
     FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
     FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, p.F[0][0], p.F[0][1]));
     FFT_TRY(fft_rows(ctx, p.F[0][0], p.F[0][1], a, nullptr, (int64_t)nb * M, N, true));                      // real part only
@@ -530,12 +563,23 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
                                         hipMemcpyDeviceToHost, st));
         }
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        for (int i = 0; i < nb; i++) {                       // the final arithmetic of roam_fmt_rotation
-            out3[3 * (b0 + i)] = roam_normalize_angle(-o[3 * i + 1] * 2.0 * M_PI / (double)sz);
+        for (int i = 0; i < nb; i++) {                       // FMT.py:84-90: the shifts as an angle and a scale
+            out3[3 * (b0 + i)] = normalize_angle(-o[3 * i + 1] * 2.0 * M_PI / (double)sz);
             out3[3 * (b0 + i) + 1] = pow(log_base, o[3 * i]);
             out3[3 * (b0 + i) + 2] = o[3 * i + 2];
         }
     }
+    return ROAM_OK;
+}
+
+// what the host entries of the rotation prior check alike: the image size and the downsampling, then clip = the range bins kept
+// (clip_px <= 0 or >= cols: all of them) and R = clip / downsample, the columns after the resize
+static int32_t fmt_clip_radius(roam_ctx *ctx, int rows, int cols, int clip_px, int downsample, int *clip, int *R)
+{
+    ARG_CHECK(ctx, rows >= 8 && rows <= 16384 && cols >= 2 && downsample >= 1);
+    *clip = (clip_px > 0 && clip_px < cols) ? clip_px : cols;
+    *R = *clip / downsample;
+    ARG_CHECK(ctx, *R >= ROAM_FMT_MIN_R && *R <= ROAM_FMT_MAX_R);
     return ROAM_OK;
 }
 
@@ -546,15 +590,33 @@ extern "C" int32_t roam_fmt_rotation_batch_f32(roam_ctx *ctx, const float *src, 
     if (!ctx) return ROAM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ARG_CHECK(ctx, src && tgt && out3 && n >= 1);
-    ARG_CHECK(ctx, rows >= 8 && rows <= 16384 && cols >= 2 && downsample >= 1);
+    int clip, R;
+    FFT_TRY(fmt_clip_radius(ctx, rows, cols, clip_px, downsample, &clip, &R));
     ARG_CHECK(ctx, row_stride >= cols && (n == 1 || image_stride >= (int64_t)(rows - 1) * row_stride + cols));
-    const int clip = (clip_px > 0 && clip_px < cols) ? clip_px : cols;
-    const int R = clip / downsample;
-    ARG_CHECK(ctx, R >= ROAM_FMT_MIN_R && R <= ROAM_FMT_MAX_R);
     FmtBatchIn in;
     in.host_src = src; in.host_tgt = tgt; in.row_stride = row_stride; in.image_stride = n == 1 ? (int64_t)rows * row_stride : image_stride;
     in.cols = cols;
     return roam_fmt_batch_run(ctx, in, n, rows, clip, R, out3, logpolar_out);
+}
+
+// one contiguous pair: n = 1 of the batch call
+extern "C" int32_t roam_fmt_rotation(roam_ctx *ctx, const float *src_polar, const float *tgt_polar, int32_t rows, int32_t cols,
+                                     int32_t clip_px, int32_t downsample, double *angle_rad, double *scale, double *response)
+{
+    if (!ctx) return ROAM_E_ARG;
+    ARG_CHECK(ctx, src_polar && tgt_polar && angle_rad);
+    int clip, R;
+    FFT_TRY(fmt_clip_radius(ctx, rows, cols, clip_px, downsample, &clip, &R));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    FmtBatchIn in;
+    in.host_src = src_polar; in.host_tgt = tgt_polar; in.row_stride = cols; in.image_stride = (int64_t)rows * cols;
+    in.cols = cols;
+    double out3[3];
+    FFT_TRY(roam_fmt_batch_run(ctx, in, 1, rows, clip, R, out3, nullptr));
+    *angle_rad = out3[0];
+    if (scale) *scale = out3[1];
+    if (response) *response = out3[2];
+    return ROAM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ batched registration
@@ -653,11 +715,11 @@ extern "C" int32_t roam_fmt_register_batch_f32(roam_ctx *ctx, const float *src, 
     if (!ctx) return ROAM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ARG_CHECK(ctx, src && tgt && out6 && n >= 1);
-    ARG_CHECK(ctx, rows >= 8 && rows <= 16384 && cols >= 2 && cols <= 16384 && downsample >= 1 && cart_downsample >= 1);
+    int clip, R;
+    FFT_TRY(fmt_clip_radius(ctx, rows, cols, clip_px, downsample, &clip, &R));
+    ARG_CHECK(ctx, cols <= 16384 && cart_downsample >= 1);
     ARG_CHECK(ctx, row_stride >= cols && (n == 1 || image_stride >= (int64_t)(rows - 1) * row_stride + cols));
-    const int clip = (clip_px > 0 && clip_px < cols) ? clip_px : cols;
-    const int R = clip / downsample, Rc = cols / cart_downsample;
-    ARG_CHECK(ctx, R >= ROAM_FMT_MIN_R && R <= ROAM_FMT_MAX_R);
+    const int Rc = cols / cart_downsample;
     ARG_CHECK(ctx, 2 * Rc >= 2 && 2 * Rc <= FFT_MAX_N);
     FmtBatchIn in;
     in.host_src = src; in.host_tgt = tgt; in.row_stride = row_stride; in.image_stride = n == 1 ? (int64_t)rows * row_stride : image_stride;
@@ -666,6 +728,51 @@ extern "C" int32_t roam_fmt_register_batch_f32(roam_ctx *ctx, const float *src, 
 }
 
 // ------------------------------------------------------------------------------------------------ test / measurement entries
+// The direct 2-D DFT (float64 accumulation, twiddles from sincospi on (k mod n) / n), O(M N (M + N)): the baseline roam_time_fft2 times
+// the FFT against (ROAM_TIME_DFT_FIVE).  No product path calls these three.
+// along x: out[y][v] = sum_x in[y][x] exp(sign 2 pi i v x / N); in real (im_in == null) or complex
+static __global__ void fmt_dft_x_kernel(const double *__restrict__ re_in, const double *__restrict__ im_in, int M, int N, double sign,
+                                        double *__restrict__ re_out, double *__restrict__ im_out)
+{
+    const int v = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (v >= N) return;
+    double ar = 0, ai = 0;
+    for (int x = 0; x < N; x++) {
+        double s, c;
+        sincospi(sign * 2.0 * (double)((v * x) % N) / (double)N, &s, &c);
+        const double xr = re_in[(int64_t)y * N + x], xi = im_in ? im_in[(int64_t)y * N + x] : 0.0;
+        ar += xr * c - xi * s; ai += xr * s + xi * c;
+    }
+    re_out[(int64_t)y * N + v] = ar; im_out[(int64_t)y * N + v] = ai;
+}
+
+// along y: out[u][v] = sum_y in[y][v] exp(sign 2 pi i u y / M); im_out may be null
+static __global__ void fmt_dft_y_kernel(const double *__restrict__ re_in, const double *__restrict__ im_in, int M, int N, double sign,
+                                        double *__restrict__ re_out, double *__restrict__ im_out)
+{
+    const int v = blockIdx.x * blockDim.x + threadIdx.x, u = blockIdx.y;
+    if (v >= N) return;
+    double ar = 0, ai = 0;
+    for (int y = 0; y < M; y++) {
+        double s, c;
+        sincospi(sign * 2.0 * (double)((u * y) % M) / (double)M, &s, &c);
+        const double xr = re_in[(int64_t)y * N + v], xi = im_in[(int64_t)y * N + v];
+        ar += xr * c - xi * s; ai += xr * s + xi * c;
+    }
+    re_out[(int64_t)u * N + v] = ar;
+    if (im_out) im_out[(int64_t)u * N + v] = ai;
+}
+
+// fmt_dft_x_kernel into tmp, then fmt_dft_y_kernel
+static hipError_t launch_fmt_dft2(hipStream_t st, const double *re_in, const double *im_in, int M, int N, double sign, double *tmp_re,
+                                  double *tmp_im, double *re_out, double *im_out)
+{
+    const dim3 gmn((N + 63) / 64, M);
+    hipLaunchKernelGGL(fmt_dft_x_kernel, gmn, dim3(64), 0, st, re_in, im_in, M, N, sign, tmp_re, tmp_im);
+    hipLaunchKernelGGL(fmt_dft_y_kernel, gmn, dim3(64), 0, st, tmp_re, tmp_im, M, N, sign, re_out, im_out);
+    return hipGetLastError();
+}
+
 extern "C" int32_t roam_debug_fft2_f64(roam_ctx *ctx, const double *re_in, const double *im_in, int32_t rows, int32_t cols, int32_t inverse,
                                        double *re_out, double *im_out)
 {

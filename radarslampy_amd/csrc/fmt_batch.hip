@@ -1,12 +1,12 @@
-// Batched front end of the Fourier-Mellin rotation prior (FMT.getRotationUsingFMT, reference FMT.py:36-90) for 2 nb images at once,
-// the image in grid.z: the first nb are the sources of a chunk of pairs, the next nb their targets.
+// Front end of the Fourier-Mellin rotation prior (FMT.getRotationUsingFMT, reference FMT.py:36-90), the only one: for 2 nb images at
+// once (a single pair is nb = 1), the image in grid.z: the first nb are the sources of a chunk of pairs, the next nb their targets.
 //   fmtb_resize_kernel    cv2.resize(img[:, :clip], (R, rows)), INTER_LINEAR, R = clip / downsample.  The source is a float32 polar
 //                         image (row and image stride) or a u8 record read in place (float(u8) / 255.0f in float32,
 //                         extractDataFromRadarImage's arithmetic; the engine's pool through a list of record indices).
 //   fmtb_cart_kernel      inverse linear warpPolar to 2R x 2R, centre (R, R), maxRadius R (convertPolarImgToLogPolar, parseData.py:138-160)
 //   fmtb_logpolar_kernel  forward semilog warpPolar to round(R) x round(pi R), [the image before the window -> lp_out,] times the
 //                         cv2.createHanningWindow factor, rounded to float32, zero-padded into the float64 M x N plane of the FFT
-// The maps, the remap and the window product are cvmap.h's, the same definitions warppolar.hip and fmt.hip call; like warppolar.hip the
+// The maps, the remap and the window product are cvmap.h's, the same definitions warppolar.hip calls; like warppolar.hip the
 // radius, cos / sin and window tables come from the host's libm, so that the log-polar image equals the oracle's bit for bit.
 // The correlation behind it is fft.hip's (roam_fmt_batch_run): these kernels only fill its planes.  No atomics: every output element
 // has one writer, and an image's result does not depend on its place in the batch.

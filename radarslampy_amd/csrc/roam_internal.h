@@ -187,14 +187,6 @@ int roam_comm_rank(const roam_ctx *ctx);
 int roam_comm_world(const roam_ctx *ctx);
 int32_t roam_comm_allgather_bytes(roam_ctx *ctx, const void *send, void *recv, size_t bytes, hipStream_t st);
 
-// fmt.hip kernels for fft.hip: the normalised cross-power spectrum of n bins (fmt_cross_power_kernel), and one direct 2-D DFT
-// (fmt_dft_x_kernel into tmp, then fmt_dft_y_kernel; im_in / im_out may be null) for timing the FFT against it
-hipError_t launch_fmt_cross_power(hipStream_t st, const double *r1, const double *i1, const double *r2, const double *i2, int n, double *cr,
-                                  double *ci);
-hipError_t launch_fmt_dft2(hipStream_t st, const double *re_in, const double *im_in, int M, int N, double sign, double *tmp_re, double *tmp_im,
-                           double *re_out, double *im_out);
-// fmt.hip: cv2.getOptimalDFTSize: the smallest 2^a 3^b 5^c >= n
-int optimal_dft_size(int n);
 // fft.hip: free the context's twiddle tables
 void roam_fft_release(roam_ctx *ctx);
 
@@ -208,8 +200,6 @@ void roam_warp_polar_tables(int dw, int dh, double max_radius, bool semilog, flo
 // copies as the layout allows
 hipError_t roam_upload_packed_f32(hipStream_t st, float *dst, const float *src, int n, int width, int rows, int64_t row_stride,
                                   int64_t image_stride);
-// fmt.hip: utils.normalize_angles, (th + pi) % (2 pi) - pi with Python's modulo
-double roam_normalize_angle(double th);
 
 // fmt_batch.hip: the batched front end of the rotation prior.  Image z of a launch reads base + (index ? index[z] : z) * image_stride
 // (+ payload_off for u8 records); strides in elements (floats or bytes); base and index are device pointers

@@ -5,7 +5,7 @@ shapes, four pairs each, and the oracle's results for them, computed once per pr
   a     400 x 2025                      1012 / 10           101  317 x 101   320 x 108    the live shape
   b     16 x 40, random float32         none / 2            20   63 x 20     64 x 20      short rows, repeated angular wrap
   c     399 x 497, non-contiguous view  497 / 7             71   223 x 71    225 x 72     odd sizes, strides
-  d     case a's images                 1012 / 2            506  1590 x 506  1600 x 512   a size the direct DFTs were never meant for
+  d     case a's images                 1012 / 2            506  1590 x 506  1600 x 512   a large plane: only the FFT makes it practical
 
 The pairs of a (and d) are those of test_fmt_rotation_matches_oracle: (p0, p0), (p0, p1), (p0, roll(p0, 7)), (p1, roll(p0, -31)) on
 synth.make_sequence(3, 2, n_movers=6); b and c follow the same pattern on their own images and row shifts."""

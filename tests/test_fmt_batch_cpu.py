@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C_TYPES = {"roam_ctx *": C.c_void_p, "const float *": C.c_void_p, "float *": C.c_void_p, "double *": C.c_void_p,
            "const int32_t *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64}
 ENTRIES = {
+    "roam_fmt_rotation": ["ctx", "src_polar", "tgt_polar", "rows", "cols", "clip_px", "downsample", "angle_rad", "scale", "response"],
     "roam_fmt_rotation_batch_f32": ["ctx", "src", "tgt", "n", "rows", "cols", "row_stride", "image_stride", "clip_px", "downsample", "out3",
                                     "logpolar_out"],
     "roam_engine_fmt_rotation": ["ctx", "n", "prev_pool_idx", "curr_pool_idx", "clip_px", "downsample", "out3"],

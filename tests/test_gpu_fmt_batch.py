@@ -47,8 +47,8 @@ def test_batch_matches_oracle_and_logpolar_is_exact(ctx, case):
         _check(f"case {case} pair {i}", out[i], want["out3"][i])
     assert np.array_equal(ctx.fmt_rotation_batch(A, B, clip_px=clip_px, downsample=ds), out)     # the images are optional
     if case == "a":
-        for i in range(4):
-            _check(f"case a pair {i} against the single-pair path", out[i], ctx.fmt_rotation(A[i], B[i]))
+        for i in range(4):                                                    # the single-pair entry: n = 1 of the same pass
+            assert np.array_equal(out[i], ctx.fmt_rotation(A[i], B[i], clip_px=clip_px, downsample=ds))
         # known answer: the scan turned by k azimuth rows
         assert abs(out[2, 0] + 7 * 2 * np.pi / 400) < 5e-3
     if case == "c":                                                           # the strided view and its contiguous copy
@@ -56,7 +56,7 @@ def test_batch_matches_oracle_and_logpolar_is_exact(ctx, case):
 
 
 def test_large_plane_through_the_fft(ctx):
-    """case d: 1012 / 2 -> a 1600 x 512 plane, 10^10 sincospi calls per transform for the direct DFTs"""
+    """case d: 1012 / 2 -> a 1600 x 512 plane, a size only the FFT makes practical"""
     clip_px, ds, R, _, _ = cases.CASES["d"]
     A, B = cases.batch("d")
     out = ctx.fmt_rotation_batch(A, B, clip_px=clip_px, downsample=ds)
@@ -74,6 +74,44 @@ def test_result_does_not_depend_on_the_batch(ctx, case):
         o1, l1 = ctx.fmt_rotation_batch(A[i], B[i], clip_px=clip_px, downsample=ds, want_logpolar=True)
         assert o1.shape == (1, 3) and np.array_equal(o1[0], out[i]), (case, i, o1, out[i])
         assert np.array_equal(l1[0], lp[i]) and np.array_equal(l1[1], lp[4 + i])
+
+
+def _single_vs_batch_pairs():
+    rng = np.random.default_rng(11)
+    yield "b", cases.batch("b"), cases.CASES["b"][:2]
+    yield "c, contiguous", tuple(np.ascontiguousarray(x) for x in cases.batch("c")), cases.CASES["c"][:2]
+    # R = 4 = ROAM_FMT_MIN_R, rows at their minimum; no oracle here: nobody has checked that this pair's correlation peak is unique
+    yield "8 x 8", (rng.random((1, 8, 8), dtype=np.float32), rng.random((1, 8, 8), dtype=np.float32)), (0, 2)
+
+
+def test_single_pair_entry_is_the_batch_of_one(ctx):
+    """roam_fmt_rotation against roam_fmt_rotation_batch_f32 at n = 1 on the same pair, bit for bit (case a: above)"""
+    for tag, (A, B), (clip_px, ds) in _single_vs_batch_pairs():
+        i = min(1, len(A) - 1)
+        want = ctx.fmt_rotation_batch(A[i], B[i], clip_px=clip_px, downsample=ds)
+        got = ctx.fmt_rotation(A[i], B[i], clip_px=clip_px, downsample=ds)
+        print(f"{tag}: single {got}, batch of one {tuple(want[0])}")
+        assert want.shape == (1, 3) and np.array_equal(want[0], got), (tag, got, want)
+
+
+def test_single_pair_entry_argument_errors_on_the_device_side(ctx):
+    """the C entry's own refusals, before any device call; scale and response are optional"""
+    import ctypes as C
+    from radarslampy_amd import _ffi
+    a = np.random.default_rng(12).random((8, 8), dtype=np.float32)
+    ang = C.c_double(0)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    call = lambda *args: ctx.lib.roam_fmt_rotation(ctx.h, *args)
+    assert call(p(a), p(a), 8, 8, 0, 2, C.byref(ang), None, None) == _ffi.ROAM_OK
+    assert call(None, p(a), 8, 8, 0, 2, C.byref(ang), None, None) == _ffi.ROAM_E_ARG
+    assert call(p(a), None, 8, 8, 0, 2, C.byref(ang), None, None) == _ffi.ROAM_E_ARG
+    assert call(p(a), p(a), 8, 8, 0, 2, None, None, None) == _ffi.ROAM_E_ARG
+    assert call(p(a), p(a), 7, 8, 0, 2, C.byref(ang), None, None) == _ffi.ROAM_E_ARG
+    assert call(p(a), p(a), 8, 1, 0, 1, C.byref(ang), None, None) == _ffi.ROAM_E_ARG
+    assert call(p(a), p(a), 8, 8, 0, 0, C.byref(ang), None, None) == _ffi.ROAM_E_ARG
+    assert call(p(a), p(a), 8, 8, 6, 2, C.byref(ang), None, None) == _ffi.ROAM_E_ARG            # R = 3
+    assert call(p(a), p(a), 8, 1304, 0, 1, C.byref(ang), None, None) == _ffi.ROAM_E_ARG         # R = 1304: refused before a is read
+    assert b"bad argument" in ctx.lib.roam_last_error(ctx.h)
 
 
 def test_chunked_batch_equals_its_originals(ctx, monkeypatch):
@@ -108,7 +146,7 @@ def test_drop_in_name(ctx):
     assert ang.shape == sc.shape == resp.shape == (4,)
     assert np.array_equal(ang, out[:, 0]) and np.array_equal(sc, out[:, 1]) and np.array_equal(resp, out[:, 2])
     assert np.array_equal(out, ctx.fmt_rotation_batch(A, B))
-    assert getRotationUsingFMT(A[1], B[1]) == ctx.fmt_rotation(A[1], B[1])    # 2-D input: the single-pair path, as before
+    assert getRotationUsingFMT(A[1], B[1]) == ctx.fmt_rotation(A[1], B[1])    # 2-D input: the single-pair entry, as before
 
 
 ENGINE_CASES = [((2025, 400, 3779, 11), 1012, 10), ((497, 399, 504, 5), 497, 7)]

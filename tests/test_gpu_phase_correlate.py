@@ -167,7 +167,7 @@ def test_large_batch_is_chunked_bit_for_bit(ctx, to_cart):
 @pytest.mark.timeout(600)
 def test_fft_is_not_slower_than_the_direct_dft(ctx):
     """the five 2-D transforms of one phase correlation at the rotation prior's size (320 x 108: 108 rows of 320) through the FFT and
-    through roam_fmt_rotation's direct DFTs, HIP events after warm runs, best of three; and the figures docs/KERNELS.md records at
+    through the direct DFTs the single-pair path used until this change, HIP events after warm runs, best of three; and the figures docs/KERNELS.md records at
     2025 x 2025 and 2048 x 2048 (printed, not asserted: there is no earlier number to hold them to)"""
     from radarslampy_amd import _ffi
     modes = (("five transforms", _ffi.TIME_FFT_FIVE), ("row pass", _ffi.TIME_FFT_ROWS), ("transpose", _ffi.TIME_FFT_TRANSPOSE),

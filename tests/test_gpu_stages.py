@@ -401,7 +401,7 @@ def test_get_features_matches_oracle(ctx, cart_pair):
 
 # ------------------------------------------------------------------ f4 Fourier-Mellin rotation prior
 def test_fmt_rotation_matches_oracle(ctx):
-    """roam_fmt_rotation (resize, two warpPolar steps, windowed phase correlation by direct DFTs) vs the oracle's numpy
+    """roam_fmt_rotation (resize, two warpPolar steps, windowed phase correlation: n = 1 of the batched pass) vs the oracle's numpy
     restatement of FMT.getRotationUsingFMT: 1e-5 rad; and through the reference-named wrappers (FMT, Tracker.track slot 3)"""
     from radarslampy_amd import synth
     from radarslampy_amd.FMT import getRotationUsingFMT
