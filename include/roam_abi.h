@@ -151,6 +151,20 @@ int32_t roam_klt_track_u8(roam_ctx *ctx, const uint8_t *prev_img, const uint8_t 
 int32_t roam_klt_track_f32(roam_ctx *ctx, const float *prev_img, const float *next_img,
                            int32_t w, int32_t h, const float *pts, int32_t K,
                            float *next_pts, uint8_t *status, float *err);
+/* The same with cv2's OPTFLOW_USE_INITIAL_FLOW: init_pts (K,2) f32 is where the search for each feature STARTS in next_img (a motion
+ * prior).  OpenCV's rule: only the top pyramid level differs - there the start is init_pts * 2^-maxLevel instead of pts * 2^-maxLevel;
+ * the window and its derivatives are taken at pts as before, lower levels start at twice the level above, status and err follow
+ * the same rules.  init_pts == NULL is roam_klt_track_u8 / _f32, bit for bit; init_pts == pts gives those bits as well.
+ * ROAM_E_ARG before any device work: a guess coordinate that is not finite or whose magnitude exceeds ROAM_KLT_MAX_GUESS px
+ * (2^20, the bound of roam_warp_affine_f32's coordinates: the tracker's float -> int conversions of the window origin stay
+ * defined far beyond any image the pyramid accepts). */
+#define ROAM_KLT_MAX_GUESS 1048576.0f
+int32_t roam_klt_track_u8_flow(roam_ctx *ctx, const uint8_t *prev_img, const uint8_t *next_img,
+                               int32_t w, int32_t h, const float *pts, const float *init_pts, int32_t K,
+                               float *next_pts, uint8_t *status, float *err);
+int32_t roam_klt_track_f32_flow(roam_ctx *ctx, const float *prev_img, const float *next_img,
+                                int32_t w, int32_t h, const float *pts, const float *init_pts, int32_t K,
+                                float *next_pts, uint8_t *status, float *err);
 /* pyrDown (5x5 Gaussian, REFLECT_101): src w x h -> dst ((w+1)/2 x (h+1)/2) */
 int32_t roam_pyr_down_u8(roam_ctx *ctx, const uint8_t *src, int32_t w, int32_t h, uint8_t *dst);
 
@@ -348,6 +362,19 @@ int32_t roam_engine_init_lane(roam_ctx *ctx, int32_t lane, int32_t pool_idx, con
  * synchronised execution; roam_engine_results and the other blocking accessors return the state
  * after the LAST enqueued step.  The host may run at most three steps ahead of the device. */
 int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx);
+/* Motion prior of the NEXT roam_engine_step only (consumed by that step, then gone): affine (lanes, 6) f32, row-major
+ * [a00 a01 a02 a10 a11 a12] per lane - the predicted position in the lane's current full-size Cartesian image, in pixels, of a
+ * feature at p = (x, y) in the previous one: (a00 x + a01 y) + a02, (a10 x + a11 y) + a12, evaluated on the device in float32 with every
+ * operation rounded.  The lane's tracker starts its search there (roam_klt_track_*_flow's rule) instead of at p.  use (lanes) u8,
+ * may be NULL = every lane: lanes with use[i] == 0 run unseeded, bit for bit.  affine == NULL withdraws a prior that no step has
+ * consumed yet.  A lane that starts a new sequence on that step has no features and ignores its prior.  The call does not touch the
+ * device: the values are staged in pinned memory of the engine (a ring of four slots; a slot is reused only after the tracker
+ * of the step that read it has finished, which the step pipeline's own three-step limit already guarantees) and roam_engine_step
+ * copies them asynchronously on the compute stream, ahead of its tracker.  ROAM_E_ARG: an entry that is not finite, a linear
+ * coefficient (a00 a01 a10 a11) above ROAM_PRIOR_MAX_LINEAR in magnitude, a translation (a02 a12) above ROAM_KLT_MAX_GUESS px - with
+ * features inside a 16384 px image the start then stays below 2^22 px.  ROAM_E_STATE: no engine. */
+#define ROAM_PRIOR_MAX_LINEAR 64.0f
+int32_t roam_engine_set_motion_prior(roam_ctx *ctx, const float *affine, const uint8_t *use);
 /* scan_idx[i] | ROAM_STEP_NEW_SEQUENCE: lane i starts a NEW sequence on this scan - its features are dropped before the pair,
  * nothing is tracked, the pose stays, and the first-frame detection (appendNewFeatures(prevImgCart, empty),
  * RawROAMSystem.py:150) runs on this scan inside the step (needs cfg.retrack_on_device).  A stream of finite sequences

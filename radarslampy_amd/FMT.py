@@ -85,3 +85,41 @@ def rotateImg(image, angle_degrees):
     M = getRotationMatrix2D(center, ang, 1.0) if ang.ndim == 0 else np.stack([getRotationMatrix2D(center, t, 1.0) for t in ang])
     _ffi.warp_affine_args(img, M, (w, h))
     return _ffi.default_context().warp_affine_f32(img, M, (w, h))
+
+
+def flowPriorFromFMT(angleRad, dxdy, cartDownsampleFactor: int = FMT_CART_DOWNSAMPLE_FACTOR, trackDownsampleFactor: int = 2,
+                     cols: int = 2025):
+    """A registration result (getTransformUsingFMT, Engine.fmt_register) as the tracker's motion prior -> float32 (2, 3): the affine
+    map from a feature's pixel position in the previous Cartesian image at trackDownsampleFactor to its predicted position in the
+    current one (getTrackedPointsKLT's initialFlow through tests' apply_affine order, Engine.set_motion_prior).  Arrays of n angles
+    and (n, 2) translations give (n, 2, 3).  Host code only.
+
+    On the registration's grid the chain is: srcRot = warpAffine(src, M), M = getRotationMatrix2D((w / 2, h / 2), degrees(angleRad),
+    1) - a feature at p in src lies at M p in srcRot - then phaseCorrelate(srcRot, target) = (dx, dy), which is the shift that
+    takes srcRot to target: the feature lies at M p + (dx, dy) in the target.  (PARITY.md's "minus the ego motion": the scene moves
+    against the sensor.)  The grids: parseData.convertPolarImageToCartesian at factor f makes a 2 R_f x 2 R_f image, R_f = cols // f,
+    centred on (R_f, R_f), in which one pixel spans cols / R_f range bins.  A pixel q of the registration's grid is therefore pixel
+    s q of the tracker's, s = R_track / R_reg = (cols // trackDownsampleFactor) / (cols // cartDownsampleFactor) - 1012 / 101 =
+    10.0198 for 2025 bins at 2 and 20 (a 2024-px image against a 202-px one), not the integer ratio 10 - and the prior is
+    [ M_linear | s (M_translation + (dx, dy)) ]: the same rotation about the tracker image's own centre (R_track, R_track), and
+    the translation scaled."""
+    ang = np.asarray(angleRad, np.float64)
+    d = np.asarray(dxdy, np.float64)
+    if ang.ndim > 1 or d.shape != ang.shape + (2,):
+        raise ValueError(f"flowPriorFromFMT: one angle and (dx, dy), or n angles and (n, 2) translations, not {ang.shape} and {d.shape}")
+    if int(cartDownsampleFactor) < 1 or int(trackDownsampleFactor) < 1 or int(cols) // int(cartDownsampleFactor) < 1 \
+            or int(cols) // int(trackDownsampleFactor) < 1:
+        raise ValueError("flowPriorFromFMT: downsample factors >= 1 that leave at least one pixel of radius")
+    if not (np.isfinite(ang).all() and np.isfinite(d).all()):
+        raise ValueError("flowPriorFromFMT: the registration result is not finite")
+    r_reg, r_trk = int(cols) // int(cartDownsampleFactor), int(cols) // int(trackDownsampleFactor)
+    s = r_trk / r_reg
+
+    def one(a, t):
+        M = getRotationMatrix2D((2 * r_reg / 2, 2 * r_reg / 2), math.degrees(float(a)), 1.0)
+        M[:, 2] = s * (M[:, 2] + t)
+        return M.astype(np.float32)
+
+    if ang.ndim == 0:
+        return one(ang, d)
+    return np.stack([one(a, t) for a, t in zip(ang, d)]) if len(ang) else np.zeros((0, 2, 3), np.float32)

@@ -83,6 +83,8 @@ _SIGS = {
     "roam_time_warp_affine": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _P(C.c_float)]),
     "roam_klt_track_u8": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "roam_klt_track_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    "roam_klt_track_u8_flow": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    "roam_klt_track_f32_flow": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
     "roam_pyr_down_u8": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
     "roam_reject_outliers": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_double, C.c_int64, _vp, _P(C.c_int32), _P(C.c_int32), _vp]),
     "roam_time_reject_outliers": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_int32, _P(C.c_float), _P(C.c_float),
@@ -106,6 +108,7 @@ _SIGS = {
     "roam_engine_step_results": (C.c_int32, [_vp, C.c_int64, _P(LaneResult), C.c_int32]),
     "roam_engine_steps_enqueued": (C.c_int32, [_vp, _P(C.c_int64)]),
     "roam_engine_set_retrack": (C.c_int32, [_vp, C.c_int32]),
+    "roam_engine_set_motion_prior": (C.c_int32, [_vp, _vp, _vp]),
     "roam_engine_init_lane_detect": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp]),
     "roam_engine_init_lanes_detect": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_engine_lane_features": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, _P(C.c_int32)]),
@@ -290,6 +293,48 @@ def warp_affine_args(src, M, dsize_wh, inverse_map=False):
             raise ValueError(f"warp_affine_f32: matrix {k} maps a corner of the output to source coordinate {worst:g} px; the "
                              f"fixed-point coordinates hold magnitudes below 2^20 px")
     return a, m, dw, dh
+
+
+KLT_MAX_GUESS = float(1 << 20)          # ROAM_KLT_MAX_GUESS
+PRIOR_MAX_LINEAR = 64.0                 # ROAM_PRIOR_MAX_LINEAR
+
+
+def klt_flow_args(pts, init_pts):
+    """The argument checks of Context.klt_track's initial flow, made before any device call -> (pts (K, 2) float32, init_pts (K, 2)
+    float32 or None).  ValueError: init_pts whose shape is not that of pts, a guess that is not finite, or one beyond
+    KLT_MAX_GUESS = 2^20 px in magnitude (what roam_klt_track_*_flow refuse)."""
+    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+    if init_pts is None:
+        return pts, None
+    g = np.asarray(init_pts)
+    if g.shape != pts.shape:
+        raise ValueError(f"klt_track: init_pts of shape {pts.shape} like pts, not {g.shape}")
+    g = np.ascontiguousarray(g, np.float32)
+    if not np.isfinite(g).all():
+        raise ValueError("klt_track: init_pts is not finite")
+    if g.size and float(np.abs(g).max()) > KLT_MAX_GUESS:
+        raise ValueError(f"klt_track: init_pts beyond 2^20 px in magnitude ({float(np.abs(g).max()):g})")
+    return pts, g
+
+
+def motion_prior_args(affine, use, lanes):
+    """The argument checks of Engine.set_motion_prior, made before any device call -> (affine (lanes, 6) float32, use (lanes,) uint8 or
+    None).  ValueError: affine neither (lanes, 2, 3) nor (lanes, 6), use not (lanes,), an entry that is not finite, a linear coefficient
+    above PRIOR_MAX_LINEAR = 64 or a translation above KLT_MAX_GUESS = 2^20 px in magnitude (what roam_engine_set_motion_prior refuses)."""
+    a = np.asarray(affine)
+    if a.shape not in ((lanes, 2, 3), (lanes, 6)):
+        raise ValueError(f"set_motion_prior: affine of shape ({lanes}, 2, 3) or ({lanes}, 6), not {a.shape}")
+    a = np.ascontiguousarray(a.reshape(lanes, 6), np.float32)
+    if not np.isfinite(a).all():
+        raise ValueError("set_motion_prior: affine is not finite")
+    if float(np.abs(a[:, [0, 1, 3, 4]]).max()) > PRIOR_MAX_LINEAR or float(np.abs(a[:, [2, 5]]).max()) > KLT_MAX_GUESS:
+        raise ValueError(f"set_motion_prior: linear coefficients within {PRIOR_MAX_LINEAR:g}, translations within 2^20 px")
+    if use is not None:
+        u = np.asarray(use)
+        if u.shape != (lanes,):
+            raise ValueError(f"set_motion_prior: use of shape ({lanes},), not {u.shape}")
+        use = np.ascontiguousarray(u != 0, np.uint8)
+    return a, use
 
 
 def _f32_rows_in_place(a):
@@ -502,8 +547,11 @@ class Context:
                                               int(offs[0]), int(offs[1]), int(offs[2]), C.byref(k)))
         return {1: "rows", 2: "wave"}[k.value]
 
-    def klt_track(self, prev_img, next_img, pts):
-        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+    def klt_track(self, prev_img, next_img, pts, init_pts=None):
+        """cv2.calcOpticalFlowPyrLK with the reference's LK_PARAMS -> (nextPts (K, 2) f32, status (K, 1) u8, err (K, 1) f32).  init_pts
+        (K, 2): OPTFLOW_USE_INITIAL_FLOW, where the search for each feature starts (roam_klt_track_*_flow); None: at the feature.
+        ValueError before any device call for what klt_flow_args refuses."""
+        pts, init_pts = klt_flow_args(pts, init_pts)
         K = pts.shape[0]
         nxt = np.zeros((K, 2), np.float32)
         st = np.zeros((K,), np.uint8)
@@ -512,11 +560,14 @@ class Context:
         assert next_img.shape == prev_img.shape
         if prev_img.dtype == np.uint8:
             a, b = np.ascontiguousarray(prev_img), np.ascontiguousarray(next_img, np.uint8)
-            fn = self.lib.roam_klt_track_u8
+            fn, fn_flow = self.lib.roam_klt_track_u8, self.lib.roam_klt_track_u8_flow
         else:
             a, b = np.ascontiguousarray(prev_img, np.float32), np.ascontiguousarray(next_img, np.float32)
-            fn = self.lib.roam_klt_track_f32
-        self.check(fn(self.h, _ptr(a), _ptr(b), w, h, _ptr(pts), K, _ptr(nxt), _ptr(st), _ptr(err)))
+            fn, fn_flow = self.lib.roam_klt_track_f32, self.lib.roam_klt_track_f32_flow
+        if init_pts is None:
+            self.check(fn(self.h, _ptr(a), _ptr(b), w, h, _ptr(pts), K, _ptr(nxt), _ptr(st), _ptr(err)))
+        else:
+            self.check(fn_flow(self.h, _ptr(a), _ptr(b), w, h, _ptr(pts), _ptr(init_pts), K, _ptr(nxt), _ptr(st), _ptr(err)))
         return nxt, st.reshape(-1, 1), err.reshape(-1, 1)
 
     def reject_outliers(self, prev, new, thr_px, node_limit=0, want_adj=False):

@@ -307,7 +307,15 @@ extern "C" int32_t roam_pyr_down2_u8(roam_ctx *ctx, uint8_t *buf, int64_t bytes,
     return ROAM_OK;
 }
 
-static int32_t klt_common(roam_ctx *ctx, uint8_t *pyrA, uint8_t *pyrB, const PyrDesc &d, const float *pts, int K,
+// the start of the search as roam_klt_track_*_flow document it: finite and below 2^20 px in magnitude
+static bool klt_guess_ok(const float *g, int K)
+{
+    for (int64_t i = 0; i < 2 * (int64_t)K; i++)
+        if (!(fabsf(g[i]) <= ROAM_KLT_MAX_GUESS)) return false;       // (false for NaN as well)
+    return true;
+}
+
+static int32_t klt_common(roam_ctx *ctx, uint8_t *pyrA, uint8_t *pyrB, const PyrDesc &d, const float *pts, const float *init_pts, int K,
                           float *next_pts, uint8_t *status, float *err)
 {
     HIP_TRY(ctx, launch_build_pyramid(ctx->stream, pyrA, d, 1));
@@ -317,7 +325,13 @@ static int32_t klt_common(roam_ctx *ctx, uint8_t *pyrA, uint8_t *pyrB, const Pyr
     SCRATCH(dst, uint8_t, S_OUT1, (size_t)K);
     SCRATCH(derr, float, S_OUT2, sizeof(float) * (size_t)K);
     H2D(dpts, pts, sizeof(float) * 2 * (size_t)K);
-    HIP_TRY(ctx, launch_klt(ctx->stream, pyrA, pyrB, d, dpts, nullptr, K, K, 1, dnext, dst, derr));
+    float *dguess = nullptr;
+    if (init_pts) {
+        SCRATCH(dg, float, S_IN3, sizeof(float) * 2 * (size_t)K);
+        H2D(dg, init_pts, sizeof(float) * 2 * (size_t)K);
+        dguess = dg;
+    }
+    HIP_TRY(ctx, launch_klt(ctx->stream, pyrA, pyrB, d, dpts, nullptr, K, K, 1, dnext, dst, derr, dguess));
     D2H(next_pts, dnext, sizeof(float) * 2 * (size_t)K);
     D2H(status, dst, (size_t)K);
     D2H(err, derr, sizeof(float) * (size_t)K);
@@ -325,12 +339,13 @@ static int32_t klt_common(roam_ctx *ctx, uint8_t *pyrA, uint8_t *pyrB, const Pyr
     return ROAM_OK;
 }
 
-extern "C" int32_t roam_klt_track_u8(roam_ctx *ctx, const uint8_t *prev_img, const uint8_t *next_img,
-                                     int32_t w, int32_t h, const float *pts, int32_t K,
-                                     float *next_pts, uint8_t *status, float *err)
+extern "C" int32_t roam_klt_track_u8_flow(roam_ctx *ctx, const uint8_t *prev_img, const uint8_t *next_img,
+                                          int32_t w, int32_t h, const float *pts, const float *init_pts, int32_t K,
+                                          float *next_pts, uint8_t *status, float *err)
 {
     ENTER();
     ARG_CHECK(ctx, prev_img && next_img && pts && next_pts && status && err && w >= 16 && h >= 16 && K >= 0);
+    ARG_CHECK(ctx, !init_pts || klt_guess_ok(init_pts, K));
     if (K == 0) return ROAM_OK;
     PyrDesc d;
     pyr_desc_init(&d, w, h);
@@ -338,15 +353,23 @@ extern "C" int32_t roam_klt_track_u8(roam_ctx *ctx, const uint8_t *prev_img, con
     SCRATCH(pb, uint8_t, S_PYR_B, (size_t)d.lane_stride);
     H2D(pa, prev_img, (size_t)w * h);
     H2D(pb, next_img, (size_t)w * h);
-    return klt_common(ctx, pa, pb, d, pts, K, next_pts, status, err);
+    return klt_common(ctx, pa, pb, d, pts, init_pts, K, next_pts, status, err);
 }
 
-extern "C" int32_t roam_klt_track_f32(roam_ctx *ctx, const float *prev_img, const float *next_img,
-                                      int32_t w, int32_t h, const float *pts, int32_t K,
-                                      float *next_pts, uint8_t *status, float *err)
+extern "C" int32_t roam_klt_track_u8(roam_ctx *ctx, const uint8_t *prev_img, const uint8_t *next_img,
+                                     int32_t w, int32_t h, const float *pts, int32_t K,
+                                     float *next_pts, uint8_t *status, float *err)
+{
+    return roam_klt_track_u8_flow(ctx, prev_img, next_img, w, h, pts, nullptr, K, next_pts, status, err);
+}
+
+extern "C" int32_t roam_klt_track_f32_flow(roam_ctx *ctx, const float *prev_img, const float *next_img,
+                                           int32_t w, int32_t h, const float *pts, const float *init_pts, int32_t K,
+                                           float *next_pts, uint8_t *status, float *err)
 {
     ENTER();
     ARG_CHECK(ctx, prev_img && next_img && pts && next_pts && status && err && w >= 16 && h >= 16 && K >= 0);
+    ARG_CHECK(ctx, !init_pts || klt_guess_ok(init_pts, K));
     if (K == 0) return ROAM_OK;
     PyrDesc d;
     pyr_desc_init(&d, w, h);
@@ -359,7 +382,14 @@ extern "C" int32_t roam_klt_track_f32(roam_ctx *ctx, const float *prev_img, cons
     H2D(fb, next_img, sizeof(float) * npx);
     HIP_TRY(ctx, launch_quantize_u8(ctx->stream, fa, (int64_t)npx, pa));
     HIP_TRY(ctx, launch_quantize_u8(ctx->stream, fb, (int64_t)npx, pb));
-    return klt_common(ctx, pa, pb, d, pts, K, next_pts, status, err);
+    return klt_common(ctx, pa, pb, d, pts, init_pts, K, next_pts, status, err);
+}
+
+extern "C" int32_t roam_klt_track_f32(roam_ctx *ctx, const float *prev_img, const float *next_img,
+                                      int32_t w, int32_t h, const float *pts, int32_t K,
+                                      float *next_pts, uint8_t *status, float *err)
+{
+    return roam_klt_track_f32_flow(ctx, prev_img, next_img, w, h, pts, nullptr, K, next_pts, status, err);
 }
 
 extern "C" int32_t roam_reject_outliers(roam_ctx *ctx, const float *prev, const float *next, int32_t K,

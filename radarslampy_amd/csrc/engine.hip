@@ -51,6 +51,11 @@ struct Engine {
     int32_t *scan_idx[3] = {nullptr, nullptr, nullptr};
     int32_t *scan_host = nullptr;       // pinned staging of the scan indices + new-sequence flags (3 x 2B)
     int pk = 0;                         // ring slot of the latest step (valid peak / scan-index buffers)
+    // motion prior of the next step (roam_engine_set_motion_prior): per slot B x 6 f32 affine rows, then B use bytes.  Four slots, indexed
+    // like ev_klt: the host slot is rewritten and the device slot overwritten only after the tracker of four steps ago
+    uint8_t *prior_host = nullptr, *prior_dev = nullptr;
+    size_t prior_bytes = 0;             // of one slot
+    bool prior_set = false;             // prior_host's slot of the next step holds a prior that no step has consumed
     int64_t nstep = 0;
     float *feat = nullptr;              // B x KS x 2
     int32_t *feat_n = nullptr;
@@ -597,6 +602,7 @@ int32_t roam_engine_destroy(roam_ctx *ctx)
     for (auto &row : e->tr_ev) for (auto &ev : row) kill(ev);
     for (auto &row : e->rt_ev) for (auto &ev : row) kill(ev);
     if (e->scan_host) hipHostFree(e->scan_host);
+    if (e->prior_host) hipHostFree(e->prior_host);
     if (e->results_host) hipHostFree(e->results_host);
     for (auto &ev : e->ev_res) if (ev) hipEventDestroy(ev);
     if (e->st_comm) { hipStreamSynchronize(e->st_comm); hipStreamDestroy(e->st_comm); }
@@ -668,6 +674,11 @@ int32_t roam_engine_create(roam_ctx *ctx, const roam_engine_cfg *cfg)
     if (ok && hipHostMalloc(reinterpret_cast<void **>(&e->scan_host), sizeof(int32_t) * 6 * (size_t)B, hipHostMallocDefault) != hipSuccess) {
         ROAM_SET_ERR(ctx, "engine: hipHostMalloc failed"); ok = false;
     }
+    e->prior_bytes = ((size_t)B * 25 + 15) & ~(size_t)15;
+    if (ok && hipHostMalloc(reinterpret_cast<void **>(&e->prior_host), 4 * e->prior_bytes, hipHostMallocDefault) != hipSuccess) {
+        ROAM_SET_ERR(ctx, "engine: hipHostMalloc failed"); ok = false;
+    }
+    ok = ok && dalloc(ctx, e, &e->prior_dev, 4 * e->prior_bytes);
     ok = ok && dalloc(ctx, e, &e->feat, (size_t)B * KS * 2);
     ok = ok && dalloc(ctx, e, &e->feat_n, (size_t)B);
     ok = ok && dalloc(ctx, e, &e->klt_next, (size_t)B * KS * 2);
@@ -1286,6 +1297,32 @@ int32_t roam_engine_init_lanes_detect(roam_ctx *ctx, int32_t lane0, int32_t n, c
     return ROAM_OK;
 }
 
+int32_t roam_engine_set_motion_prior(roam_ctx *ctx, const float *affine, const uint8_t *use)
+{
+    ENGINE();
+    if (!affine) { e->prior_set = false; return ROAM_OK; }
+    const int B = e->B;
+    for (int b = 0; b < B; b++)
+        for (int i = 0; i < 6; i++) {
+            const float lim = (i % 3 == 2) ? ROAM_KLT_MAX_GUESS : ROAM_PRIOR_MAX_LINEAR;
+            if (!(fabsf(affine[6 * b + i]) <= lim)) {                   // (NaN fails it too)
+                ROAM_SET_ERR(ctx, "set_motion_prior: lane %d, entry %d = %g: finite, linear part within %g, translation within %g px",
+                             b, i, (double)affine[6 * b + i], (double)ROAM_PRIOR_MAX_LINEAR, (double)ROAM_KLT_MAX_GUESS);
+                return ROAM_E_ARG;
+            }
+        }
+    const int k4 = (int)(e->nstep & 3);
+    // the slot's last upload was enqueued ahead of the tracker of step nstep - 4; roam_engine_step has waited for that step's end
+    // since (it lets the host run three steps ahead), so this returns at once - it states the guard, as for scan_host
+    if (e->nstep >= 4) HIP_TRY(ctx, hipEventSynchronize(e->ev_klt[k4]));
+    uint8_t *slot = e->prior_host + (size_t)k4 * e->prior_bytes;
+    memcpy(slot, affine, sizeof(float) * 6 * (size_t)B);
+    if (use) for (int b = 0; b < B; b++) slot[24 * (size_t)B + b] = use[b] ? 1 : 0;
+    else memset(slot + 24 * (size_t)B, 1, (size_t)B);
+    e->prior_set = true;
+    return ROAM_OK;
+}
+
 int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
 {
     ENGINE();
@@ -1324,6 +1361,17 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
     const int pb = (int)(e->nstep % 3);                 // ring slot of the peak / scan-index buffers
     const int k4 = (int)(e->nstep & 3), w4 = (int)((e->nstep + 1) & 3);   // event slot of this step / of step N-3
     uint8_t *prev = e->pyr[e->cur], *next = e->pyr[(e->cur + 1) & 3];
+    // the motion prior of this step, if one was set: one small copy on the compute stream, behind the previous step's back end (which
+    // no longer reads the slot: its tracker ran four steps ago) and long before this step's tracker is released by its pyramid
+    const float *prior_aff = nullptr;
+    const uint8_t *prior_use = nullptr;
+    if (e->prior_set) {
+        uint8_t *dslot = e->prior_dev + (size_t)k4 * e->prior_bytes;
+        HIP_TRY(ctx, hipMemcpyAsync(dslot, e->prior_host + (size_t)k4 * e->prior_bytes, 25 * (size_t)B, hipMemcpyHostToDevice, st));
+        prior_aff = reinterpret_cast<const float *>(dslot);
+        prior_use = dslot + 24 * (size_t)B;
+        e->prior_set = false;
+    }
     HIP_TRY(ctx, hipStreamWaitEvent(sA, e->ev_klt[w4], 0));
     HIP_TRY(ctx, hipStreamWaitEvent(sA, e->ev_g4[w4], 0));
     // (lane initialisation, retracks and synchronous uploads finish on the host before a step is enqueued)
@@ -1386,7 +1434,8 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
         hipLaunchKernelGGL(new_sequence_kernel, dim3((B + 255) / 256), dim3(256), 0, st, e->feat_n, e->scan_idx[pb] + B, B);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, launch_klt(st, prev, next, e->pd, e->feat, e->feat_n, KM, KS, B, e->klt_next, e->klt_status, e->klt_err));
+    HIP_TRY(ctx, launch_klt(st, prev, next, e->pd, e->feat, e->feat_n, KM, KS, B, e->klt_next, e->klt_status, e->klt_err, nullptr,
+                            prior_aff, prior_use));
     HIP_TRY(ctx, hipEventRecord(e->ev_klt[k4], st));
     hipLaunchKernelGGL(g1_good_kernel, dim3(B), dim3(256), 0, st, e->feat, e->feat_n, e->klt_next, e->klt_status, e->klt_err,
                        e->good_old, e->good_new, e->good_idx, e->good_n, KM);

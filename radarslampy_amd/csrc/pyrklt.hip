@@ -728,7 +728,9 @@ __global__ __launch_bounds__(64) void klt_kernel(const uint8_t *__restrict__ pre
                                                  const uint8_t *__restrict__ next_pyr, PyrDesc d,
                                                  const float *__restrict__ pts, const int32_t *__restrict__ count,
                                                  int kstride, float *__restrict__ next_out,
-                                                 uint8_t *__restrict__ status_out, float *__restrict__ err_out)
+                                                 uint8_t *__restrict__ status_out, float *__restrict__ err_out,
+                                                 const float *__restrict__ guess, const float *__restrict__ lane_affine,
+                                                 const uint8_t *__restrict__ lane_use)
 {
     __shared__ __align__(16) uint8_t It8[18][20];               // 18x18 neighbourhood of the previous image (u8, dword rows)
     __shared__ __align__(16) short Dx[16][20], Dy[16][20];      // Scharr derivatives, rows padded to 40 B
@@ -741,7 +743,16 @@ __global__ __launch_bounds__(64) void klt_kernel(const uint8_t *__restrict__ pre
     const float FLT_SCALE = 1.f / (1 << 20);
     const float eps2 = __fmul_rn(0.03f, 0.03f);
     const float min_eig_thr = 1e-4f;
-    float out_x = 0.f, out_y = 0.f, er = 0.f;
+    // Start of the search at the top level (OPTFLOW_USE_INITIAL_FLOW): the feature's own position, a per-point guess, or the lane's
+    // affine prior applied to it.  The choice depends on kernel arguments and blockIdx only (scalar branches), and the start lives in
+    // out_x / out_y, which the top level overwrites anyway: the unseeded launch (three null pointers) carries nothing extra.
+    float out_x = ptx, out_y = pty, er = 0.f;
+    if (guess) { out_x = guess[pidx]; out_y = guess[pidx + 1]; }
+    else if (lane_affine && (!lane_use || lane_use[b])) {
+        const float *A = lane_affine + (int64_t)b * 6;
+        out_x = __fadd_rn(__fadd_rn(__fmul_rn(A[0], ptx), __fmul_rn(A[1], pty)), A[2]);
+        out_y = __fadd_rn(__fadd_rn(__fmul_rn(A[3], ptx), __fmul_rn(A[4], pty)), A[5]);
+    }
     int st = 1;
 
     // window pixels owned by this lane: row ry, columns 4g .. 4g+3 (15 x 15 window -> lanes 0..59, the
@@ -768,7 +779,7 @@ __global__ __launch_bounds__(64) void klt_kernel(const uint8_t *__restrict__ pre
         const float scale = 1.f / (float)(1 << level);
         float px = __fmul_rn(ptx, scale), py = __fmul_rn(pty, scale);
         float nx, ny;
-        if (level == ROAM_PYR_LEVELS - 1) { nx = px; ny = py; }
+        if (level == ROAM_PYR_LEVELS - 1) { nx = __fmul_rn(out_x, scale); ny = __fmul_rn(out_y, scale); }
         else { nx = __fmul_rn(out_x, 2.f); ny = __fmul_rn(out_y, 2.f); }
         out_x = nx; out_y = ny;
         px = __fsub_rn(px, halfWin); py = __fsub_rn(py, halfWin);
@@ -960,10 +971,11 @@ __global__ __launch_bounds__(64) void klt_kernel(const uint8_t *__restrict__ pre
 
 hipError_t launch_klt(hipStream_t st, const uint8_t *prev_pyr, const uint8_t *next_pyr,
                       const PyrDesc &d, const float *pts, const int32_t *count, int K, int kstride,
-                      int B, float *next, uint8_t *status, float *err)
+                      int B, float *next, uint8_t *status, float *err, const float *guess, const float *lane_affine,
+                      const uint8_t *lane_use)
 {
     if (K <= 0 || B <= 0) return hipSuccess;
     hipLaunchKernelGGL(klt_kernel, dim3(K, B), dim3(64), 0, st, prev_pyr, next_pyr, d, pts, count, kstride,
-                       next, status, err);
+                       next, status, err, guess, lane_affine, lane_use);
     return hipGetLastError();
 }

@@ -132,9 +132,15 @@ size_t pyr_dark_words(int h);
 hipError_t launch_pyr_dark(hipStream_t st, const uint32_t *map, int w, int h, int cols, unsigned long long *dark);
 
 // KLT: pts/next: B x kstride x 2 f32; count[b] features per lane (or all K if count==null)
+// Start of the search at the top pyramid level (cv2's OPTFLOW_USE_INITIAL_FLOW), all null = the feature's own position:
+//   guess: laid out as pts, one start per feature;
+//   lane_affine: B x 6 f32 [a00 a01 a02 a10 a11 a12], the start is A applied to the feature in float32 ((a00 x + a01 y) + a02, every
+//   operation rounded, no contraction); lane_use: B bytes, 0 = that lane starts at its features (null: every lane is seeded).
+// guess wins over lane_affine.
 hipError_t launch_klt(hipStream_t st, const uint8_t *prev_pyr, const uint8_t *next_pyr,
                       const PyrDesc &d, const float *pts, const int32_t *count, int K, int kstride,
-                      int B, float *next, uint8_t *status, float *err);
+                      int B, float *next, uint8_t *status, float *err, const float *guess = nullptr,
+                      const float *lane_affine = nullptr, const uint8_t *lane_use = nullptr);
 
 // consistency graph: adj: B x K_stride rows x nw words
 hipError_t launch_consistency_graph(hipStream_t st, const float *prev, const float *next,

@@ -145,6 +145,18 @@ class Engine:
         assert idx.shape == (self.lanes,)
         self.ctx.check(self.lib.roam_engine_step(self.ctx.h, _ffi._ptr(idx)))
 
+    def set_motion_prior(self, affine, use=None):
+        """Motion prior of the NEXT step only (roam_engine_set_motion_prior): affine (lanes, 2, 3) or (lanes, 6), per lane the map
+        from a feature's pixel position in the previous full-size Cartesian image to its predicted position in the current one
+        (FMT.flowPriorFromFMT makes one from a registration); the lane's tracker starts its search there.  use (lanes,): lanes with 0
+        run unseeded; None seeds every lane.  affine=None withdraws a prior that no step has consumed.  Does not synchronise.
+        ValueError before any device call for what _ffi.motion_prior_args refuses."""
+        if affine is None:
+            self.ctx.check(self.lib.roam_engine_set_motion_prior(self.ctx.h, None, None))
+            return
+        a, u = _ffi.motion_prior_args(affine, use, self.lanes)
+        self.ctx.check(self.lib.roam_engine_set_motion_prior(self.ctx.h, _ffi._ptr(a), _ffi._ptr(u)))
+
     def synchronize(self):
         self.ctx.check(self.lib.roam_synchronize(self.ctx.h))
 

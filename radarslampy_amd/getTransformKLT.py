@@ -14,15 +14,27 @@ def calculateTransformSVD(srcCoords: np.ndarray, targetCoords: np.ndarray):
     return _ffi.default_context().kabsch2d(srcCoords, targetCoords)
 
 
-def getTrackedPointsKLT(srcImg: np.ndarray, targetImg: np.ndarray, blobCoordSrc: np.ndarray):
-    """-> (good_new, good_old, bad_new, bad_old, correspondenceStatus (K,1) u8) — note new before old."""
+def getTrackedPointsKLT(srcImg: np.ndarray, targetImg: np.ndarray, blobCoordSrc: np.ndarray, initialFlow=None):
+    """-> (good_new, good_old, bad_new, bad_old, correspondenceStatus (K,1) u8) — note new before old.
+    initialFlow (K, 2), one row per row of blobCoordSrc: where the search for each feature starts in targetImg
+    (cv2.OPTFLOW_USE_INITIAL_FLOW, which the reference never passes); None is the reference's call.  Features that this function
+    appends itself start at their own position."""
     global N_FEATURES_BEFORE_RETRACK
     featurePtSrc = np.ascontiguousarray(blobCoordSrc[:, :2]).astype(np.float32)
+    if initialFlow is not None:
+        initialFlow = np.asarray(initialFlow)
+        if initialFlow.shape != featurePtSrc.shape:
+            raise ValueError(f"getTrackedPointsKLT: initialFlow of shape {featurePtSrc.shape}, not {initialFlow.shape}")
+        initialFlow = initialFlow.astype(np.float32)
     if featurePtSrc.shape[0] < N_FEATURES_BEFORE_RETRACK:
         from .getFeatures import appendNewFeatures
+        n_own = featurePtSrc.shape[0]
         featurePtSrc, N_FEATURES_BEFORE_RETRACK = appendNewFeatures(srcImg, featurePtSrc)
         print("WARNING: getTransformKLT added new features!")
-    nextPts, status, err = _ffi.default_context().klt_track(srcImg, targetImg, featurePtSrc)
+        if initialFlow is not None:
+            featurePtSrc = np.ascontiguousarray(featurePtSrc, np.float32)
+            initialFlow = np.concatenate([initialFlow, featurePtSrc[n_own:]])
+    nextPts, status, err = _ffi.default_context().klt_track(srcImg, targetImg, featurePtSrc, initialFlow)
     status &= (err < ERR_THRESHOLD)
     good = (status == 1).flatten()
     bad = ~good
