@@ -375,6 +375,37 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx);
  * features inside a 16384 px image the start then stays below 2^22 px.  ROAM_E_STATE: no engine. */
 #define ROAM_PRIOR_MAX_LINEAR 64.0f
 int32_t roam_engine_set_motion_prior(roam_ctx *ctx, const float *affine, const uint8_t *use);
+/* The motion prior as a mode of the engine: while it is on, every roam_engine_step registers each lane's previous scan against its
+ * current one (roam_engine_fmt_register's pass, FMT.py:211-250, 134-168, 13-33, on the raw pool records) and hands the affine of
+ * FMT.flowPriorFromFMT to the lane's tracker, all on the device: the pass is enqueued on a stream of its own beside the warp of its
+ * step, the tracker waits for it, and no call synchronises the host.  Pair i of a step is (the scan lane i consumed in its previous
+ * step, scan_idx[i]); a lane without a previous step or with ROAM_STEP_NEW_SEQUENCE is not registered and runs unseeded.
+ * clip_px, downsample, cart_downsample: as roam_engine_fmt_register (0, 0, 0 = 1012, 10, 20).  min_rot_response, min_trans_response:
+ * a lane whose rotation or translation correlation answers below its minimum runs unseeded, bit for bit; 0 = no gate.  A lane also
+ * runs unseeded when a number of its registration is not finite or its affine is beyond roam_engine_set_motion_prior's limits.
+ * roam_engine_set_auto_prior is the only blocking part: it waits for the enqueued steps, allocates the pass's buffers (one device
+ * allocation, sized for chunks of floor(2000 MiB / bytes per pair) pairs, at most `lanes`; ROAM_FMT_BATCH_CHUNK in the environment
+ * is read here, once, and caps the chunk), uploads the host tables and makes the FFT's twiddle tables.  cfg == NULL switches the mode
+ * off and frees everything.  ROAM_E_ARG, before any device call: whatever roam_engine_fmt_register refuses, a minimum that is
+ * negative or not finite.  ROAM_E_HIP: the memory cannot be had; the mode stays off.
+ * A prior set with roam_engine_set_motion_prior still belongs to the next step only and wins for that whole step: no registration
+ * is enqueued for it.
+ * The previous record must still be in its pool slot: the engine counts the writes to every slot (roam_engine_upload_scan,
+ * _upload_scans_async, _copy_scan) and remembers the count of the slot each lane consumed.  A step that finds the previous slot of a
+ * lane written since returns ROAM_E_STATE (the message names lane and slot) before it enqueues anything.  It is said once: the lane's
+ * next step trusts the slot, so the caller restores the record and steps again. */
+typedef struct roam_auto_prior_cfg {
+    int32_t clip_px, downsample, cart_downsample;   /* as roam_engine_fmt_register; 0, 0, 0 = 1012 / 10 / 20 clipped to cfg.clip */
+    double min_rot_response, min_trans_response;    /* lanes below either run unseeded; 0 = no gate */
+} roam_auto_prior_cfg;
+int32_t roam_engine_set_auto_prior(roam_ctx *ctx, const roam_auto_prior_cfg *cfg);   /* NULL: off */
+/* the prior of step `step` (0-based, as roam_engine_step_results, which it waits like: for that step only; ROAM_E_STATE once the step
+ * has left the ring of 8, or if the mode was off when the step was enqueued or has been switched off since).  Row i of n <= lanes:
+ * out6 {angle_rad, scale, rot_response, dx, dy, trans_response} in roam_engine_fmt_register's column order (the scale is made on the
+ * host from the record's raw shift, with the blocking pass's expression), NaN for a lane that was not registered; affine (n, 6) f32,
+ * the prior the lane's tracker was offered; source (n) u8: 0 = unseeded, 1 = in-step registration, 2 = the caller's
+ * roam_engine_set_motion_prior.  Any of the three may be NULL. */
+int32_t roam_engine_step_prior(roam_ctx *ctx, int64_t step, double *out6, float *affine, uint8_t *source, int32_t n);
 /* scan_idx[i] | ROAM_STEP_NEW_SEQUENCE: lane i starts a NEW sequence on this scan - its features are dropped before the pair,
  * nothing is tracked, the pose stays, and the first-frame detection (appendNewFeatures(prevImgCart, empty),
  * RawROAMSystem.py:150) runs on this scan inside the step (needs cfg.retrack_on_device).  A stream of finite sequences

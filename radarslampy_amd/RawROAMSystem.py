@@ -1,7 +1,7 @@
 """Streaming odometry driver on the device-resident engine.
 
 Same entry points as the reference's RawROAMSystem (constructor arguments, run(startSeqInd, endSeqInd), the paramFlags
-`rejectOutliers` / `correctMotionDistortion`; reference RawROAMSystem.py:20-160), but not its loop: frames are decoded on
+`rejectOutliers` / `correctMotionDistortion`, and Tracker's addition `fmtPrior`: the in-step motion prior; reference RawROAMSystem.py:20-160), but not its loop: frames are decoded on
 the host (PNG inflate), copied into a pinned staging ring, uploaded on the copy stream while earlier frames are being
 processed (roam_engine_upload_scans_async), and every scan pair is ONE roam_engine_step - tracking, outlier rejection,
 pose solve, keyframe bookkeeping and the feature re-detection all stay on the GPU.  Poses come back through the engine's
@@ -18,6 +18,7 @@ from .trajectoryPlotting import Trajectory, computePosesRMSE, getGroundTruthTraj
 from .utils import radarImgPathToTimestamp
 
 RING = 8            # resident scans per lane: frames k-1 .. k+LOOKAHEAD and a margin for the 3-deep step pipeline
+                    # (frame k-1: the previous scan of the in-step motion prior, paramFlags["fmtPrior"])
 LOOKAHEAD = 3       # uploads run this many frames ahead of the step that consumes them
 LAG = 2             # results are read this many steps behind the enqueue front
 
@@ -102,6 +103,12 @@ def stream_records(records, n_frames, init_pose, paramFlags=None, ctx=None, rows
     eng = Engine(1, RING, ctx=ctx, rows=rows, stride=stride, payload_off=payload_off, clip=clip,
                  reject_outliers=flags.get("rejectOutliers", True), motion_distortion=flags.get("correctMotionDistortion", True),
                  retrack_on_device=True, stage_events=False)
+    if flags.get("fmtPrior", False):
+        # Tracker's flag: every pair is registered on the device inside its step and seeds the tracker (Engine.set_auto_prior).  The
+        # pass of step k reads frame k - 1 besides frame k: slot (k - 1) % RING is next written by frame k + RING - 1, whose upload is
+        # enqueued behind the fence of step k + RING - 1 - LOOKAHEAD >= k + 4 - and the fence covers the pass, which the compute stream
+        # waits for ahead of its tracker.  The ring needs no further slot
+        eng.set_auto_prior(True)
     if on_engine is not None:
         on_engine(eng)
     pinned = None if records_pinned else ctx.host_alloc((RING, rows, stride))

@@ -45,6 +45,15 @@ class LaneResult(C.Structure):
                 ("lm_info", C.c_int32), ("flags", C.c_int32), ("n_after_retrack", C.c_int32)]
 
 
+class AutoPriorCfg(C.Structure):
+    """roam_abi.h roam_auto_prior_cfg"""
+    _fields_ = [("clip_px", C.c_int32), ("downsample", C.c_int32), ("cart_downsample", C.c_int32),
+                ("min_rot_response", C.c_double), ("min_trans_response", C.c_double)]
+
+
+PRIOR_RECORD = np.dtype([("out6", np.float64, (6,)), ("affine", np.float32, (2, 3)), ("source", np.uint8)])     # Engine.step_prior's rows
+
+
 class KeyframeHdr(C.Structure):
     _fields_ = [("pose", C.c_double * 3), ("velocity", C.c_double * 3), ("n_features", C.c_int32), ("n_peaks", C.c_int32),
                 ("scan", C.c_int32), ("lane", C.c_int32)]
@@ -109,6 +118,8 @@ _SIGS = {
     "roam_engine_steps_enqueued": (C.c_int32, [_vp, _P(C.c_int64)]),
     "roam_engine_set_retrack": (C.c_int32, [_vp, C.c_int32]),
     "roam_engine_set_motion_prior": (C.c_int32, [_vp, _vp, _vp]),
+    "roam_engine_set_auto_prior": (C.c_int32, [_vp, _P(AutoPriorCfg)]),
+    "roam_engine_step_prior": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int32]),
     "roam_engine_init_lane_detect": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp]),
     "roam_engine_init_lanes_detect": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_engine_lane_features": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, _P(C.c_int32)]),
@@ -335,6 +346,24 @@ def motion_prior_args(affine, use, lanes):
             raise ValueError(f"set_motion_prior: use of shape ({lanes},), not {u.shape}")
         use = np.ascontiguousarray(u != 0, np.uint8)
     return a, use
+
+
+def auto_prior_args(cols, rows, clip_px, downsample, cart_downsample, min_rot_response, min_trans_response):
+    """The argument checks of Engine.set_auto_prior, made before any device call -> AutoPriorCfg.  cols, rows: the engine's clip and
+    rows.  What Engine.fmt_register refuses - fmt_clip_radius's and fmt_cart_radius's conditions: ValueError, TypeError for a
+    cart_downsample that is no integer - and a response minimum that is negative or not finite: ValueError."""
+    fmt_clip_radius(cols, clip_px, downsample, rows)
+    fmt_cart_radius(cols, cart_downsample)
+    gates = []
+    for name, v in (("min_rot_response", min_rot_response), ("min_trans_response", min_trans_response)):
+        v = float(v)
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"set_auto_prior: {name} finite and >= 0, not {v}")
+        gates.append(v)
+    clip_px, downsample, cart_downsample = int(clip_px), int(downsample), int(cart_downsample)
+    if clip_px == 0 and downsample == 0 and cart_downsample == 0:        # (refused above: downsample < 1; never the ABI's "defaults")
+        raise ValueError("set_auto_prior: downsample >= 1")
+    return AutoPriorCfg(clip_px, downsample, cart_downsample, gates[0], gates[1])
 
 
 def _f32_rows_in_place(a):

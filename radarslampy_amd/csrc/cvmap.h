@@ -74,6 +74,28 @@ __device__ __forceinline__ void cv_affine_fixed32(const double *__restrict__ m, 
     Y = (int)(Y0 + bdelta) >> 5;
 }
 
+// OpenCV's invertAffineTransform as warpAffine applies it in place, float64 (no fused multiply-add: roam_internal.h); a singular matrix
+// becomes all zeros.  Host and device: the host entries invert with it, fmtr_angle_matrix_kernel on the device
+__host__ __device__ inline void cv_invert_affine(const double *in, double *M)
+{
+    for (int k = 0; k < 6; k++) M[k] = in[k];
+    double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0 ? 1. / D : 0;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11; M[1] *= -D;
+    M[3] *= -D; M[4] = A22;
+    const double b1 = -M[0] * M[2] - M[1] * M[5];
+    const double b2 = -M[3] * M[2] - M[4] * M[5];
+    M[2] = b1; M[5] = b2;
+}
+
+// cv2.getRotationMatrix2D((cx, cy), degrees, 1.0) from the cosine and sine of the angle (the caller's libm makes them): 6 doubles
+__host__ __device__ inline void cv_rotation_matrix(double a, double b, double cx, double cy, double *M)
+{
+    M[0] = a; M[1] = b; M[2] = (1 - a) * cx - b * cy;
+    M[3] = -b; M[4] = a; M[5] = b * cx + (1 - a) * cy;
+}
+
 // saturate_cast<short>(s >> INTER_BITS)
 __device__ __forceinline__ int cv_tap_index(int s) { return min(max(s >> 5, -32768), 32767); }
 

@@ -57,6 +57,21 @@ struct Engine {
     size_t prior_bytes = 0;             // of one slot
     bool prior_set = false;             // prior_host's slot of the next step holds a prior that no step has consumed
     int64_t nstep = 0;
+    // the prior as a mode (roam_engine_set_auto_prior): fft.hip's in-step registration on ap_stream writes the step's slot of prior_dev and
+    // one record per lane into ap_rec (ring of RES_RING x B, behind the pass's buffers in ap_slab), mirrored to pinned memory behind the step
+    FmtAuto *ap = nullptr;
+    FmtAutoPlan ap_plan = {};
+    uint8_t *ap_slab = nullptr;
+    FmtPriorRec *ap_rec = nullptr, *ap_rec_host = nullptr;
+    int64_t ap_rec_step[RES_RING] = {-1, -1, -1, -1, -1, -1, -1, -1};      // the step whose prior records a ring slot holds
+    hipStream_t ap_stream = nullptr;
+    hipEvent_t ap_ev = nullptr;         // end of the latest pass (the tracker of its step waits for it)
+    uint64_t ap_up_waited = 0;          // as up_waited, for ap_stream
+    bool ap_pool_dirty = false;         // as pool_dirty, for ap_stream
+    std::vector<int32_t> prev_scan;     // host: the scan each lane's previous pyramid was made from (init_lane*, every step), -1: none
+    std::vector<uint64_t> slot_writes;  // host: writes to each pool slot so far (upload_scan, upload_scans_async, copy_scan)
+    std::vector<uint64_t> lane_seen;    // host: slot_writes of prev_scan when the lane consumed it; UINT64_MAX: whatever it holds (after a refusal)
+    std::vector<int32_t> ap_prev, ap_curr, ap_pair;
     float *feat = nullptr;              // B x KS x 2
     int32_t *feat_n = nullptr;
     float *klt_next = nullptr, *klt_err = nullptr;
@@ -584,6 +599,18 @@ __global__ __launch_bounds__(256) void ingest_rows_kernel(const uint8_t *__restr
 // ------------------------------------------------------------------------------ API
 extern "C" {
 
+// the in-step prior's resources; the caller has waited for the enqueued steps
+static void auto_prior_release(Engine *e)
+{
+    if (e->ap_stream) { (void)hipStreamSynchronize(e->ap_stream); (void)hipStreamDestroy(e->ap_stream); e->ap_stream = nullptr; }
+    if (e->ap_ev) { (void)hipEventDestroy(e->ap_ev); e->ap_ev = nullptr; }
+    roam_fmt_auto_free(e->ap); e->ap = nullptr;
+    if (e->ap_slab) { (void)hipFree(e->ap_slab); e->ap_slab = nullptr; }
+    if (e->ap_rec_host) { (void)hipHostFree(e->ap_rec_host); e->ap_rec_host = nullptr; }
+    e->ap_rec = nullptr;
+    for (auto &st : e->ap_rec_step) st = -1;
+}
+
 int32_t roam_engine_destroy(roam_ctx *ctx)
 {
     if (!ctx) return ROAM_E_ARG;
@@ -591,6 +618,7 @@ int32_t roam_engine_destroy(roam_ctx *ctx)
     if (!e) return ROAM_OK;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
+    auto_prior_release(e);
     for (void *p : e->allocs) hipFree(p);
     // every event handle starts out null, so a creation that failed half way leaks nothing
     auto kill = [](hipEvent_t &ev) { if (ev) { hipEventDestroy(ev); ev = nullptr; } };
@@ -651,6 +679,9 @@ int32_t roam_engine_create(roam_ctx *ctx, const roam_engine_cfg *cfg)
     const int B = e->B = cfg->lanes;
     e->lane_k.assign(B, 0);
     e->last_scan.assign(B, -1);
+    e->prev_scan.assign(B, -1);
+    e->lane_seen.assign(B, 0);
+    e->slot_writes.assign((size_t)cfg->pool_scans, 0);
     e->W = 2 * (cfg->clip / 2);
     e->stage_cap = (cfg->clip + 1) / 2;
     pyr_desc_init(&e->pd, e->W, e->W);
@@ -849,6 +880,7 @@ int32_t roam_engine_upload_scan(roam_ctx *ctx, int32_t pool_idx, const uint8_t *
 {
     ENGINE();
     ARG_CHECK(ctx, rec && pool_idx >= 0 && pool_idx < e->cfg.pool_scans);
+    e->slot_writes[(size_t)pool_idx]++;
     HIP_TRY(ctx, hipMemcpyAsync(e->pool + (size_t)pool_idx * e->rec_bytes, rec, e->rec_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ROAM_OK;
@@ -882,7 +914,7 @@ int32_t roam_engine_upload_scans_async(roam_ctx *ctx, int32_t pool_idx0, int32_t
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_up, ctx->stream3));
     e->up_seq++;
-    for (int i = 0; i < n; i++) e->slot_seq[(size_t)pool_idx0 + i] = e->up_seq;
+    for (int i = 0; i < n; i++) { e->slot_seq[(size_t)pool_idx0 + i] = e->up_seq; e->slot_writes[(size_t)pool_idx0 + i]++; }
     HIP_TRY(ctx, hipEventRecord(e->ev_up_ring[e->up_seq & 15], ctx->stream3));
     e->uploads_pending = true;
     return ROAM_OK;
@@ -906,6 +938,8 @@ int32_t roam_engine_copy_scan(roam_ctx *ctx, int32_t dst_idx, int32_t src_idx)
                                     e->rec_bytes, hipMemcpyDeviceToDevice, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(e->ev_pool, ctx->stream));         // the front-end streams of the next step wait for it
         e->pool_dirty = true;
+        e->ap_pool_dirty = true;
+        e->slot_writes[(size_t)dst_idx]++;
     }
     return ROAM_OK;
 }
@@ -1029,6 +1063,7 @@ int32_t roam_engine_init_lane(roam_ctx *ctx, int32_t lane, int32_t pool_idx, con
     HIP_TRY(ctx, hipMemcpyAsync(e->pose + 3 * (size_t)lane, pose3, sizeof(double) * 3, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(e->vel + 3 * (size_t)lane, zero, sizeof(double) * 3, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    e->prev_scan[lane] = pool_idx; e->lane_seen[lane] = e->slot_writes[(size_t)pool_idx];
     return set_features_impl(ctx, e, lane, pts, K, pool_idx);
 }
 
@@ -1293,7 +1328,10 @@ int32_t roam_engine_init_lanes_detect(roam_ctx *ctx, int32_t lane0, int32_t n, c
     e->rt.res = nullptr;
     HIP_TRY(ctx, launch_retrack(st, e->rt, n));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (int i = 0; i < n; i++) e->lane_k[lane0 + i] = 320;
+    for (int i = 0; i < n; i++) {
+        e->lane_k[lane0 + i] = 320;
+        e->prev_scan[lane0 + i] = pool_idx[i]; e->lane_seen[lane0 + i] = e->slot_writes[(size_t)pool_idx[i]];
+    }
     return ROAM_OK;
 }
 
@@ -1323,12 +1361,101 @@ int32_t roam_engine_set_motion_prior(roam_ctx *ctx, const float *affine, const u
     return ROAM_OK;
 }
 
+int32_t roam_engine_set_auto_prior(roam_ctx *ctx, const roam_auto_prior_cfg *cfg)
+{
+    if (!ctx) return ROAM_E_ARG;
+    Engine *e = ctx->engine;
+    if (!e) { ROAM_SET_ERR(ctx, "engine not created"); return ROAM_E_STATE; }
+    FmtAutoCfg ac = {};
+    FmtAutoPlan plan = {};
+    if (cfg) {
+        // what roam_engine_fmt_register refuses, before any device call
+        const bool dflt = cfg->clip_px == 0 && cfg->downsample == 0 && cfg->cart_downsample == 0;
+        const int clip_px = dflt ? 1012 : cfg->clip_px, ds = dflt ? 10 : cfg->downsample, cds = dflt ? 20 : cfg->cart_downsample;
+        ARG_CHECK(ctx, ds >= 1 && cds >= 1 && e->cfg.rows >= 8);
+        const int clip = (clip_px > 0 && clip_px < e->cfg.clip) ? clip_px : e->cfg.clip;
+        ac.rows = e->cfg.rows; ac.cols = e->cfg.clip; ac.clip = clip; ac.R = clip / ds; ac.Rc = e->cfg.clip / cds; ac.lanes = e->B;
+        ac.min_rot = cfg->min_rot_response; ac.min_trans = cfg->min_trans_response;
+        const int32_t rc_ = roam_fmt_auto_plan(ctx, ac, &plan);
+        if (rc_ != ROAM_OK) return rc_;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the one blocking part: the enqueued steps finish first (every stream a step uses)
+    for (hipStream_t s : {ctx->stream, ctx->stream2, ctx->stream4, ctx->stream5}) HIP_TRY(ctx, hipStreamSynchronize(s));
+    auto_prior_release(e);
+    if (!cfg) return ROAM_OK;
+    const size_t B = (size_t)e->B, rec_bytes = sizeof(FmtPriorRec) * B * RES_RING;
+    hipError_t er = hipMalloc(reinterpret_cast<void **>(&e->ap_slab), plan.slab_bytes + rec_bytes);
+    if (er == hipSuccess) er = hipMemsetAsync(e->ap_slab, 0, plan.slab_bytes + rec_bytes, ctx->stream);
+    if (er == hipSuccess) er = hipHostMalloc(reinterpret_cast<void **>(&e->ap_rec_host), rec_bytes, hipHostMallocDefault);
+    // a stream of its own: every stream of the context carries a stage of the step or the uploads
+    if (er == hipSuccess) er = hipStreamCreateWithFlags(&e->ap_stream, hipStreamNonBlocking);
+    if (er == hipSuccess) er = hipEventCreateWithFlags(&e->ap_ev, hipEventDisableTiming);
+    int32_t rc = ROAM_OK;
+    if (er != hipSuccess) {
+        (void)hipGetLastError();
+        ROAM_SET_ERR(ctx, "auto prior: %zu bytes of device memory for chunks of %zu pairs: %s", plan.slab_bytes + rec_bytes, plan.chunk, hipGetErrorString(er));
+        rc = ROAM_E_HIP;
+    } else {
+        e->ap_rec = reinterpret_cast<FmtPriorRec *>(e->ap_slab + plan.slab_bytes);
+        rc = roam_fmt_auto_init(ctx, ac, plan, e->ap_slab, &e->ap);          // (synchronises ctx->stream: the memset has landed)
+    }
+    if (rc != ROAM_OK) { auto_prior_release(e); return rc; }
+    e->ap_plan = plan;
+    e->ap_up_waited = 0;
+    e->ap_pool_dirty = e->pool_dirty;
+    return ROAM_OK;
+}
+
+int32_t roam_engine_step_prior(roam_ctx *ctx, int64_t step, double *out6, float *affine, uint8_t *source, int32_t n)
+{
+    ENGINE();
+    ARG_CHECK(ctx, n >= 1 && n <= e->B);
+    if (step < 0 || step >= e->nstep || step < e->nstep - RES_RING) {
+        ROAM_SET_ERR(ctx, "step %lld is not in the result ring (steps %lld..%lld)", (long long)step,
+                     (long long)std::max<int64_t>(0, e->nstep - RES_RING), (long long)e->nstep - 1);
+        return ROAM_E_STATE;
+    }
+    const int rs = (int)(step % RES_RING);
+    if (!e->ap || e->ap_rec_step[rs] != step) {
+        ROAM_SET_ERR(ctx, "step %lld has no prior records: roam_engine_set_auto_prior was off when it was enqueued or has been since", (long long)step);
+        return ROAM_E_STATE;
+    }
+    HIP_TRY(ctx, hipEventSynchronize(e->ev_res[rs]));      // that step's records only
+    const FmtPriorRec *r = e->ap_rec_host + (size_t)rs * e->B;
+    for (int i = 0; i < n; i++) {
+        if (out6) {
+            double *q = out6 + 6 * (size_t)i;
+            q[0] = r[i].v[3]; q[1] = roam_fmt_scale(e->ap_plan.log_base, r[i].v[0]); q[2] = r[i].v[2];
+            q[3] = r[i].v[4]; q[4] = r[i].v[5]; q[5] = r[i].v[6];
+        }
+        if (affine) memcpy(affine + 6 * (size_t)i, r[i].affine, sizeof(float) * 6);
+        if (source) source[i] = r[i].source;
+    }
+    return ROAM_OK;
+}
+
 int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
 {
     ENGINE();
     ARG_CHECK(ctx, scan_idx);
     const int B = e->B;
     for (int b = 0; b < B; b++) ARG_CHECK(ctx, scan_idx[b] >= 0 && (scan_idx[b] & ~ROAM_STEP_NEW_SEQUENCE) < e->cfg.pool_scans);
+    // the in-step prior registers each lane's previous record against its current one - unless the caller's own prior takes this step
+    const bool ap_manual = e->ap && e->prior_set, ap_run = e->ap && !e->prior_set;
+    if (ap_run) {
+        int bad = -1;
+        for (int b = B - 1; b >= 0; b--) {
+            const int ps = e->prev_scan[b];
+            if (ps < 0 || (scan_idx[b] & ROAM_STEP_NEW_SEQUENCE) || e->lane_seen[b] == UINT64_MAX || e->slot_writes[(size_t)ps] == e->lane_seen[b]) continue;
+            e->lane_seen[b] = UINT64_MAX;        // said once: the caller restores the record and steps again, and that step trusts the slot
+            bad = b;
+        }
+        if (bad >= 0) {
+            ROAM_SET_ERR(ctx, "auto prior: pool slot %d, the previous scan of lane %d, was written after the lane consumed it", e->prev_scan[bad], bad);
+            return ROAM_E_STATE;
+        }
+    }
     for (int b = 0; b < B; b++) e->last_scan[b] = scan_idx[b] & ~ROAM_STEP_NEW_SEQUENCE;
     bool any_new = false;
     for (int b = 0; b < B; b++) any_new = any_new || (scan_idx[b] & ROAM_STEP_NEW_SEQUENCE);
@@ -1374,6 +1501,25 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
     }
     HIP_TRY(ctx, hipStreamWaitEvent(sA, e->ev_klt[w4], 0));
     HIP_TRY(ctx, hipStreamWaitEvent(sA, e->ev_g4[w4], 0));
+    int ap_pairs = 0;
+    if (ap_run) {
+        // the pairs of this step, and what stage A waits for below, for the previous and the current slots alike, on the pass's stream
+        e->ap_prev.resize((size_t)B); e->ap_curr.resize((size_t)B); e->ap_pair.resize((size_t)B);
+        uint64_t need = 0;
+        for (int b = 0; b < B; b++) {
+            const int ps = e->prev_scan[b], cs = scan_idx[b] & ~ROAM_STEP_NEW_SEQUENCE;
+            e->ap_pair[b] = -1;
+            if (ps < 0 || (scan_idx[b] & ROAM_STEP_NEW_SEQUENCE)) continue;
+            e->ap_pair[b] = ap_pairs; e->ap_prev[ap_pairs] = ps; e->ap_curr[ap_pairs] = cs; ap_pairs++;
+            need = std::max(need, std::max(e->slot_seq[(size_t)ps], e->slot_seq[(size_t)cs]));
+        }
+        if (need > e->ap_up_waited) {
+            if (e->up_seq - need < 16) HIP_TRY(ctx, hipStreamWaitEvent(e->ap_stream, e->ev_up_ring[need & 15], 0));
+            else { HIP_TRY(ctx, hipStreamWaitEvent(e->ap_stream, ctx->ev_up, 0)); need = e->up_seq; }
+            e->ap_up_waited = need;
+        }
+        if (e->ap_pool_dirty) { HIP_TRY(ctx, hipStreamWaitEvent(e->ap_stream, e->ev_pool, 0)); e->ap_pool_dirty = false; }
+    }
     // (lane initialisation, retracks and synchronous uploads finish on the host before a step is enqueued)
     if (e->uploads_pending) {
         uint64_t need = 0;
@@ -1390,6 +1536,34 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
     if (e->nstep >= 3) HIP_TRY(ctx, hipEventSynchronize(e->ev_g4[w4]));   // the staging slot's last copy has long been consumed
     for (int b = 0; b < B; b++) { hs[b] = scan_idx[b] & ~ROAM_STEP_NEW_SEQUENCE; hs[B + b] = (scan_idx[b] & ROAM_STEP_NEW_SEQUENCE) ? 1 : 0; }
     HIP_TRY(ctx, hipMemcpyAsync(e->scan_idx[pb], hs, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, sA));
+    if (ap_run) {
+        // The registration of this step: it reads raw pool records only, like stage A, and runs beside it.  Its index copy is its own
+        // stream's first command; it writes the step's slot of prior_dev (last read by the tracker of four steps ago) and of the record
+        // ring (whose copy of eight steps ago the host has waited for above); its staging slot was consumed four steps ago (the wait
+        // for g4 of step N - 3 just above covers it).  The chunks of a pass, and the passes of consecutive steps, share buffers and run
+        // in order on the one stream; the pass of step N + 1 may run while step N tracks
+        FmtBatchIn in;
+        in.pool = e->pool; in.rec_bytes = (int64_t)e->rec_bytes; in.rec_stride = c.stride; in.payload_off = c.payload_off;
+        uint8_t *dslot = e->prior_dev + (size_t)k4 * e->prior_bytes;
+        const int32_t rc_ = roam_fmt_auto_enqueue(ctx, e->ap, e->ap_stream, in, k4, ap_pairs, e->ap_prev.data(), e->ap_curr.data(), e->ap_pair.data(),
+                                                  dslot, e->ap_rec + (size_t)rs * B);
+        if (rc_ != ROAM_OK) return rc_;
+        HIP_TRY(ctx, hipEventRecord(e->ap_ev, e->ap_stream));
+        prior_aff = reinterpret_cast<const float *>(dslot);
+        prior_use = dslot + 24 * (size_t)B;
+    }
+    if (e->ap) {
+        e->ap_rec_step[rs] = e->nstep;
+        if (ap_manual) {                 // the caller's prior: no registration, the records say so (the ring slot is the host's: see above)
+            const uint8_t *hp = e->prior_host + (size_t)k4 * e->prior_bytes;
+            FmtPriorRec *hr = e->ap_rec_host + (size_t)rs * B;
+            for (int b = 0; b < B; b++) {
+                for (double &v : hr[b].v) v = NAN;
+                memcpy(hr[b].affine, hp + 24 * (size_t)b, 24);
+                hr[b].source = hp[24 * (size_t)B + b] ? 2 : 0;
+            }
+        }
+    } else e->ap_rec_step[rs] = -1;
     hipEvent_t *tr = e->tr_ev[e->nstep & 63];
     if (e->stage_ev) {
         for (auto &ev : e->tr_ev[e->nstep & 63]) if (!ev) HIP_TRY(ctx, hipEventCreate(&ev));
@@ -1434,6 +1608,7 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
         hipLaunchKernelGGL(new_sequence_kernel, dim3((B + 255) / 256), dim3(256), 0, st, e->feat_n, e->scan_idx[pb] + B, B);
         HIP_TRY(ctx, hipGetLastError());
     }
+    if (ap_run) HIP_TRY(ctx, hipStreamWaitEvent(st, e->ap_ev, 0));        // the affines of the in-step registration
     HIP_TRY(ctx, launch_klt(st, prev, next, e->pd, e->feat, e->feat_n, KM, KS, B, e->klt_next, e->klt_status, e->klt_err, nullptr,
                             prior_aff, prior_use));
     HIP_TRY(ctx, hipEventRecord(e->ev_klt[k4], st));
@@ -1492,7 +1667,9 @@ int32_t roam_engine_step(roam_ctx *ctx, const int32_t *scan_idx)
     // (on the compute stream itself: a side stream waiting on an event here cost 11 % of the step rate - the extra stream
     // shares a hardware queue with one of the pipeline's streams and serialises it; the 0.5 MB copy takes ~20 us)
     HIP_TRY(ctx, hipMemcpyAsync(e->results_host + (size_t)rs * B, res_slot, sizeof(roam_lane_result) * (size_t)B, hipMemcpyDeviceToHost, st));
+    if (ap_run) HIP_TRY(ctx, hipMemcpyAsync(e->ap_rec_host + (size_t)rs * B, e->ap_rec + (size_t)rs * B, sizeof(FmtPriorRec) * (size_t)B, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipEventRecord(e->ev_res[rs], st));
+    for (int b = 0; b < B; b++) { e->prev_scan[b] = e->last_scan[b]; e->lane_seen[b] = e->slot_writes[(size_t)e->last_scan[b]]; }
     e->cur = (e->cur + 1) & 3;
     e->pk = pb;
     e->nstep++;

@@ -17,9 +17,13 @@
 // roam_fmt_rotation is n = 1 of it.
 // The registration (roam_fmt_register_batch_f32, roam_engine_fmt_register) adds a second correlation, on the Cartesian images that the
 // kernels of fmt_register.hip make and turn by the angle of the first: roam_fmt_register_run.
+// Both halves are enqueue-only cores (fmt_rot_enqueue, fmt_trans_enqueue) that the blocking entries and the engine's in-step pass
+// (roam_fmt_auto_enqueue, for roam_engine_set_auto_prior) share.
 #include "cvmap.h"
 #include <math.h>
 #include <stdlib.h>
+#include <algorithm>
+#include <new>
 
 #define FFT_MAX_N 4096
 #define FFT_THREADS 512
@@ -222,7 +226,7 @@ __global__ __launch_bounds__(256) void fft_transpose_kernel(const double *__rest
     }
 }
 
-static int32_t fft_rows(roam_ctx *ctx, const double *re_in, const double *im_in, double *re_out, double *im_out, int64_t total_rows, int n,
+static int32_t fft_rows(roam_ctx *ctx, hipStream_t st, const double *re_in, const double *im_in, double *re_out, double *im_out, int64_t total_rows, int n,
                         bool inverse)
 {
     FftPlan plan;
@@ -233,15 +237,15 @@ static int32_t fft_rows(roam_ctx *ctx, const double *re_in, const double *im_in,
     if (rpw < 1) rpw = 1;
     const int64_t groups = (total_rows + rpw - 1) / rpw;
     if (inverse) { const double *ti = re_in; re_in = im_in; im_in = ti; double *to = re_out; re_out = im_out; im_out = to; }
-    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)groups), dim3(FFT_THREADS), 0, ctx->stream, re_in, im_in, re_out, im_out, total_rows, plan,
+    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)groups), dim3(FFT_THREADS), 0, st, re_in, im_in, re_out, im_out, total_rows, plan,
                        rpw, tw, tw + n);
     HIP_TRY(ctx, hipGetLastError());
     return ROAM_OK;
 }
 
-static int32_t fft_transpose(roam_ctx *ctx, const double *re_in, const double *im_in, int batch, int M, int N, double *re_out, double *im_out)
+static int32_t fft_transpose(roam_ctx *ctx, hipStream_t st, const double *re_in, const double *im_in, int batch, int M, int N, double *re_out, double *im_out)
 {
-    hipLaunchKernelGGL(fft_transpose_kernel, dim3((N + 31) / 32, (M + 31) / 32, batch), dim3(32, 8), 0, ctx->stream, re_in, im_in, M, N, re_out,
+    hipLaunchKernelGGL(fft_transpose_kernel, dim3((N + 31) / 32, (M + 31) / 32, batch), dim3(32, 8), 0, st, re_in, im_in, M, N, re_out,
                        im_out);
     HIP_TRY(ctx, hipGetLastError());
     return ROAM_OK;
@@ -365,14 +369,6 @@ static int optimal_dft_size(int n)
     return best;
 }
 
-// utils.normalize_angles: (th + pi) % (2 pi) - pi (Python modulo)
-static double normalize_angle(double th)
-{
-    th = fmod(th + M_PI, 2.0 * M_PI);
-    if (th < 0) th += 2.0 * M_PI;
-    return th - M_PI;
-}
-
 // cv2.createHanningWindow's float64 factor per row or column of a side of n
 void roam_hanning_factors(int n, double *w)
 {
@@ -413,11 +409,11 @@ static size_t pc_chunk(size_t bytes_per_pair, size_t n, size_t cap, bool env)
     return chunk;
 }
 
-// The correlation of nb pairs, 12 launches on ctx->stream: win[0] / win[1] hold the nb windowed, zero-padded M x N sources / targets
+// The correlation of nb pairs, 12 launches on st: win[0] / win[1] hold the nb windowed, zero-padded M x N sources / targets
 // (planes of `base`: a, and F2 re - which nothing touches before its own row pass has consumed it).  Per image set a row pass, a
 // transpose and a row pass (the spectrum stays transposed, N x M); the cross-power spectrum; the three inverse passes; the peak search
 // -> d_out[3 b] = {dx, dy, response}.  d_pv, d_pi: nb x pc_peak_grid(M N).nblk partial maxima
-static int32_t pc_correlate(roam_ctx *ctx, int nb, int M, int N, double *base, const double *win0, const double *win1, double *d_pv,
+static int32_t pc_correlate(roam_ctx *ctx, hipStream_t st, int nb, int M, int N, double *base, const double *win0, const double *win1, double *d_pv,
                             int *d_pi, double *d_out)
 {
     const size_t pl = (size_t)M * N * nb;
@@ -425,18 +421,17 @@ static int32_t pc_correlate(roam_ctx *ctx, int nb, int M, int N, double *base, c
     const PcPeakGrid g = pc_peak_grid((size_t)M * N);
     double *const a = p.a, *const tr = p.tr, *const ti = p.ti;
     const double *win[2] = {win0, win1};
-    hipStream_t st = ctx->stream;
     for (int k = 0; k < 2; k++) {
-        FFT_TRY(fft_rows(ctx, win[k], nullptr, tr, ti, (int64_t)nb * M, N, false));
-        FFT_TRY(fft_transpose(ctx, tr, ti, nb, M, N, p.F[k][0], p.F[k][1]));
-        FFT_TRY(fft_rows(ctx, p.F[k][0], p.F[k][1], p.F[k][0], p.F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
+        FFT_TRY(fft_rows(ctx, st, win[k], nullptr, tr, ti, (int64_t)nb * M, N, false));
+        FFT_TRY(fft_transpose(ctx, st, tr, ti, nb, M, N, p.F[k][0], p.F[k][1]));
+        FFT_TRY(fft_rows(ctx, st, p.F[k][0], p.F[k][1], p.F[k][0], p.F[k][1], (int64_t)nb * N, M, false));       // spectrum, N x M
     }
     hipLaunchKernelGGL(fmt_cross_power_kernel, dim3((unsigned)((pl + 255) / 256)), dim3(256), 0, st, p.F[0][0], p.F[0][1], p.F[1][0], p.F[1][1],
                        (int)pl, tr, ti);
     HIP_TRY(ctx, hipGetLastError());
-    FFT_TRY(fft_rows(ctx, tr, ti, tr, ti, (int64_t)nb * N, M, true));
-    FFT_TRY(fft_transpose(ctx, tr, ti, nb, N, M, p.F[0][0], p.F[0][1]));
-    FFT_TRY(fft_rows(ctx, p.F[0][0], p.F[0][1], a, nullptr, (int64_t)nb * M, N, true));                      // real part only
+    FFT_TRY(fft_rows(ctx, st, tr, ti, tr, ti, (int64_t)nb * N, M, true));
+    FFT_TRY(fft_transpose(ctx, st, tr, ti, nb, N, M, p.F[0][0], p.F[0][1]));
+    FFT_TRY(fft_rows(ctx, st, p.F[0][0], p.F[0][1], a, nullptr, (int64_t)nb * M, N, true));                      // real part only
     hipLaunchKernelGGL(pc_peak_partial_kernel, dim3(g.nblk, nb), dim3(256), 0, st, a, M, N, g.per, d_pv, d_pi);
     hipLaunchKernelGGL(pc_peak_final_kernel, dim3(nb), dim3(256), 0, st, a, M, N, g.nblk, d_pv, d_pi, d_out);
     HIP_TRY(ctx, hipGetLastError());
@@ -483,7 +478,7 @@ extern "C" int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, con
                                hanning ? d_win : (const double *)nullptr, d_win + rows, M, N, wpl[k]);
             HIP_TRY(ctx, hipGetLastError());
         }
-        FFT_TRY(pc_correlate(ctx, nb, M, N, d_f, wpl[0], wpl[1], d_pv, d_pi, d_out));
+        FFT_TRY(pc_correlate(ctx, st, nb, M, N, d_f, wpl[0], wpl[1], d_pv, d_pi, d_out));
         HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
         for (int i = 0; i < nb; i++) {
@@ -494,14 +489,81 @@ extern "C" int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, con
     return ROAM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ enqueue-only cores
+// Both halves of the registration as work that is only enqueued: caller-owned device buffers, a caller-given stream, no host
+// synchronisation and no allocation (the twiddle tables of the plane sizes excepted: they are made on first use, which the blocking
+// entries accept and roam_fmt_auto_init forestalls).  The blocking entries below and the engine's in-step pass (roam_fmt_auto_enqueue)
+// call these two and differ only in what stands between them: the host's libm or fmtr_angle_matrix_kernel.
+
+// the log-polar size of the rotation half and its DFT plane
+struct FmtRotSize {
+    int dw, dh, M, N, sz;
+    size_t tab_bytes;
+};
+// FMT.py:84-90: the base of the log-polar radius and the scale of a shift along it
+static double fmt_log_base(const FmtRotSize &g) { return exp(log((double)g.dh / 2.0) / (double)g.sz); }
+static double fmt_scale(double log_base, double shift_x) { return pow(log_base, shift_x); }
+static FmtRotSize fmt_rot_size(int R)
+{
+    FmtRotSize g;
+    g.dw = (int)rint((double)R); g.dh = (int)rint((double)R * M_PI);
+    g.M = optimal_dft_size(g.dh); g.N = optimal_dft_size(g.dw);
+    g.sz = g.dh > g.dw ? g.dh : g.dw;
+    g.tab_bytes = sizeof(double) * (3 * (size_t)g.dh + g.dw) + sizeof(float) * g.dw;
+    return g;
+}
+
+// OpenCV's host tables of the forward warpPolar (Kmag and Kangle from the destination size) and createHanningWindow's factors:
+// cos, sin per row (2 dh doubles) | window per row (dh) | per column (dw) | radius per column (dw floats)
+static void fmt_rot_tables(const FmtRotSize &g, int R, unsigned char *tab)
+{
+    double *cs = (double *)tab, *wr = cs + 2 * g.dh, *wc = wr + g.dh;
+    roam_warp_polar_tables(g.dw, g.dh, (double)(2 * R) / 2.0, true, (float *)(wc + g.dw), cs);
+    roam_hanning_factors(g.dh, wr);
+    roam_hanning_factors(g.dw, wc);
+}
+
+// rotation half of nb pairs (src: nb sources, then nb targets): front end of fmt_batch.hip, correlation -> d_out[3 b] = {shift_x,
+// shift_y, response}.  d_tab: fmt_rot_tables on the device; d_f: 7 nb planes of M x N doubles; d_lp optional
+static int32_t fmt_rot_enqueue(roam_ctx *ctx, hipStream_t st, const FmtBatchSrc &src, int nb, int rows, int clip, int R, const FmtRotSize &g,
+                               const unsigned char *d_tab, float *d_small, float *d_cart, double *d_f, float *d_lp, double *d_pv, int *d_pi,
+                               double *d_out)
+{
+    const double *d_tabd = (const double *)d_tab;
+    const float *d_br = (const float *)(d_tabd + 3 * (size_t)g.dh + g.dw);
+    const PcPlanes p = pc_planes(d_f, (size_t)g.M * g.N * nb);
+    HIP_TRY(ctx, launch_fmt_batch_front(st, src, nb, rows, clip, R, g.dw, g.dh, g.M, g.N, d_tabd, d_br, d_small, d_cart, d_f, (int64_t)4 * nb, d_lp));
+    return pc_correlate(ctx, st, nb, g.M, g.N, d_f, p.a, p.F[1][0], d_pv, d_pi, d_out);         // the windowed images: sources, targets
+}
+
+// translation half of nb pairs: the Cartesian images (2 nb x S x S, S = 2 Rc), the sources turned by d_M (6 doubles per pair,
+// destination -> source), the window (d_win: S row factors, then S column factors), the correlation on M x M planes -> d_out[3 b] =
+// {dx, dy, response}.  d_rot optional: the turned sources before the window
+static int32_t fmt_trans_enqueue(roam_ctx *ctx, hipStream_t st, const FmtBatchSrc &src, int nb, int rows, int cols, int Rc, int M, float *d_cart,
+                                 const double *d_M, const double *d_win, double *d_f, float *d_rot, double *d_pv, int *d_pi, double *d_out)
+{
+    const PcPlanes p = pc_planes(d_f, (size_t)M * M * nb);
+    HIP_TRY(ctx, launch_fmtr_cart(st, src, 2 * nb, rows, cols, Rc, d_cart));
+    HIP_TRY(ctx, launch_fmtr_rotate_window(st, d_cart, 2 * Rc, M, M, nb, (int64_t)4 * nb, d_M, d_win, d_f, d_rot));
+    return pc_correlate(ctx, st, nb, M, M, d_f, p.a, p.F[1][0], d_pv, d_pi, d_out);             // the windowed images: turned sources, targets
+}
+
+// bytes of device memory per pair of the two halves on resident records (the planes of each half are counted: a chunk of the
+// registration is one chunk of the rotation pass too)
+static size_t fmt_rot_bytes_per_pair(int rows, int R)
+{
+    const FmtRotSize g = fmt_rot_size(R);
+    return 7 * sizeof(double) * (size_t)g.M * g.N + 2 * sizeof(float) * ((size_t)rows * R + (size_t)(2 * R) * (2 * R)) + 2 * sizeof(int32_t);
+}
+
 // ------------------------------------------------------------------------------------------------ batched rotation prior
 // FMT.getRotationUsingFMT for n pairs: the front end of fmt_batch.hip fills the planes, the correlation is the one above.  Per chunk of
 // nb pairs, 7 nb planes: sources' windowed images | work re, im | F1 re, im | F2 re, im - the targets' windowed images wait in the
 // F2 re planes, which nothing touches before their own row pass has consumed them.  One stream synchronisation per chunk.
 int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows, int clip, int R, double *out3, float *logpolar_out)
 {
-    const int W = 2 * R, dw = (int)rint((double)R), dh = (int)rint((double)R * M_PI);
-    const int M = optimal_dft_size(dh), N = optimal_dft_size(dw);
+    const FmtRotSize g = fmt_rot_size(R);
+    const int W = 2 * R, dw = g.dw, dh = g.dh, M = g.M, N = g.N;
     ARG_CHECK(ctx, M <= FFT_MAX_N && N <= FFT_MAX_N);
     const bool host = in.host_src != nullptr;
     const size_t nmn = (size_t)M * N, nsmall = (size_t)rows * R, ncart = (size_t)W * W, nlp = (size_t)dh * dw;
@@ -518,30 +580,21 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
     float *d_cart = (float *)roam_scratch(ctx, S_TMP5, sizeof(float) * ncart * 2 * chunk);
     float *d_lp = logpolar_out ? (float *)roam_scratch(ctx, S_TMP6, sizeof(float) * nlp * 2 * chunk) : nullptr;
     double *d_f = (double *)roam_scratch(ctx, S_TMP2, sizeof(double) * nmn * 7 * chunk);
-    const size_t tab_bytes = sizeof(double) * (3 * (size_t)dh + dw) + sizeof(float) * dw;
+    const size_t tab_bytes = g.tab_bytes;
     unsigned char *d_tab = (unsigned char *)roam_scratch(ctx, S_TMP1, tab_bytes);
     double *d_pv = (double *)roam_scratch(ctx, S_TMP0, sizeof(double) * (size_t)nblk * chunk);
     int *d_pi = (int *)roam_scratch(ctx, S_TMP3, sizeof(int) * (size_t)nblk * chunk);
     double *d_out = (double *)roam_scratch(ctx, S_OUT0, sizeof(double) * 3 * chunk);
     if ((host && !d_in) || (!host && !d_idx) || !d_small || !d_cart || (logpolar_out && !d_lp) || !d_f || !d_tab || !d_pv || !d_pi || !d_out)
         return ROAM_E_HIP;
-    // OpenCV's host tables of the forward warpPolar (Kmag and Kangle from the destination size) and createHanningWindow's factors
     std::vector<unsigned char> tab(tab_bytes);
-    {
-        double *cs = (double *)tab.data(), *wr = cs + 2 * dh, *wc = wr + dh;
-        roam_warp_polar_tables(dw, dh, (double)W / 2.0, true, (float *)(wc + dw), cs);
-        roam_hanning_factors(dh, wr);
-        roam_hanning_factors(dw, wc);
-    }
+    fmt_rot_tables(g, R, tab.data());
     HIP_TRY(ctx, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
-    const double *d_tabd = (const double *)d_tab;
-    const float *d_br = (const float *)(d_tabd + 3 * (size_t)dh + dw);
     std::vector<double> o(3 * chunk);
-    const int sz = dh > dw ? dh : dw;
-    const double log_base = exp(log((double)dh / 2.0) / (double)sz);
+    const int sz = g.sz;
+    const double log_base = fmt_log_base(g);
     for (size_t b0 = 0; b0 < (size_t)n; b0 += chunk) {
         const int nb = (int)(((size_t)n - b0) < chunk ? ((size_t)n - b0) : chunk);
-        const PcPlanes p = pc_planes(d_f, nmn * nb);
         FmtBatchSrc src;
         if (host) {
             const float *h[2] = {in.host_src, in.host_tgt};
@@ -554,8 +607,7 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
             HIP_TRY(ctx, hipMemcpyAsync(d_idx + nb, in.curr_idx + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, st));
             src = {in.pool, in.rec_bytes, in.rec_stride, in.payload_off, in.pool_f32 ? 0 : 1, d_idx};
         }
-        HIP_TRY(ctx, launch_fmt_batch_front(st, src, nb, rows, clip, R, dw, dh, M, N, d_tabd, d_br, d_small, d_cart, d_f, (int64_t)4 * nb, d_lp));
-        FFT_TRY(pc_correlate(ctx, nb, M, N, d_f, p.a, p.F[1][0], d_pv, d_pi, d_out));       // the windowed images: sources, targets
+        FFT_TRY(fmt_rot_enqueue(ctx, st, src, nb, rows, clip, R, g, d_tab, d_small, d_cart, d_f, d_lp, d_pv, d_pi, d_out));
         HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
         if (logpolar_out) {
             HIP_TRY(ctx, hipMemcpyAsync(logpolar_out + b0 * nlp, d_lp, sizeof(float) * nlp * nb, hipMemcpyDeviceToHost, st));
@@ -564,8 +616,8 @@ int32_t roam_fmt_batch_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows,
         }
         HIP_TRY(ctx, hipStreamSynchronize(st));
         for (int i = 0; i < nb; i++) {                       // FMT.py:84-90: the shifts as an angle and a scale
-            out3[3 * (b0 + i)] = normalize_angle(-o[3 * i + 1] * 2.0 * M_PI / (double)sz);
-            out3[3 * (b0 + i) + 1] = pow(log_base, o[3 * i]);
+            out3[3 * (b0 + i)] = roam_normalize_angle(-o[3 * i + 1] * 2.0 * M_PI / (double)sz);
+            out3[3 * (b0 + i) + 1] = fmt_scale(log_base, o[3 * i]);
             out3[3 * (b0 + i) + 2] = o[3 * i + 2];
         }
     }
@@ -636,9 +688,7 @@ int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int ro
     const size_t nmn = (size_t)M * N, ncart = (size_t)S * S, nin = host ? (size_t)rows * in.cols : 0;
     // the rotation half per pair, as roam_fmt_batch_run counts it for resident images, and this half (the shared planes count twice):
     // a chunk of this size is one chunk there too
-    const int Wr = 2 * R, dwr = (int)rint((double)R), dhr = (int)rint((double)R * M_PI);
-    const size_t per_rot = 7 * sizeof(double) * (size_t)optimal_dft_size(dhr) * optimal_dft_size(dwr)
-                           + 2 * sizeof(float) * ((size_t)rows * R + (size_t)Wr * Wr) + 2 * sizeof(int32_t);
+    const size_t per_rot = fmt_rot_bytes_per_pair(rows, R);
     const size_t per_reg = 7 * sizeof(double) * nmn + sizeof(float) * (2 * ncart + (cart_out ? ncart : 0) + 2 * nin) + 6 * sizeof(double)
                            + 2 * sizeof(int32_t);
     const size_t chunk = pc_chunk(per_rot + per_reg, n, 32767, true);        // 2 chunk images in grid.z
@@ -686,12 +736,9 @@ int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int ro
         int *d_pi = (int *)roam_scratch(ctx, S_TMP3, sizeof(int) * (size_t)nblk * chunk);
         double *d_out = (double *)roam_scratch(ctx, S_OUT0, sizeof(double) * 3 * chunk);
         if (!d_f || !d_win || !d_pv || !d_pi || !d_out) return ROAM_E_HIP;
-        const PcPlanes p = pc_planes(d_f, nmn * nb);
         HIP_TRY(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(double) * win.size(), hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(d_M, Mh.data(), sizeof(double) * 6 * nb, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, launch_fmtr_cart(st, src, 2 * nb, rows, in.cols, Rc, d_cart));
-        HIP_TRY(ctx, launch_fmtr_rotate_window(st, d_cart, S, M, N, nb, (int64_t)4 * nb, d_M, d_win, d_f, d_rot));
-        FFT_TRY(pc_correlate(ctx, nb, M, N, d_f, p.a, p.F[1][0], d_pv, d_pi, d_out));           // the windowed images: turned sources, targets
+        FFT_TRY(fmt_trans_enqueue(ctx, st, src, nb, rows, in.cols, Rc, M, d_cart, d_M, d_win, d_f, d_rot, d_pv, d_pi, d_out));
         HIP_TRY(ctx, hipMemcpyAsync(o.data(), d_out, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st));
         if (cart_out) {
             HIP_TRY(ctx, hipMemcpyAsync(cart_out + b0 * ncart, d_rot, sizeof(float) * ncart * nb, hipMemcpyDeviceToHost, st));
@@ -725,6 +772,131 @@ extern "C" int32_t roam_fmt_register_batch_f32(roam_ctx *ctx, const float *src, 
     in.host_src = src; in.host_tgt = tgt; in.row_stride = row_stride; in.image_stride = n == 1 ? (int64_t)rows * row_stride : image_stride;
     in.cols = cols;
     return roam_fmt_register_run(ctx, in, n, rows, clip, R, Rc, out6, cart_out);
+}
+
+// ------------------------------------------------------------------------------------------------ in-step registration
+// The registration as a part of roam_engine_step (roam_engine_set_auto_prior): the two cores above with fmtr_angle_matrix_kernel between
+// them and fmtr_prior_kernel behind them, on a stream the engine gives, in buffers carved from one slab the engine allocated.  Nothing
+// here synchronises or allocates once roam_fmt_auto_init has returned.
+struct FmtAuto {
+    FmtAutoCfg cfg;
+    FmtAutoPlan plan;
+    FmtRotSize g;
+    int Mt;                             // DFT side of the translation half
+    int32_t *h_idx = nullptr;           // pinned: 4 slots of 3 lanes ints (the chunks' index lists, then pair_of)
+    int32_t *d_idx = nullptr;           // the same ring on the device
+    unsigned char *d_tab = nullptr;
+    double *d_win = nullptr, *d_f = nullptr, *d_pv = nullptr, *d_rot3 = nullptr, *d_trans3 = nullptr, *d_ang = nullptr, *d_M = nullptr;
+    int *d_pi = nullptr;
+    float *d_small = nullptr, *d_cart_r = nullptr, *d_cart_t = nullptr;
+};
+
+// the slab's parts in order, each on a 256-byte boundary; a null slab only counts
+static size_t fmt_auto_carve(FmtAuto *a, const FmtAutoCfg &c, size_t chunk, uint8_t *slab)
+{
+    const FmtRotSize g = fmt_rot_size(c.R);
+    const int S = 2 * c.Rc, Mt = optimal_dft_size(S);
+    const size_t nmn_r = (size_t)g.M * g.N, nmn_t = (size_t)Mt * Mt, nmn = nmn_r > nmn_t ? nmn_r : nmn_t;
+    const size_t nblk = (size_t)std::max(pc_peak_grid(nmn_r).nblk, pc_peak_grid(nmn_t).nblk), L = (size_t)c.lanes;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { uint8_t *p = slab ? slab + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    uint8_t *idx = take(sizeof(int32_t) * 4 * 3 * L), *tab = take(g.tab_bytes), *win = take(sizeof(double) * 2 * S);
+    uint8_t *f = take(sizeof(double) * 7 * nmn * chunk), *pv = take(sizeof(double) * nblk * chunk), *pi = take(sizeof(int) * nblk * chunk);
+    uint8_t *small = take(sizeof(float) * (size_t)c.rows * c.R * 2 * chunk), *cr = take(sizeof(float) * (size_t)(2 * c.R) * (2 * c.R) * 2 * chunk);
+    uint8_t *ct = take(sizeof(float) * (size_t)S * S * 2 * chunk);
+    uint8_t *r3 = take(sizeof(double) * 3 * L), *t3 = take(sizeof(double) * 3 * L), *ang = take(sizeof(double) * L), *M = take(sizeof(double) * 6 * L);
+    if (a) {
+        a->g = g; a->Mt = Mt;
+        a->d_idx = (int32_t *)idx; a->d_tab = tab; a->d_win = (double *)win; a->d_f = (double *)f; a->d_pv = (double *)pv; a->d_pi = (int *)pi;
+        a->d_small = (float *)small; a->d_cart_r = (float *)cr; a->d_cart_t = (float *)ct;
+        a->d_rot3 = (double *)r3; a->d_trans3 = (double *)t3; a->d_ang = (double *)ang; a->d_M = (double *)M;
+    }
+    return off;
+}
+
+int32_t roam_fmt_auto_plan(roam_ctx *ctx, const FmtAutoCfg &c, FmtAutoPlan *plan)
+{
+    // what roam_engine_fmt_register refuses
+    ARG_CHECK(ctx, c.lanes >= 1 && c.rows >= 8 && c.rows <= 16384 && c.cols >= 2 && c.cols <= 16384 && c.clip >= 1 && c.clip <= c.cols);
+    ARG_CHECK(ctx, c.R >= ROAM_FMT_MIN_R && c.R <= ROAM_FMT_MAX_R && c.Rc >= 1 && 2 * c.Rc <= FFT_MAX_N);
+    ARG_CHECK(ctx, c.min_rot >= 0.0 && c.min_rot <= 1e300 && c.min_trans >= 0.0 && c.min_trans <= 1e300);       // (NaN fails them too)
+    const FmtRotSize g = fmt_rot_size(c.R);
+    ARG_CHECK(ctx, g.M <= FFT_MAX_N && g.N <= FFT_MAX_N);
+    const int S = 2 * c.Rc, Mt = optimal_dft_size(S);
+    // as roam_fmt_register_run counts a pair on resident records
+    const size_t per_reg = 7 * sizeof(double) * (size_t)Mt * Mt + sizeof(float) * 2 * (size_t)S * S + 6 * sizeof(double) + 2 * sizeof(int32_t);
+    plan->per_pair = fmt_rot_bytes_per_pair(c.rows, c.R) + per_reg;
+    plan->chunk = pc_chunk(plan->per_pair, (size_t)c.lanes, 32767, true);
+    plan->slab_bytes = fmt_auto_carve(nullptr, c, plan->chunk, nullptr);
+    plan->sz = g.sz;
+    plan->log_base = fmt_log_base(g);
+    return ROAM_OK;
+}
+
+double roam_fmt_scale(double log_base, double shift_x) { return fmt_scale(log_base, shift_x); }
+
+void roam_fmt_auto_free(FmtAuto *a)
+{
+    if (!a) return;
+    if (a->h_idx) (void)hipHostFree(a->h_idx);
+    delete a;
+}
+
+int32_t roam_fmt_auto_init(roam_ctx *ctx, const FmtAutoCfg &c, const FmtAutoPlan &plan, uint8_t *slab, FmtAuto **out)
+{
+    FmtAuto *a = new (std::nothrow) FmtAuto();
+    if (!a) { ROAM_SET_ERR(ctx, "auto prior: out of host memory"); return ROAM_E_HIP; }
+    a->cfg = c; a->plan = plan;
+    fmt_auto_carve(a, c, plan.chunk, slab);
+    const int S = 2 * c.Rc;
+    std::vector<unsigned char> tab(a->g.tab_bytes);
+    std::vector<double> win(2 * (size_t)S);
+    fmt_rot_tables(a->g, c.R, tab.data());
+    roam_hanning_factors(S, win.data());
+    roam_hanning_factors(S, win.data() + S);
+    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&a->h_idx), sizeof(int32_t) * 4 * 3 * (size_t)c.lanes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemcpyAsync(a->d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(a->d_win, win.data(), sizeof(double) * win.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        ROAM_SET_ERR(ctx, "auto prior: staging or table upload failed: %s", hipGetErrorString(e));
+        roam_fmt_auto_free(a);
+        return ROAM_E_HIP;
+    }
+    for (int n : {a->g.M, a->g.N, a->Mt})                  // now, not at the first step
+        if (!fft_twiddles(ctx, n)) { roam_fmt_auto_free(a); return ROAM_E_HIP; }
+    *out = a;
+    return ROAM_OK;
+}
+
+int32_t roam_fmt_auto_enqueue(roam_ctx *ctx, FmtAuto *a, hipStream_t st, const FmtBatchIn &pool, int slot4, int npairs, const int32_t *prev,
+                              const int32_t *curr, const int32_t *pair_of, uint8_t *prior_slot, FmtPriorRec *rec_slot)
+{
+    const FmtAutoCfg &c = a->cfg;
+    const size_t L = (size_t)c.lanes, chunk = a->plan.chunk;
+    int32_t *h = a->h_idx + (size_t)slot4 * 3 * L, *d = a->d_idx + (size_t)slot4 * 3 * L;
+    for (size_t p0 = 0; p0 < (size_t)npairs; p0 += chunk) {          // chunk by chunk: the sources' records, then the targets'
+        const size_t nb = std::min(chunk, (size_t)npairs - p0);
+        memcpy(h + 2 * p0, prev + p0, sizeof(int32_t) * nb);
+        memcpy(h + 2 * p0 + nb, curr + p0, sizeof(int32_t) * nb);
+    }
+    memcpy(h + 2 * L, pair_of, sizeof(int32_t) * L);
+    HIP_TRY(ctx, hipMemcpyAsync(d, h, sizeof(int32_t) * 3 * L, hipMemcpyHostToDevice, st));
+    const double cc = (double)(float)c.Rc;                   // getRotationMatrix2D's centre (w / 2, h / 2) as a cv::Point2f
+    for (size_t p0 = 0; p0 < (size_t)npairs; p0 += chunk) {
+        const int nb = (int)std::min(chunk, (size_t)npairs - p0);
+        const FmtBatchSrc src = {pool.pool, pool.rec_bytes, pool.rec_stride, pool.payload_off, 1, d + 2 * p0};
+        FFT_TRY(fmt_rot_enqueue(ctx, st, src, nb, c.rows, c.clip, c.R, a->g, a->d_tab, a->d_small, a->d_cart_r, a->d_f, nullptr, a->d_pv, a->d_pi,
+                                a->d_rot3 + 3 * p0));
+        HIP_TRY(ctx, launch_fmtr_angle_matrix(st, a->d_rot3 + 3 * p0, nb, a->plan.sz, cc, a->d_ang + p0, a->d_M + 6 * p0));
+        FFT_TRY(fmt_trans_enqueue(ctx, st, src, nb, c.rows, c.cols, c.Rc, a->Mt, a->d_cart_t, a->d_M + 6 * p0, a->d_win, a->d_f, nullptr, a->d_pv,
+                                  a->d_pi, a->d_trans3 + 3 * p0));
+    }
+    // the tracker's grid against the registration's: FMT.flowPriorFromFMT's s = (cols // 2) / (cols // cart_downsample)
+    FmtPriorArgs pa = {d + 2 * L, a->d_rot3, a->d_ang, a->d_trans3, c.lanes, cc, (double)(c.cols / 2) / (double)c.Rc, c.min_rot, c.min_trans,
+                       prior_slot, rec_slot};
+    HIP_TRY(ctx, launch_fmtr_prior(st, pa));
+    return ROAM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ test / measurement entries
@@ -789,10 +961,10 @@ extern "C" int32_t roam_debug_fft2_f64(roam_ctx *ctx, const double *re_in, const
     HIP_TRY(ctx, hipMemcpyAsync(ar, re_in, sizeof(double) * nmn, hipMemcpyHostToDevice, st));
     if (im_in) HIP_TRY(ctx, hipMemcpyAsync(ai, im_in, sizeof(double) * nmn, hipMemcpyHostToDevice, st));
     else HIP_TRY(ctx, hipMemsetAsync(ai, 0, sizeof(double) * nmn, st));
-    FFT_TRY(fft_rows(ctx, ar, ai, ar, ai, M, N, inverse != 0));
-    FFT_TRY(fft_transpose(ctx, ar, ai, 1, M, N, br, bi));
-    FFT_TRY(fft_rows(ctx, br, bi, br, bi, N, M, inverse != 0));
-    FFT_TRY(fft_transpose(ctx, br, bi, 1, N, M, ar, ai));
+    FFT_TRY(fft_rows(ctx, st, ar, ai, ar, ai, M, N, inverse != 0));
+    FFT_TRY(fft_transpose(ctx, st, ar, ai, 1, M, N, br, bi));
+    FFT_TRY(fft_rows(ctx, st, br, bi, br, bi, N, M, inverse != 0));
+    FFT_TRY(fft_transpose(ctx, st, br, bi, 1, N, M, ar, ai));
     HIP_TRY(ctx, hipMemcpyAsync(re_out, ar, sizeof(double) * nmn, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(im_out, ai, sizeof(double) * nmn, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -821,22 +993,22 @@ extern "C" int32_t roam_time_fft2(roam_ctx *ctx, int32_t rows, int32_t cols, int
         if (rep == 0) (void)hipEventRecord(e0, st);
         if (what == ROAM_TIME_FFT_FIVE) {
             for (int k = 0; k < 2 && rc == ROAM_OK; k++) {
-                rc = fft_rows(ctx, p.a, nullptr, p.tr, p.ti, M, N, false);
-                if (rc == ROAM_OK) rc = fft_transpose(ctx, p.tr, p.ti, 1, M, N, p.F[k][0], p.F[k][1]);
-                if (rc == ROAM_OK) rc = fft_rows(ctx, p.F[k][0], p.F[k][1], p.F[k][0], p.F[k][1], N, M, false);
+                rc = fft_rows(ctx, st, p.a, nullptr, p.tr, p.ti, M, N, false);
+                if (rc == ROAM_OK) rc = fft_transpose(ctx, st, p.tr, p.ti, 1, M, N, p.F[k][0], p.F[k][1]);
+                if (rc == ROAM_OK) rc = fft_rows(ctx, st, p.F[k][0], p.F[k][1], p.F[k][0], p.F[k][1], N, M, false);
             }
-            if (rc == ROAM_OK) rc = fft_rows(ctx, p.tr, p.ti, p.tr, p.ti, N, M, true);
-            if (rc == ROAM_OK) rc = fft_transpose(ctx, p.tr, p.ti, 1, N, M, p.F[0][0], p.F[0][1]);
-            if (rc == ROAM_OK) rc = fft_rows(ctx, p.F[0][0], p.F[0][1], p.a, nullptr, M, N, true);
+            if (rc == ROAM_OK) rc = fft_rows(ctx, st, p.tr, p.ti, p.tr, p.ti, N, M, true);
+            if (rc == ROAM_OK) rc = fft_transpose(ctx, st, p.tr, p.ti, 1, N, M, p.F[0][0], p.F[0][1]);
+            if (rc == ROAM_OK) rc = fft_rows(ctx, st, p.F[0][0], p.F[0][1], p.a, nullptr, M, N, true);
         } else if (what == ROAM_TIME_DFT_FIVE) {
             for (int k = 0; k < 2; k++) (void)launch_fmt_dft2(st, p.a, nullptr, M, N, -1.0, p.tr, p.ti, p.F[k][0], p.F[k][1]);
             (void)launch_fmt_dft2(st, p.tr, p.ti, M, N, 1.0, p.F[0][0], p.F[0][1], p.a, nullptr);
         } else if (what == ROAM_TIME_FFT_ROWS) {
-            rc = fft_rows(ctx, p.tr, p.ti, p.tr, p.ti, M, N, false);
+            rc = fft_rows(ctx, st, p.tr, p.ti, p.tr, p.ti, M, N, false);
         } else if (what == ROAM_TIME_FFT_TRANSPOSE) {
-            rc = fft_transpose(ctx, p.tr, p.ti, 1, M, N, p.F[0][0], p.F[0][1]);
+            rc = fft_transpose(ctx, st, p.tr, p.ti, 1, M, N, p.F[0][0], p.F[0][1]);
         } else {
-            rc = fft_rows(ctx, p.tr, p.ti, p.tr, p.ti, N, M, false);
+            rc = fft_rows(ctx, st, p.tr, p.ti, p.tr, p.ti, N, M, false);
         }
     }
     (void)hipEventRecord(e1, st);

@@ -248,8 +248,66 @@ hipError_t launch_fmtr_rotate_window(hipStream_t st, const float *cart, int S, i
                                      const double *win, double *planes, float *rot_out);
 // warpaffine.hip: the inverse (destination -> source) of cv2.getRotationMatrix2D((cx, cy), angle_deg, 1.0), host float64
 void roam_rotation_inverse_map(double cx, double cy, double angle_deg, double *Minv);
+// utils.normalize_angles: (th + pi) % (2 pi) - pi (Python modulo).  Host and device: fmod is exact in IEEE arithmetic (its result is
+// representable), the other operations are single rounded ones, so both sides give the same bits
+__host__ __device__ inline double roam_normalize_angle(double th)
+{
+    th = fmod(th + M_PI, 2.0 * M_PI);
+    if (th < 0) th += 2.0 * M_PI;
+    return th - M_PI;
+}
 // fft.hip: the registration of n pairs on ctx->stream, blocking: per chunk of pairs roam_fmt_batch_run (one synchronisation: the
 // angles come to the host, which makes the matrices), then the Cartesian images, the turn, the window and the second correlation (one
 // more).  `in` as for roam_fmt_batch_run, in.cols = the polar width the Cartesian half reads (all of it); Rc = in.cols / cart_downsample.
 // out6: n x 6 {angle_rad, scale, rot_response, dx, dy, trans_response}; cart_out: optional, 2 n x 2Rc x 2Rc (turned sources, targets)
 int32_t roam_fmt_register_run(roam_ctx *ctx, const FmtBatchIn &in, int n, int rows, int clip, int R, int Rc, double *out6, float *cart_out);
+
+// ---------------------------------------------------------------- in-step motion prior (roam_engine_set_auto_prior)
+// One record per lane and step, written by fmtr_prior_kernel: v = {shift_x, shift_y, rot_response, angle, dx, dy, trans_response}
+// (NaN for a lane without a registration), the affine the tracker was given, source 0 = unseeded, 1 = in-step registration
+struct FmtPriorRec {
+    double v[7];
+    float affine[6];
+    uint8_t source, pad[7];
+};
+// fmt_register.hip: the two kernels that stand in for the host between and behind the two correlations of the in-step pass.
+// launch_fmtr_angle_matrix: pair i of n reads rot3 + 3 i = {shift_x, shift_y, response} of the rotation correlation and writes its
+// angle (ang + i; sz = the larger side of the log-polar image) and the inverse rotation about (c, c) (Minv + 6 i) that
+// launch_fmtr_rotate_window reads.
+hipError_t launch_fmtr_angle_matrix(hipStream_t st, const double *rot3, int n, int sz, double c, double *ang, double *Minv);
+// launch_fmtr_prior: lane b of B with pair_of[b] = p >= 0 takes rot3 / ang / trans3 of pair p, makes FMT.flowPriorFromFMT's affine
+// (rotation about (c, c), translation scaled by s) and writes it with its use byte into prior_slot (B x 6 f32, then B bytes: what
+// launch_klt reads) and, with the numbers, into rec[b]; pair_of[b] < 0: the identity, use 0, NaN numbers
+struct FmtPriorArgs {
+    const int32_t *pair_of;
+    const double *rot3, *ang, *trans3;
+    int B;
+    double c, s, min_rot, min_trans;
+    uint8_t *prior_slot;
+    FmtPriorRec *rec;
+};
+hipError_t launch_fmtr_prior(hipStream_t st, const FmtPriorArgs &a);
+
+// fft.hip: the in-step registration pass.  roam_fmt_auto_plan is host arithmetic only (sizes, bytes per pair, pairs per chunk, the
+// bytes of the one device slab the pass lives in); roam_fmt_auto_init carves the caller's slab, uploads the host tables of both halves
+// and makes the twiddle tables (blocking, on ctx->stream); roam_fmt_auto_enqueue only enqueues on st: the index lists of the step
+// (staged in pinned memory of the pass, ring slot slot4), per chunk the rotation half, fmtr_angle_matrix_kernel and the translation
+// half, then fmtr_prior_kernel for all lanes.
+struct FmtAutoCfg {
+    int rows, cols, clip, R, Rc, lanes;          // cols: the record's clipped width (the Cartesian half reads all of it)
+    double min_rot, min_trans;
+};
+struct FmtAutoPlan {
+    size_t per_pair, chunk, slab_bytes;
+    int sz;                                      // larger side of the log-polar image: shift_y -> angle
+    double log_base;                             // shift_x -> scale
+};
+struct FmtAuto;
+int32_t roam_fmt_auto_plan(roam_ctx *ctx, const FmtAutoCfg &cfg, FmtAutoPlan *plan);
+int32_t roam_fmt_auto_init(roam_ctx *ctx, const FmtAutoCfg &cfg, const FmtAutoPlan &plan, uint8_t *slab, FmtAuto **out);
+void roam_fmt_auto_free(FmtAuto *a);
+// prev / curr: npairs pool indices (host), pair_of: lanes (host); pool as FmtBatchIn describes it; rec_slot: lanes records (device)
+int32_t roam_fmt_auto_enqueue(roam_ctx *ctx, FmtAuto *a, hipStream_t st, const FmtBatchIn &pool, int slot4, int npairs, const int32_t *prev,
+                              const int32_t *curr, const int32_t *pair_of, uint8_t *prior_slot, FmtPriorRec *rec_slot);
+// FMT.py:84-90 on the host, the blocking pass's own expressions: a record's raw shifts -> angle (what the device wrote) and scale
+double roam_fmt_scale(double log_base, double shift_x);

@@ -35,28 +35,14 @@ __global__ __launch_bounds__(WA_TILE_X * WA_TILE_Y) void warp_affine_kernel(cons
     dst[(img * dh + y) * dw + x] = cv_remap(tap, X, Y);
 }
 
-// OpenCV's invertAffineTransform as warpAffine applies it in place (no fused multiply-add: roam_internal.h)
-static void wa_invert(const double *in, double *M)
-{
-    for (int k = 0; k < 6; k++) M[k] = in[k];
-    double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0 ? 1. / D : 0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] *= -D;
-    M[3] *= -D; M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5];
-    const double b2 = -M[3] * M[2] - M[4] * M[5];
-    M[2] = b1; M[5] = b2;
-}
-
 // rotateImg's matrix (FMT.py:93-100) as warpAffine applies it: cv2.getRotationMatrix2D((cx, cy), angle_deg, 1.0) in float64 - the centre is
-// a cv::Point2f, the caller passes float32 values - inverted by wa_invert -> Minv[6], destination -> source
+// a cv::Point2f, the caller passes float32 values - inverted by cvmap.h's cv_invert_affine -> Minv[6], destination -> source
 void roam_rotation_inverse_map(double cx, double cy, double angle_deg, double *Minv)
 {
     const double rad = angle_deg * M_PI / 180.0;
-    const double a = cos(rad), b = sin(rad);
-    const double M[6] = {a, b, (1 - a) * cx - b * cy, -b, a, b * cx + (1 - a) * cy};
-    wa_invert(M, Minv);
+    double M[6];
+    cv_rotation_matrix(cos(rad), sin(rad), cx, cy, M);
+    cv_invert_affine(M, Minv);
 }
 
 static void wa_launch(hipStream_t st, const float *d_in, int n, int rows, int cols, const double *d_M, int m_count, float *d_out, int dw,
@@ -76,7 +62,7 @@ static int32_t wa_upload_matrices(roam_ctx *ctx, const double *M, int m_count, i
     inv.resize((size_t)m_count * 6);
     for (int i = 0; i < m_count; i++) {
         if (flags & ROAM_WARP_AFFINE_INVERSE_MAP) memcpy(&inv[(size_t)i * 6], M + (size_t)i * 6, sizeof(double) * 6);
-        else wa_invert(M + (size_t)i * 6, &inv[(size_t)i * 6]);
+        else cv_invert_affine(M + (size_t)i * 6, &inv[(size_t)i * 6]);
     }
     double *d = (double *)roam_scratch(ctx, S_TMP0, sizeof(double) * inv.size());
     if (!d) return ROAM_E_HIP;

@@ -157,6 +157,32 @@ class Engine:
         a, u = _ffi.motion_prior_args(affine, use, self.lanes)
         self.ctx.check(self.lib.roam_engine_set_motion_prior(self.ctx.h, _ffi._ptr(a), _ffi._ptr(u)))
 
+    def set_auto_prior(self, on=True, clip_px=1012, downsample=10, cart_downsample=20, min_rot_response=0.0, min_trans_response=0.0):
+        """The motion prior as a mode of the engine (roam_engine_set_auto_prior): while it is on, every step registers each lane's
+        previous scan against its current one on the device (fmt_register's pass on the pool records) and seeds the lane's tracker
+        with FMT.flowPriorFromFMT's affine - no host round trip, nothing in a step synchronises.  Lanes whose rotation / translation
+        response is below min_rot_response / min_trans_response run unseeded (0: no gate).  A prior set with set_motion_prior still
+        wins for its step.  This call is blocking (it waits for the enqueued steps and allocates the pass's buffers); on=False
+        switches the mode off and frees them.  ValueError (TypeError for a cart_downsample that is no integer) before any device call
+        for what _ffi.auto_prior_args refuses."""
+        if not on:
+            self.ctx.check(self.lib.roam_engine_set_auto_prior(self.ctx.h, None))
+            return
+        cfg = _ffi.auto_prior_args(self.cfg.clip, self.rows, clip_px, downsample, cart_downsample, min_rot_response, min_trans_response)
+        self.ctx.check(self.lib.roam_engine_set_auto_prior(self.ctx.h, C.byref(cfg)))
+
+    def step_prior(self, step: int = None):
+        """the in-step prior of the last step, or of step `step` (0-based; only that step is waited for, as results(step)) -> structured
+        array (lanes,) of _ffi.PRIOR_RECORD: out6 = (angle rad, scale, rotation response, dx, dy, translation response) as fmt_register
+        gives them (NaN for a lane that was not registered), affine (2, 3) float32 = the prior the lane's tracker was offered, source
+        0 = unseeded, 1 = in-step registration, 2 = the caller's set_motion_prior"""
+        step = self.steps_enqueued() - 1 if step is None else int(step)
+        out = np.zeros(self.lanes, _ffi.PRIOR_RECORD)
+        o6, aff, src = np.empty((self.lanes, 6), np.float64), np.empty((self.lanes, 6), np.float32), np.empty(self.lanes, np.uint8)
+        self.ctx.check(self.lib.roam_engine_step_prior(self.ctx.h, step, _ffi._ptr(o6), _ffi._ptr(aff), _ffi._ptr(src), self.lanes))
+        out["out6"], out["affine"], out["source"] = o6, aff.reshape(-1, 2, 3), src
+        return out
+
     def synchronize(self):
         self.ctx.check(self.lib.roam_synchronize(self.ctx.h))
 
