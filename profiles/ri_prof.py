@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """where a column wave and the row wave of rt_integral_kernel spend a phase (a -DRI_PROF build: ROAM_LIB=variants/libroam_riprof.so):
-s_memtime ticks (100 MHz) summed over the workgroups of 512 detections, wave 0 and the row wave of each"""
+s_memtime ticks (100 MHz) summed over the workgroups of 512 detections, column wave 0 (the top quarter of a 64 x 64 phase) and the row wave of each"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -23,10 +23,10 @@ lib.roam_debug_integral_prof(out, 1)
 ms, by = eng.time_kernel("doh_integral", 3)
 lib.roam_debug_integral_prof(out, 0)
 v = np.array(list(out), float)
-names = ["col: loop head", "col: barrier wait", "col: C (tile -> HBM)", "col: A1 (box + taps)", "col: A2 (column sums -> tile)", "row: loop head", "row: barrier wait", "row: B = rest"]
+names = ["col: loop head", "col: barrier wait", "col: A2 (base + column sums -> tile)", "col: A1 (box + taps + quarter total)"]
 print(f"doh_integral {ms:.2f} ms per {N}")
-tot_c = v[:5].sum()
-for k in range(5): print(f"  {names[k]:32s} {100 * v[k] / tot_c:5.1f} %")
-tot_r = v[8 + 5] + v[8 + 6]
-print(f"  row wave: loop body (B + head) {100 * v[8 + 5] / tot_r:5.1f} %   barrier wait {100 * v[8 + 6] / tot_r:5.1f} %")
+tot_c = v[:4].sum()
+for k in range(4): print(f"  {names[k]:32s} {100 * v[k] / tot_c:5.1f} %")
+tot_r = v[8 + 5] + v[8 + 6] + v[8 + 7]
+print(f"  row wave: B (the chain) {100 * v[8 + 7] / tot_r:5.1f} %   C (tile -> HBM) + loop head {100 * v[8 + 5] / tot_r:5.1f} %   barrier wait {100 * v[8 + 6] / tot_r:5.1f} %")
 eng.close(); ctx.close()

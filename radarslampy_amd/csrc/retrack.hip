@@ -3,7 +3,8 @@
 // roam_engine_step, without a host round trip.  Per flagged lane ("slot" = one detection):
 //   K1+K2 rt_integral    the float64 integral image in ONE sweep: float32 Cartesian pixel from the polar record through the engine's
 //                        sampling map (the arithmetic of warp.hip, never written to memory; the polar footprint of a wave's patch
-//                        staged in LDS), column cumsum in registers, row cumsum through double-buffered LDS tiles - both in NumPy's
+//                        staged in LDS), phases of 64 rows x 64 columns: column cumsum by four stacked waves of 16 rows each (exact
+//                        in float64 in any order), row cumsum by a fifth wave through double-buffered LDS tiles in NumPy's
 //                        sequential order, image written once.  Chunks of fewer than RT_TWO_PASS_SLOTS detections (and a lane's
 //                        first detection) take rt_integ_cols + rt_integ_rows instead: thousands of threads per detection
 //   K3 rt_det_strip      box-filter Hessian determinants of both live layers (sigma 5.005 / 10, sizes 15 / 30; the sigma 0.01 layer

@@ -3,8 +3,8 @@
 
 // ------------------------------------------------------------------------------------------------ K1 / K2: integral image
 // Two ways to the integral image, chosen on the device by the number of detections of the chunk (only the device knows it):
-//   * rt_integral_kernel (below): one workgroup per detection, the image written once - 12.7 us per detection at 512, but a chain of
-//     1016 dependent phases per detection: 6.5 ms per chunk whatever its size
+//   * rt_integral_kernel (below): one workgroup per detection, the image written once, but a chain of ~950 dependent phases
+//     (64 rows x 64 columns each) per detection: milliseconds per chunk whatever its size
 //   * rt_integ_cols_kernel (+ the band fix-up by its last workgroups) + rt_integ_rows_kernel: thousands of threads per detection, three times the
 //     traffic, 0.26 ms for one alone
 // Both are launched; the one whose regime it is not returns at once.
@@ -185,45 +185,53 @@ __global__ __launch_bounds__(256) void rt_integ_rows_kernel(RtArgs a, int first,
 }
 
 // ------------------------------------------------------------------------------------------------ K1+K2 fused: one sweep
-// One workgroup per detection walks the image in bands of RI_ROWS rows and, inside a band, in groups of RI_WAVES 64-column tiles.
-// For every (band, group) "phase" i:
-//   A(i)  column waves, lane = column: the band's RI_ROWS pixels of the column (computed from the polar record, see rt_pixel) are
-//         added one after the other to the column's running sum (a register, carried from band to band) -> tile[row][column]
-//   B(i)  the row wave, lane = row: the row's running sum walks through the group's tiles column by column (carried in a register
-//         from group to group) - the second cumsum, in place
-//   C(i)  every column wave writes its tile to the integral image
-// The tiles are double-buffered, so that between two barriers the column waves run C(i-1) and A(i+1) while the row wave runs B(i):
-// A is bound by load latency, B by the latency of 64 x RI_WAVES dependent float64 additions, and they hide each other.
-// Both cumulative sums keep NumPy's sequential order; the float64 image is written ONCE (32.8 MB per detection instead of the
-// 98.6 MB moved by the two-pass kernels above, which stay for small chunks - see rt_one_sweep - and for image sizes above 2048).
-#ifndef RI_ROWS
-#define RI_ROWS 16
-#endif
-#ifndef RI_WAVES
-#define RI_WAVES 4
-#endif
-#define RI_GROUPS (2048 / (64 * RI_WAVES))
-// (round 6, measured and dropped: ONE tile buffer with the taps of A(i + 1) beside B(i), with bands of 16 or of 32 rows - bit-identical,
-// no faster in the step; more waves per CU make this kernel slower, not faster: profiles/r06_detection_experiments.txt)
-#define RI_PHL_MAX 1024                     // phases of the largest image of the one-sweep kernel (128 bands x 8 groups)
+// One workgroup per detection walks the image in bands of RI_ROWS = 64 rows and, inside a band, tile by tile (64 columns): a "phase" is
+// one (band, tile), 64 x 64 pixels.  The four column waves are stacked: wave w owns the band's rows 16 w .. 16 w + 15 (a "quarter"),
+// lane = column; the fifth wave is the row wave, lane = row of the band.  For every phase i:
+//   A1(i) column waves: the quarter's 16 pixels of the lane's column (computed from the polar record, see rt_pixel) -> v[], their
+//         sum -> tot[w][column]; the wave that owns the tile's column sums (tile & 3) publishes what lies above the band -> cb[column]
+//   A2(i) column waves: cb + the totals of the quarters above + the quarter's pixels one after the other -> tile[row][column]; the
+//         owner adds the four totals to its running sum.  (Every partial column sum is EXACT in float64 in any order - see the
+//         column pass above - so the quarters change no bit of NumPy's sequential cumsum.)
+//   B(i)  the row wave: the row's running sum walks through the tile's 64 columns (carried in a register from tile to tile) - the
+//         second cumsum, in place, in NumPy's order: the only rounding chain of the kernel, 64 dependent additions a phase
+//   C(i)  the row wave, two rows per instruction: the quarters of the tile that are read go to the integral image
+// Tiles and tot / cb are double-buffered by the phase's parity; one barrier per phase.  Between barriers i and i + 1 the column waves
+// run A2(i), then A1(i+1), on buffer i & 1, and the row wave B(i-1), then C(i-1), on the other buffer; tot / cb of phase i are read while
+// those of phase i + 1 are written.  (With C in the column waves - every wave its own quarter, two phases behind - they were what a
+// phase waited for: taps 66 %, C 16 % of their time, the row wave idle for 79 % of it.)
+// Before that a phase was 16 rows x 256 columns (the column waves side by side): the same pixels, but 256 dependent additions and
+// 128 LDS instructions of the row wave per phase with 16 of its lanes, which the column waves waited for (profiles/ROUNDS.md).
+// The float64 image is written ONCE (32.8 MB per detection instead of the 98.6 MB moved by the two-pass kernels above, which stay
+// for small chunks - see rt_one_sweep - and for image sizes above 2048).
+#define RI_ROWS 64                          // rows of a band
+#define RI_WAVES 4                          // column waves = quarters of a band
+#define RI_Q (RI_ROWS / RI_WAVES)           // rows of a quarter: the height of a tile of the need / lit matrices and of boxtab
+#define RI_TILES (2048 / 64)                // tiles of a band of the largest image
+#define RI_OWN (RI_TILES / RI_WAVES)        // tiles whose column sums a column wave carries
 #ifndef RI_BD
 #define RI_BD 4                             // batches of eight columns the row wave reads ahead of its chain
 #endif
-#define RI_TP 66                            // tile pitch in doubles: even, so that the row wave moves two columns per LDS instruction (round 6)
-#define RI_LDS_BYTES (2 * RI_WAVES * RI_ROWS * RI_TP * 8)     // two buffers of RI_WAVES tiles
-#ifndef RI_BOX
-#define RI_BOX 2560                         // (round 6: 1536 -> 2560, the LDS that is left at two workgroups per CU: fewer patches on the gather path, -2 %)
-#endif
-// the polar footprint of every (band, group, wave) patch of the sweep depends on the sampling map only: computed once per engine
-// (one wave per patch, the reduction the integral kernel used to redo for every detection and phase: 24 cross-lane exchanges)
+#define RI_TP 66                            // tile pitch in doubles: even, the row wave moves two columns per LDS instruction; lane-per-row 16-byte
+                                            // reads start at bank (4 r + 2 c) mod 64: no conflict within an instruction's lane groups
+#define RI_LDS_BYTES (2 * RI_ROWS * RI_TP * 8)                // two tile buffers (the same 67 584 bytes as 2 x 4 tiles of 16 rows)
+// static LDS beside them: tot 4 096 + cb 1 024 (new with the quarters), the boxes, the code table 1 024.  Two workgroups per CU have
+// 81 920 bytes each: the phase list left LDS (scalar loads from a.phlist) and a box shrank 2 560 -> 2 048 bytes (a few more patches on
+// the gather path; 1 536 -> 2 560 was worth 2 %)
+#define RI_BOX 2048
+static_assert(RI_LDS_BYTES + 2 * RI_WAVES * 64 * 8 + 2 * 64 * 8 + RI_WAVES * RI_BOX + 256 * 4 <= 81920, "two workgroups per CU");
+// the polar footprint of every (quarter, tile) patch - 16 rows x 64 columns - of the sweep depends on the sampling map only: computed
+// once per engine (one wave per patch, the reduction the integral kernel used to redo for every detection and phase: 24 cross-lane
+// exchanges).  Entry (4 band + wave) * RI_TILES + tile; a quarter below the image is empty.
 __global__ __launch_bounds__(64) void rt_boxtab_kernel(const uint32_t *__restrict__ map, int W, int cols, uint32_t *__restrict__ boxtab)
 {
     const int H = W, lane = threadIdx.x;
-    const int idx = blockIdx.x, wave = idx % RI_WAVES, g = (idx / RI_WAVES) % RI_GROUPS, band = idx / (RI_WAVES * RI_GROUPS);
-    const int c = min(g * 64 * RI_WAVES + 64 * wave + lane, W - 1);
+    const int idx = blockIdx.x, tile = idx % RI_TILES, quarter = idx / RI_TILES;
+    const int c = min(tile * 64 + lane, W - 1);
     int mnx = 0x7fffffff, mxx = -1, mny = 0x7fffffff, mxy = -1;
-    for (int k = 0; k < RI_ROWS; k++) {
-        const uint32_t m = map[(int64_t)min(band * RI_ROWS + k, H - 1) * W + c];
+    for (int k = 0; k < RI_Q; k++) {
+        if (quarter * RI_Q + k >= H) break;
+        const uint32_t m = map[(int64_t)(quarter * RI_Q + k) * W + c];
         const int ix = m & 4095, iy = (m >> 12) & 1023;
         if (ix < cols) { mnx = min(mnx, ix); mxx = max(mxx, ix); mny = min(mny, iy); mxy = max(mxy, iy); }
     }
@@ -236,6 +244,12 @@ __global__ __launch_bounds__(64) void rt_boxtab_kernel(const uint32_t *__restric
         boxtab[2 * idx + 1] = mxx < 0 ? 0u : ((uint32_t)mny | ((uint32_t)mxy << 16));
     }
 }
+
+// a phase-list entry: band | tile << 8 | (quarters of the tile the determinant kernel reads, one bit per column wave) << 16
+#define RI_E_BAND(e) ((int)((e) & 63u))
+#define RI_E_TILE(e) ((int)(((e) >> 8) & 31u))
+#define RI_E_BITS(e) ((uint32_t)(((e) >> 16) & 15u))
+#define RI_E_MAKE(band, tile, bits) ((uint32_t)(band) | ((uint32_t)(tile) << 8) | ((uint32_t)(bits) << 16))
 
 #ifdef RI_PROF
 __device__ unsigned long long ri_prof[16];
@@ -258,42 +272,46 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
     const int ls = (int)blockIdx.x, slot = first + ls;
     if (slot >= *a.rt_n || !rt_one_sweep(a, first) || a.fused) return;
     typedef double Tile[RI_ROWS][RI_TP];
-    Tile *tiles = reinterpret_cast<Tile *>(ri_lds);                        // [2][RI_WAVES]
+    Tile *tiles = reinterpret_cast<Tile *>(ri_lds);                        // [2]
     const int W = a.W, H = a.W, t = threadIdx.x, wave = t >> 6, lane = t & 63;
     __shared__ float lut[256];
     __shared__ __align__(4) uint8_t box[RI_WAVES][RI_BOX];
-    // the phases to walk: band | group << 8 | (tiles the determinant kernel reads, one bit per column wave) << 12, in sweep order
-    // (retrack_build_phases: a phase is left out when nothing in it is lit and its row sums are either still zero or never read again)
-    __shared__ uint16_t phl[RI_PHL_MAX];
+    __shared__ double tot[2][RI_WAVES][64];                                // the quarters' column totals of a phase
+    __shared__ double cb[2][64];                                           // the tile's column sums above the band
     if (t < 256) lut[t] = rt_code_to_f32(t);
-    const int nph = (int)a.phlist[0];
-    for (int i = t; i < nph; i += (int)blockDim.x) phl[i] = (uint16_t)a.phlist[1 + i];
+    // the phases to walk, in sweep order (retrack_build_phases: a phase is left out when nothing in it is lit and its row sums are
+    // either still zero or never read again).  Every wave reads the entries it needs as scalars, a few phases ahead of their use (the
+    // list does not change while kernels run: the constant address space makes the loads scalar ones)
+    typedef const uint32_t __attribute__((address_space(4))) *RiConstPtr;
+    const RiConstPtr phc = (RiConstPtr)(uintptr_t)a.phlist;
+    const int nph = (int)phc[0];
+    auto ph_ent = [&](int i) { return i < nph ? phc[1 + i] : 0u; };
     __syncthreads();
-    // (an entry is read once - one LDS read a phase, a phase ahead - and passed on as a scalar)
-    auto ph_ent = [&](int i) { return i < nph ? (int)__builtin_amdgcn_readfirstlane((int)phl[i]) : 0; };
-    auto ph_band = [](int e) { return e & 255; };
-    auto ph_group = [](int e) { return (e >> 8) & 15; };
     if (wave < RI_WAVES) {
-        // ------------------------------------------------------------------------------------ column waves: C(i-1), A(i+1)
+        // ------------------------------------------------------------------------------------ column waves: A2(i), A1(i+1)
         const uint8_t *p = a.pool + (int64_t)a.rt_scan[slot] * a.rec_bytes + a.payload_off;
         double *S = a.S + (int64_t)ls * a.SP * W;
         const int SP = a.SP;
         const int rows = a.rows, cols = a.cols, stride = a.stride;
-        double acc[RI_GROUPS];                                             // the running sums of this thread's columns
-#pragma unroll
-        for (int g = 0; g < RI_GROUPS; g++) acc[g] = 0.0;
-        uint32_t m[RI_ROWS];                                               // the map words of the NEXT A, in flight
-        uint32_t ext0 = 0, ext1 = 0;                                       // the polar footprint (boxtab) of the patch of the A after the next, in flight
-        uint32_t cur0 = 0xffff0000u, cur1 = 0;                             // ... of the next A (wave-uniform)
-        uint32_t raw[8];                                                   // the first eight pieces of the next A's box, in flight (prefetch_box)
         const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        auto fetch = [&](int band, int g) {
-            const int c = min(g * 64 * RI_WAVES + 64 * wave + lane, W - 1);
+        // the running sums of the columns of the tiles this wave owns (tile & 3 == wave).  own[0] is always the sum of the tile group
+        // `gcur` (tile >> 2): the array is rotated until it is (8 register moves a step; an array indexed by the group was kept in scratch
+        // memory by the compiler: 16 MB of extra HBM writes per detection); the phases the list leaves out have dark pixels only
+        double own[RI_OWN];
 #pragma unroll
-            for (int k = 0; k < RI_ROWS; k++) m[k] = a.map[(int64_t)min(band * RI_ROWS + k, H - 1) * W + c];
+        for (int g = 0; g < RI_OWN; g++) own[g] = 0.0;
+        int gcur = 0;
+        uint32_t m[RI_Q];                                                  // the map words of the NEXT A1, in flight
+        uint32_t ext0 = 0, ext1 = 0;                                       // the polar footprint (boxtab) of the patch of the A1 after the next, in flight
+        uint32_t cur0 = 0xffff0000u, cur1 = 0;                             // ... of the next A1 (wave-uniform)
+        uint32_t raw[8];                                                   // the first eight pieces of the next A1's box, in flight (prefetch_box)
+        auto fetch = [&](uint32_t e) {
+            const int c = min(RI_E_TILE(e) * 64 + lane, W - 1), r0 = RI_E_BAND(e) * RI_ROWS + wave_u * RI_Q;
+#pragma unroll
+            for (int k = 0; k < RI_Q; k++) m[k] = a.map[(int64_t)min(r0 + k, H - 1) * W + c];
         };
-        auto fetch_ext = [&](int i) {
-            const uint32_t *bt = a.boxtab + 2 * (i * RI_WAVES + wave_u);
+        auto fetch_ext = [&](uint32_t e) {
+            const uint32_t *bt = a.boxtab + 2 * ((RI_E_BAND(e) * RI_WAVES + wave_u) * RI_TILES + RI_E_TILE(e));
             ext0 = bt[0]; ext1 = bt[1];
         };
         // geometry of a patch's polar box out of its table entry (all wave-uniform)
@@ -314,26 +332,26 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
         auto load_pieces = [&](const Box &b, int q0) {
             const uint8_t *pl = p + (sub * stride + c4);
             const int npiece = b.nrg * b.ncb;
-            int kg = (q0 / b.ncb) * 4, cb = (q0 % b.ncb) * 64;
+            int kg = (q0 / b.ncb) * 4, cb_ = (q0 % b.ncb) * 64;
 #pragma unroll
             for (int u = 0; u < 8; u++) {
-                if (q0 + u < npiece) raw[u] = reinterpret_cast<const RtU32 *>(pl + ((b.mny - 1 + kg) * stride + b.mnx + cb))->v;
-                cb += 64;
-                if (cb >= b.bp) { cb = 0; kg += 4; }
+                if (q0 + u < npiece) raw[u] = reinterpret_cast<const RtU32 *>(pl + ((b.mny - 1 + kg) * stride + b.mnx + cb_))->v;
+                cb_ += 64;
+                if (cb_ >= b.bp) { cb_ = 0; kg += 4; }
             }
         };
         auto store_pieces = [&](const Box &b, int q0, uint8_t *bx) {
             uint8_t *bl = bx + (sub * b.bp + c4);
             const int npiece = b.nrg * b.ncb;
-            int kg = (q0 / b.ncb) * 4, cb = (q0 % b.ncb) * 64;
+            int kg = (q0 / b.ncb) * 4, cb_ = (q0 % b.ncb) * 64;
 #pragma unroll
             for (int u = 0; u < 8; u++) {
-                if (q0 + u < npiece && sub < b.bh - kg && c4 < b.bp - cb) *reinterpret_cast<uint32_t *>(bl + (kg * b.bp + cb)) = raw[u];
-                cb += 64;
-                if (cb >= b.bp) { cb = 0; kg += 4; }
+                if (q0 + u < npiece && sub < b.bh - kg && c4 < b.bp - cb_) *reinterpret_cast<uint32_t *>(bl + (kg * b.bp + cb_)) = raw[u];
+                cb_ += 64;
+                if (cb_ >= b.bp) { cb_ = 0; kg += 4; }
             }
         };
-        // The first eight pieces of the NEXT A's box leave one phase ahead (its extent came out of the table a phase before that): their
+        // The first eight pieces of the NEXT A1's box leave one phase ahead (its extent came out of the table a phase before that): their
         // HBM / L2 round trip - 37 % of a column wave's time when the loads were issued inside the phase that needs them (s_memtime) -
         // passes while the row wave works on the tile in between
         auto prefetch_box = [&]() {
@@ -341,8 +359,19 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
             const Box b = geom(cur0, cur1);
             if (b.inside) load_pieces(b, 0);
         };
-        float v[RI_ROWS];                                                  // the pixels of the phase A1 has prepared for A2
-        auto A1 = [&](int i, int e_n1, int e_n2) {                         // phase i of the list: the patch's pixels -> v[]; e_n1 / e_n2: the entries of the next two phases
+        float v[RI_Q];                                                     // the pixels of the phase A1 has prepared for A2
+        double vtot = 0.0;                                                 // ... and their sum
+        // the owner of a tile's column sums brings them to own[0]
+        auto rotate_to = [&](int g) {
+            while (gcur != g) {
+                const double s0 = own[0];
+#pragma unroll
+                for (int q = 0; q + 1 < RI_OWN; q++) own[q] = own[q + 1];
+                own[RI_OWN - 1] = s0;
+                gcur = (gcur + 1) % RI_OWN;
+            }
+        };
+        auto A1 = [&](int i, uint32_t e_i, uint32_t e_n1, uint32_t e_n2) {  // phase i of the list: the patch's pixels -> v[]; e_n1 / e_n2: the entries of the next two phases
             // The polar footprint of the wave's 64 x 16 pixel patch is a small box (range span x azimuth span, a few hundred bytes):
             // it is copied into LDS with a handful of coalesced row loads (16 lanes per polar row, four rows per instruction) and
             // the 4 taps per pixel become LDS byte reads; per-lane byte gathers from global memory (two 16-bit loads per pixel,
@@ -353,7 +382,7 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
             const int mnx = b.mnx, mny = b.mny, bh = b.bh, bp = b.bp;
             if (b.mxx < 0) {
 #pragma unroll
-                for (int k = 0; k < RI_ROWS; k++) v[k] = 0.f;              // beyond the maximum range
+                for (int k = 0; k < RI_Q; k++) v[k] = 0.f;                 // beyond the maximum range, or a quarter below the image
             } else if (b.staged) {
                 uint8_t *bx = box[wave];
                 if (b.inside) {
@@ -368,8 +397,8 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
                     const int kk = kg + sub;
                     int r = mny + kk - 1;
                     if (r < 0) r += rows; else if (r >= rows) r -= rows;
-                    for (int cb = 0; cb < bp; cb += 64) {
-                        const int cc = cb + c4;
+                    for (int cb_ = 0; cb_ < bp; cb_ += 64) {
+                        const int cc = cb_ + c4;
                         if (kk < bh && cc < bp) {
                             // bytes beyond the scan's last range bin read as zero: the load is moved back inside the row and shifted
                             const int x0 = mnx + cc, xl = min(x0, cols - 4), sh = 8 * (x0 - xl);
@@ -380,7 +409,7 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < RI_ROWS; k++) {
+                for (int k = 0; k < RI_Q; k++) {
                     const uint32_t mk = m[k];
                     const int ix = mk & 4095, iy = (mk >> 12) & 1023;
                     float r_ = 0.f;
@@ -398,119 +427,106 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
                 }
             } else {
 #pragma unroll
-                for (int k = 0; k < RI_ROWS; k++) v[k] = rt_pixel(m[k], p, rows, cols, stride, lut);
+                for (int k = 0; k < RI_Q; k++) v[k] = rt_pixel(m[k], p, rows, cols, stride, lut);
             }
             // the next phase's map words leave now; they land while the row wave works
             if (i + 1 < nph) {
-                fetch(ph_band(e_n1), ph_group(e_n1));
+                fetch(e_n1);
                 prefetch_box();
-                if (i + 2 < nph) fetch_ext(ph_band(e_n2) * RI_GROUPS + ph_group(e_n2));
+                if (i + 2 < nph) fetch_ext(e_n2);
+            }
+            // the quarter's total (rows below the image - their map words are the last row's - count as zero: s + 0.0 = s), and what
+            // lies above the band from the tile's owner
+            const int nlive = H - (RI_E_BAND(e_i) * RI_ROWS + wave_u * RI_Q);
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < RI_Q; k++) {
+                if (k >= nlive) v[k] = 0.f;
+                s = __dadd_rn(s, (double)v[k]);
+            }
+            vtot = s;
+            tot[i & 1][wave][lane] = s;
+            if ((RI_E_TILE(e_i) & (RI_WAVES - 1)) == wave_u) {
+                rotate_to(RI_E_TILE(e_i) / RI_WAVES);
+                cb[i & 1][lane] = own[0];
             }
         };
-        int gcur = 0;                                                      // the group whose running sums sit in acc[0]
-        auto A2 = [&](int i, int band, int g) {
-            const int c = g * 64 * RI_WAVES + 64 * wave + lane;
-            Tile &tl = tiles[(i & 1) * RI_WAVES + wave];
-            {
-                // acc[0] is always the running sum of the CURRENT group's column: the array is rotated by one after every phase (8
-                // register moves; a group-indexed array was kept in scratch memory by the compiler: 16 MB of extra HBM writes per
-                // detection) - and by as many groups as the phase list leaves out in between (their pixels are dark: sums unchanged)
-                while (gcur != g) {
-                    const double s0 = acc[0];
+        auto A2 = [&](int i, uint32_t e_i) {                               // (after the barrier behind A1(i): the other waves' totals)
+            const bool owner = (RI_E_TILE(e_i) & (RI_WAVES - 1)) == wave_u;    // (own[0] is this tile's sum since A1(i))
+            double s = cb[i & 1][lane], sum = vtot;
 #pragma unroll
-                    for (int q = 0; q + 1 < RI_GROUPS; q++) acc[q] = acc[q + 1];
-                    acc[RI_GROUPS - 1] = s0;
-                    gcur = (gcur + 1) % RI_GROUPS;
-                }
-                double s = acc[0];
-                if (c < W) {
+            for (int q = 0; q < RI_WAVES; q++) {
+                if (q == wave_u || !(q < wave_u || owner)) continue;       // (wave-uniform: at most four LDS reads for a wave that owns nothing here)
+                const double tq = tot[i & 1][q][lane];
+                if (q < wave_u) s = __dadd_rn(s, tq);
+                sum = __dadd_rn(sum, tq);
+            }
+            if (owner) own[0] = __dadd_rn(own[0], sum);
+            double (*tl)[RI_TP] = tiles[i & 1] + wave * RI_Q;
 #pragma unroll
-                    for (int k = 0; k < RI_ROWS; k++) {
-                        if (band * RI_ROWS + k < H) s = __dadd_rn(s, (double)v[k]);
-                        tl[k][lane] = s;
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q + 1 < RI_GROUPS; q++) acc[q] = acc[q + 1];
-                acc[RI_GROUPS - 1] = s;
-                gcur = (gcur + 1) % RI_GROUPS;
+            for (int k = 0; k < RI_Q; k++) {
+                s = __dadd_rn(s, (double)v[k]);
+                tl[k][lane] = s;
             }
         };
-        auto C = [&](int i, int e) {
-            const int band = ph_band(e), g = ph_group(e);
-            const int c = g * 64 * RI_WAVES + 64 * wave + lane;
-            const Tile &tl = tiles[(i & 1) * RI_WAVES + wave];
-            const bool wanted = ((e >> (12 + wave_u)) & 1) != 0;              // does anything read this tile?
-            if (c < W && wanted) {
-                double *q = S + (int64_t)band * RI_ROWS * SP + c;
-                const int nk = min(RI_ROWS, H - band * RI_ROWS);
-                if (nk == RI_ROWS) {
-#pragma unroll
-                    for (int k = 0; k < RI_ROWS; k++) q[(int64_t)k * SP] = tl[k][lane];
-                } else
-                    for (int k = 0; k < nk; k++) q[(int64_t)k * SP] = tl[k][lane];
-            }
-        };
-        // entries of phases i - 1 .. i + 3 as scalars
-        int e_m1 = 0, e_0 = ph_ent(0), e_1 = ph_ent(1), e_2 = ph_ent(2), e_3 = ph_ent(3);
+        // entries of phases i .. i + 3 as scalars
+        uint32_t e_0 = ph_ent(0), e_1 = ph_ent(1), e_2 = ph_ent(2), e_3 = ph_ent(3);
         if (nph > 0) {
-            fetch(ph_band(e_0), ph_group(e_0));
-            fetch_ext(ph_band(e_0) * RI_GROUPS + ph_group(e_0));
+            fetch(e_0);
+            fetch_ext(e_0);
             prefetch_box();
-            if (nph > 1) fetch_ext(ph_band(e_1) * RI_GROUPS + ph_group(e_1));
-            A1(0, e_1, e_2);
-            A2(0, ph_band(e_0), ph_group(e_0));
-#pragma unroll 1
-            for (int i = 0; i < nph; i++) {
-                const int e_4 = ph_ent(i + 4);                             // (lands while this phase runs)
-                RI_P(0)
-                __syncthreads();                                           // A(i) and B(i-1) are complete
-                RI_P(1)
-                if (i > 0) C(i - 1, e_m1);
-                RI_P(2)
-                if (i + 1 < nph) { A1(i + 1, e_2, e_3); RI_P(3) A2(i + 1, ph_band(e_1), ph_group(e_1)); }
-                RI_P(4)
-                e_m1 = e_0; e_0 = e_1; e_1 = e_2; e_2 = e_3; e_3 = e_4;
-            }
+            if (nph > 1) fetch_ext(e_1);
+            A1(0, e_0, e_1, e_2);
         }
-        __syncthreads();
-        if (nph > 0) C(nph - 1, e_m1);
+#pragma unroll 1
+        for (int i = 0; i < nph + 1; i++) {
+            const uint32_t e_4 = ph_ent(i + 4);                            // (lands while this phase runs)
+            RI_P(0)
+            __syncthreads();                                               // A1(i), A2(i-1), B(i-2) and C(i-2) are complete
+            RI_P(1)
+            if (i < nph) A2(i, e_0);
+            RI_P(2)
+            if (i + 1 < nph) A1(i + 1, e_1, e_2, e_3);
+            RI_P(3)
+            e_0 = e_1; e_1 = e_2; e_2 = e_3; e_3 = e_4;
+        }
     } else {
-        // ------------------------------------------------------------------------------------ the row wave: B(i)
-        // (s_setprio 3 for this wave - the chain a phase waits for - moves the wait from the column waves' barrier to their taps: the row wave
-        // busy 80 -> 70 % of a phase, the column waves' A1 55 -> 67 %, the kernel 6.44 -> 6.43 ms per 512: dropped)
+        // ------------------------------------------------------------------------------------ the row wave: B(i-1), C(i-1)
+        double *S = a.S + (int64_t)ls * a.SP * W;
+        const int SP = a.SP;
+        const int half = lane >> 5, c2 = 2 * (lane & 31);                  // C: a lane moves two columns, an instruction two rows
         double carry = 0.0;                                                // running sum of row band * RI_ROWS + lane
         int pband = -1;
-        int e_nx = ph_ent(0);
-        for (int i = 0; i < nph; i++) {
-            const int band = ph_band(e_nx), g = ph_group(e_nx);
-            e_nx = ph_ent(i + 1);
-            if (band != pband) { carry = 0.0; pband = band; }              // (the phases a band leaves out on its left have sums of zero)
-            const bool live = lane < RI_ROWS && band * RI_ROWS + lane < H;
+        uint32_t e_nx = ph_ent(0);
+        for (int i = 0; i < nph + 1; i++) {
+            const uint32_t e = e_nx;                                       // the entry of phase i - 1
+            if (i >= 1) e_nx = ph_ent(i);
             RI_P(5)
             __syncthreads();
             RI_P(6)
-            if (live) {
-                const int C0 = g * 64 * RI_WAVES, ncols = min(64 * RI_WAVES, W - C0);
-                Tile *tg = tiles + (i & 1) * RI_WAVES;
+            if (i < 1) continue;
+            const int band = RI_E_BAND(e), tile = RI_E_TILE(e);
+            if (band != pband) { carry = 0.0; pband = band; }              // (the phases a band leaves out on its left have sums of zero)
+            if (band * RI_ROWS + lane < H) {
+                const int ncols = min(64, W - tile * 64);
+                double *row = tiles[(i - 1) & 1][lane];
                 int j = 0;
                 if (ncols >= 16) {
                     // batches of eight columns (eight dependent float64 additions), 16-byte LDS accesses (two columns per instruction)
-                    auto rd = [&](double(&x)[8], int jj) {                 // (a batch never straddles two tiles: 64 = 8 x 8)
-                        const double2 *q = reinterpret_cast<const double2 *>(&tg[jj >> 6][lane][jj & 63]);
+                    auto rd = [&](double(&x)[8], int jj) {
+                        const double2 *q = reinterpret_cast<const double2 *>(row + jj);
 #pragma unroll
                         for (int u = 0; u < 4; u++) { const double2 v2 = q[u]; x[2 * u] = v2.x; x[2 * u + 1] = v2.y; }
                     };
                     auto chain_wr = [&](double(&x)[8], int jj) {
 #pragma unroll
                         for (int u = 0; u < 8; u++) { carry = __dadd_rn(carry, x[u]); x[u] = carry; }
-                        double2 *q = reinterpret_cast<double2 *>(&tg[jj >> 6][lane][jj & 63]);
+                        double2 *q = reinterpret_cast<double2 *>(row + jj);
 #pragma unroll
                         for (int u = 0; u < 4; u++) q[u] = make_double2(x[2 * u], x[2 * u + 1]);
                     };
                     // RI_BD batches of eight columns are in flight ahead of the chain: beside eight column waves' tap reads an LDS read
                     // takes several hundred cycles to come back, and one batch ahead the chain waited for it at every batch
-                    // (56 cycles per column, the row wave busy 87 % of a phase: profiles/ri_prof.py)
                     double xr[RI_BD][8];
 #pragma unroll
                     for (int u = 0; u < RI_BD; u++)
@@ -522,26 +538,40 @@ __global__ __launch_bounds__(64 * (RI_WAVES + 1)) void rt_integral_kernel(RtArgs
                             if (j + 8 * (RI_BD + u) + 8 <= ncols) rd(xr[u], j + 8 * (RI_BD + u));
                         }
                     }
-                    // (what is left of the group - fewer than RI_BD batches - is in the registers already)
+                    // (what is left of the tile - fewer than RI_BD batches - is in the registers already)
 #pragma unroll
                     for (int u = 0; u < RI_BD; u++)
                         if (j + 8 <= ncols) { chain_wr(xr[u], j); j += 8; }
                 }
                 for (; j < ncols; j++) {
-                    double *q = &tg[j >> 6][lane][j & 63];
-                    carry = __dadd_rn(carry, *q);
-                    *q = carry;
+                    carry = __dadd_rn(carry, row[j]);
+                    row[j] = carry;
+                }
+            }
+            RI_P(7)
+            // C: the quarters of the tile that are read go to the image, 16-byte accesses (W and SP are even: a pair of columns is inside
+            // the image or outside, and aligned); eight row pairs in flight
+            if (tile * 64 + c2 < W) {
+                const double (*tl)[RI_TP] = tiles[(i - 1) & 1];
+                double *q = S + (int64_t)(band * RI_ROWS + half) * SP + tile * 64 + c2;
+                for (int w = 0; w < RI_WAVES; w++) {
+                    if (!((RI_E_BITS(e) >> w) & 1u)) continue;             // does anything read this quarter of the tile?
+                    double2 x[RI_Q / 2];
+#pragma unroll
+                    for (int k = 0; k < RI_Q / 2; k++) x[k] = *reinterpret_cast<const double2 *>(&tl[w * RI_Q + 2 * k + half][c2]);
+#pragma unroll
+                    for (int k = 0; k < RI_Q / 2; k++)
+                        if (band * RI_ROWS + w * RI_Q + 2 * k + half < H) *reinterpret_cast<double2 *>(q + (int64_t)(w * RI_Q + 2 * k) * SP) = x[k];
                 }
             }
         }
-        __syncthreads();
     }
 #ifdef RI_PROF
     if (lane == 0 && (wave == 0 || wave == RI_WAVES)) for (int k = 0; k < 8; k++) atomicAdd(&ri_prof[k + (wave == 0 ? 0 : 8)], rip_[k]);
 #endif
 }
 
-size_t retrack_boxtab_words(int W) { return 2 * (size_t)((W + RI_ROWS - 1) / RI_ROWS) * RI_GROUPS * RI_WAVES; }
+size_t retrack_boxtab_words(int W) { return 2 * (size_t)((W + RI_ROWS - 1) / RI_ROWS) * RI_WAVES * RI_TILES; }
 
 hipError_t launch_retrack_boxtab(hipStream_t st, const uint32_t *map, int W, int cols, uint32_t *boxtab)
 {
@@ -550,26 +580,27 @@ hipError_t launch_retrack_boxtab(hipStream_t st, const uint32_t *map, int W, int
 }
 // ---- which phases of the one-sweep integral kernel matter (host code, once per engine; geometry only).
 // The determinant kernel never reads the blocks of the integral image that only dark steps would touch (rt_darktab_kernel), so a 16-row x
-// 64-column TILE none of its strips loads need not be written; and a (band, group) PHASE none of whose tiles is needed need not be
-// computed when its row sums cannot matter: on a band's left while every column so far has seen no lit pixel (the sums are exactly
-// zero), on its right once nothing further along the band is needed.  Needed tiles contain every lit pixel (a lit pixel lies in the
-// window of a lit step), so a phase that is left out has dark pixels only: the columns' running sums pass it unchanged.
-// out[0] = number of phases, out[1..] = band | group << 8 | needed-tile bits << 12 in sweep order.
-size_t retrack_phase_words(int W) { return 1 + (size_t)((W + RI_ROWS - 1) / RI_ROWS) * RI_GROUPS; }
+// 64-column QUARTER TILE none of its strips loads need not be written; and a (band, tile) PHASE none of whose quarters is needed need
+// not be computed when its row sums cannot matter: on a band's left while every column so far has seen no lit pixel down to the band's
+// last row (the sums are exactly zero), on its right once nothing further along the band is needed.  Needed quarters contain every lit
+// pixel (a lit pixel lies in the window of a lit step), so a phase that is left out has dark pixels only: the columns' running sums
+// pass it unchanged.  out[0] = number of phases, out[1..] = RI_E_MAKE(band, tile, needed quarters) in sweep order.
+size_t retrack_phase_words(int W) { return 1 + (size_t)((W + RI_ROWS - 1) / RI_ROWS) * RI_TILES; }
 int retrack_band_rows() { return RI_ROWS; }
 
 bool retrack_build_phases(const uint32_t *map, const uint32_t *darktab, int W, int cols, uint32_t *out)
 {
-    const int H = W, nbands = (H + RI_ROWS - 1) / RI_ROWS, ns = (W + SD_OUT - 1) / SD_OUT, nt = H / SD_T + 1, NT = RI_GROUPS * RI_WAVES;
-    static_assert(RI_ROWS % SD_T == 0, "a band of the integral kernel is one or more blocks of the determinant kernel");
+    const int H = W, nbands = (H + RI_ROWS - 1) / RI_ROWS, ns = (W + SD_OUT - 1) / SD_OUT, nt = H / SD_T + 1, NT = RI_TILES;
+    static_assert(RI_ROWS % SD_T == 0 && RI_Q % SD_T == 0, "a quarter of a band of the integral kernel is one or more blocks of the determinant kernel");
     const int ndet = (H + SD_T - 1) / SD_T;
-    if (nbands * RI_GROUPS > RI_PHL_MAX || nbands > 256) return false;
-    std::vector<uint8_t> need((size_t)nbands * NT, 0), lit((size_t)nbands * NT, 0);
+    if (W > 64 * RI_TILES) return false;
+    // need / lit: per (quarter, tile), 16 rows x 64 columns
+    std::vector<uint8_t> need((size_t)nbands * RI_WAVES * NT, 0), lit((size_t)nbands * RI_WAVES * NT, 0);
     std::vector<int> firstlit(W, H);
     for (int r = 0; r < H; r++)
         for (int c = 0; c < W; c++)
             if ((int)(map[(size_t)r * W + c] & 4095u) < cols) {
-                lit[(size_t)(r / RI_ROWS) * NT + c / 64] = 1;
+                lit[(size_t)(r / RI_Q) * NT + c / 64] = 1;
                 if (firstlit[c] == H) firstlit[c] = r;
             }
     for (int s = 0; s < ns; s++) {
@@ -581,40 +612,56 @@ bool retrack_build_phases(const uint32_t *map, const uint32_t *darktab, int W, i
         for (int j = tb; j <= te + 3 && j < ndet; j++) {
             const bool in_loop = j >= tb + 4;                               // (the four blocks of the prologue are always loaded)
             if (in_loop && ((T[8 + ((j - 4) >> 5)] >> ((j - 4) & 31)) & 1u)) continue;
-            for (int k = c_lo / 64; k <= c_hi / 64; k++) need[(size_t)(j * SD_T / RI_ROWS) * NT + k] = 1;
+            for (int k = c_lo / 64; k <= c_hi / 64; k++) need[(size_t)(j * SD_T / RI_Q) * NT + k] = 1;
         }
     }
+    const int ntile = (W + 63) / 64;
     int n = 0;
     bool sound = true;
     for (int b = 0; b < nbands; b++) {
-        bool needp[RI_GROUPS], zero[RI_GROUPS];
-        uint32_t bits[RI_GROUPS];
-        for (int g = 0; g < RI_GROUPS; g++) {
-            bits[g] = 0; zero[g] = true;
-            for (int w = 0; w < RI_WAVES; w++) if (need[(size_t)b * NT + g * RI_WAVES + w]) bits[g] |= 1u << w;
-            needp[g] = bits[g] != 0;
-            const int rend = std::min(b * RI_ROWS + RI_ROWS - 1, H - 1);
-            for (int c = g * 64 * RI_WAVES; c < std::min(W, (g + 1) * 64 * RI_WAVES); c++) if (firstlit[c] <= rend) { zero[g] = false; break; }
+        bool zero[RI_TILES];
+        uint32_t bits[RI_TILES];
+        const int rend = std::min(b * RI_ROWS + RI_ROWS - 1, H - 1);
+        for (int k = 0; k < ntile; k++) {
+            bits[k] = 0; zero[k] = true;
+            for (int w = 0; w < RI_WAVES; w++) if (need[(size_t)(b * RI_WAVES + w) * NT + k]) bits[k] |= 1u << w;
+            for (int c = k * 64; c < std::min(W, (k + 1) * 64); c++) if (firstlit[c] <= rend) { zero[k] = false; break; }
         }
-        for (int g = 0; g < RI_GROUPS; g++) {
-            bool skipL = !needp[g], skipR = true;
-            for (int q = 0; q <= g && skipL; q++) skipL = zero[q];
-            for (int q = g; q < RI_GROUPS && skipR; q++) skipR = !needp[q];
-            if (g * 64 * RI_WAVES >= W) continue;                           // (no such columns)
+        for (int k = 0; k < ntile; k++) {
+            bool skipL = !bits[k], skipR = true;
+            for (int q = 0; q <= k && skipL; q++) skipL = zero[q];
+            for (int q = k; q < ntile && skipR; q++) skipR = !bits[q];
             if (skipL || skipR) {
-                for (int w = 0; w < RI_WAVES; w++) if (lit[(size_t)b * NT + g * RI_WAVES + w]) sound = false;      // (cannot happen: see above)
+                for (int w = 0; w < RI_WAVES; w++) if (lit[(size_t)(b * RI_WAVES + w) * NT + k]) sound = false;      // (cannot happen: see above)
                 continue;
             }
-            out[1 + n++] = (uint32_t)b | ((uint32_t)g << 8) | (bits[g] << 12);
+            out[1 + n++] = RI_E_MAKE(b, k, bits[k]);
         }
     }
     if (!sound) {                                                           // belt and braces: walk everything, write everything
         n = 0;
         for (int b = 0; b < nbands; b++)
-            for (int g = 0; g < RI_GROUPS && g * 64 * RI_WAVES < W; g++) out[1 + n++] = (uint32_t)b | ((uint32_t)g << 8) | (((1u << RI_WAVES) - 1u) << 12);
+            for (int k = 0; k < ntile; k++) {
+                uint32_t all = 0;
+                for (int w = 0; w < RI_WAVES; w++) if (b * RI_ROWS + w * RI_Q < H) all |= 1u << w;
+                out[1 + n++] = RI_E_MAKE(b, k, all);
+            }
     }
     out[0] = (uint32_t)n;
     return true;
+}
+
+// pixels of the integral image the phases of a list write: its needed quarter tiles, clipped to the image
+int64_t retrack_phase_pixels(const uint32_t *ph, int W)
+{
+    int64_t px = 0;
+    for (uint32_t i = 0; i < ph[0]; i++) {
+        const uint32_t e = ph[1 + i];
+        const int wcols = std::max(0, std::min(64, W - RI_E_TILE(e) * 64));
+        for (int w = 0; w < RI_WAVES; w++)
+            if ((RI_E_BITS(e) >> w) & 1u) px += (int64_t)std::max(0, std::min(RI_Q, W - (RI_E_BAND(e) * RI_ROWS + w * RI_Q))) * wcols;
+    }
+    return px;
 }
 
 hipError_t retrack_integral_init() { return hipFuncSetAttribute(reinterpret_cast<const void *>(rt_integral_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RI_LDS_BYTES); }
