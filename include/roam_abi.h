@@ -570,6 +570,13 @@ int32_t roam_debug_keyframe_append(roam_ctx *ctx, const uint8_t *recv, int32_t w
  * first) of `what` on zero planes of that size (sizes from 2). */
 int32_t roam_debug_fft2_f64(roam_ctx *ctx, const double *re_in, const double *im_in, int32_t rows, int32_t cols, int32_t inverse,
                             double *re_out, double *im_out);
+/* test: the engine's batched SSC kernel alone (the stage call roam_ssc runs the same body with a 64 KB cell bitmap, this one with
+ * 16 KB).  kp (host): P problems as the engine lays them out, kp_cap rows of 3 float64 [row, col, sigma] each; count[p] live rows
+ * (clamped to kp_cap by the kernel); problems p with first + p >= n_active are skipped.  One launch with (num_ret, tol, cols, rows,
+ * first).  sel_out (P x kp_cap) and n_sel_out (P) are prefilled with -1 on the device before the launch. */
+int32_t roam_debug_ssc_batch(roam_ctx *ctx, const double *kp, const int32_t *count, int32_t P, int32_t kp_cap, int32_t n_active,
+                             int32_t first, int32_t num_ret, double tol, int32_t cols, int32_t rows, int32_t *sel_out,
+                             int32_t *n_sel_out);
 #define ROAM_TIME_FFT_FIVE      0   /* the five 2-D transforms of one phase correlation (two real forward, one inverse), transposes included */
 #define ROAM_TIME_DFT_FIVE      1   /* the same five as direct DFTs, a baseline only (rows * cols <= 131072) */
 #define ROAM_TIME_FFT_ROWS      2   /* one row pass: `rows` transforms of length cols, in place */

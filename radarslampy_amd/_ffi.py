@@ -147,6 +147,8 @@ _SIGS = {
                                                 C.c_int32, _vp, _vp]),
     "roam_debug_fft2_f64": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "roam_time_fft2": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
+    "roam_debug_ssc_batch": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                         _vp, _vp]),
     "roam_prune_blobs": (C.c_int32, [_vp, C.c_int32, C.c_double, _vp]),
     "roam_argsort_np122": (C.c_int32, [_vp, C.c_int32, _vp]),
     "roam_comm_available": (C.c_int32, []),
@@ -723,6 +725,20 @@ class Context:
         ro, io = np.empty_like(re), np.empty_like(re)
         self.check(self.lib.roam_debug_fft2_f64(self.h, _ptr(re), _ptr(im), rows, cols, 1 if inverse else 0, _ptr(ro), _ptr(io)))
         return ro + 1j * io
+
+    def debug_ssc_batch(self, kp, count, num_ret, tol, cols, rows, n_active=None, first=0):
+        """test entry: the engine's batched SSC kernel alone (roam_debug_ssc_batch).  kp (P, kp_cap, 3) float64, count (P,) -> (sel
+        (P, kp_cap) int32, n_sel (P,) int32), both prefilled with -1: a problem at or beyond n_active - first keeps it"""
+        kp = np.ascontiguousarray(kp, np.float64)
+        P, kp_cap, three = kp.shape
+        assert three == 3
+        count = np.ascontiguousarray(count, np.int32)
+        assert count.shape == (P,)
+        sel = np.zeros((P, kp_cap), np.int32)
+        n_sel = np.zeros(P, np.int32)
+        self.check(self.lib.roam_debug_ssc_batch(self.h, _ptr(kp), _ptr(count), P, kp_cap, P if n_active is None else int(n_active), int(first),
+                                                 int(num_ret), float(tol), int(cols), int(rows), _ptr(sel), _ptr(n_sel)))
+        return sel, n_sel
 
     def time_fft2(self, rows, cols, what, reps=20):
         """milliseconds per repetition of `what` (TIME_*) at rows x cols, by HIP events after two warm runs"""

@@ -76,3 +76,34 @@ extern "C" int32_t roam_ssc(roam_ctx *ctx, const double *kp, int32_t B, int32_t 
     *n_sel = n;
     return ROAM_OK;
 }
+
+// test entry: ssc_batch_kernel alone, on P problems laid out as the engine lays them out (problem p: kp_cap rows of 3 doubles at
+// kp + p * 3 * kp_cap, count[p] of them live) - one launch_ssc_batch with the caller's parameters.  sel_out (P x kp_cap) and n_sel_out (P)
+// are prefilled with -1 on the device, so what the kernel left alone (a skipped problem, the rows past n_sel) stays visible.
+extern "C" int32_t roam_debug_ssc_batch(roam_ctx *ctx, const double *kp, const int32_t *count, int32_t P, int32_t kp_cap, int32_t n_active,
+                                        int32_t first, int32_t num_ret, double tol, int32_t cols, int32_t rows, int32_t *sel_out,
+                                        int32_t *n_sel_out)
+{
+    if (!ctx) return ROAM_E_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ARG_CHECK(ctx, kp && count && sel_out && n_sel_out && P >= 1 && P <= 65535 && kp_cap >= 1 && (int64_t)P * kp_cap <= (1 << 24));
+    ARG_CHECK(ctx, num_ret >= 2 && cols > 0 && rows > 0 && first >= 0);
+    const size_t rows_all = (size_t)P * kp_cap;
+    double *dkp = (double *)roam_scratch(ctx, S_IN0, sizeof(double) * 3 * rows_all);
+    int32_t *dcnt = (int32_t *)roam_scratch(ctx, S_IN1, sizeof(int32_t) * ((size_t)P + 1));       // count[P], then the n_active word
+    int32_t *dwork = (int32_t *)roam_scratch(ctx, S_TMP0, sizeof(int32_t) * 4 * rows_all);
+    int32_t *dsel = (int32_t *)roam_scratch(ctx, S_OUT0, sizeof(int32_t) * rows_all);
+    int32_t *dnsel = (int32_t *)roam_scratch(ctx, S_OUT1, sizeof(int32_t) * (size_t)P);
+    if (!dkp || !dcnt || !dwork || !dsel || !dnsel) return ROAM_E_HIP;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(dkp, kp, sizeof(double) * 3 * rows_all, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dcnt, count, sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dcnt + P, &n_active, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(dsel, 0xff, sizeof(int32_t) * rows_all, st));
+    HIP_TRY(ctx, hipMemsetAsync(dnsel, 0xff, sizeof(int32_t) * (size_t)P, st));
+    HIP_TRY(ctx, launch_ssc_batch(st, dkp, (int64_t)kp_cap * 3, dcnt, kp_cap, P, num_ret, tol, cols, rows, dwork, dsel, dnsel, dcnt + P, first));
+    HIP_TRY(ctx, hipMemcpyAsync(sel_out, dsel, sizeof(int32_t) * rows_all, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(n_sel_out, dnsel, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return ROAM_OK;
+}
