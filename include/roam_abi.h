@@ -290,6 +290,50 @@ int32_t roam_fmt_register_batch_f32(roam_ctx *ctx, const float *src, const float
                                     int64_t row_stride, int64_t image_stride, int32_t clip_px, int32_t downsample,
                                     int32_t cart_downsample, double *out6, float *cart_out);
 
+/* ---- PoseGraphLib.PoseGraphOptimization (PoseGraphLib.py: g2o SparseOptimizer + OptimizationAlgorithmLevenberg; add_vertex, add_edge,
+ * optimize, get_pose), in SE(2) like the rest of the project: n_graphs independent pose graphs optimised in one device pass, one
+ * workgroup per graph, the whole Levenberg-Marquardt loop inside the kernel (csrc/posegraph.hip).  Graph g owns the vertices
+ * vertex_off[g] .. vertex_off[g + 1] (poses [x, y, theta], float64, updated in place; fixed[v] != 0: a constant) and the edges
+ * edge_off[g] .. edge_off[g + 1]: (i, j) indices WITHIN the graph in either order, duplicates summed, measurement z = (dx, dy, dtheta),
+ * information {xx xy xt yy yt tt} of the symmetric 3 x 3 matrix, and a Huber width (0 = no kernel).  g2o's EdgeSE2:
+ *   e = [R(z_th)^T (R(th_i)^T (t_j - t_i) - z_t); normalize(th_j - th_i - z_th)], its analytic Jacobians, the additive update with
+ * the angle normalised (VertexSE2::oplus); Huber: s2 = e^T O e <= delta^2: rho = s2, w = 1, else rho = 2 delta sqrt(s2) - delta^2,
+ * w = delta / sqrt(s2); H += w J^T O J, b -= w J^T O e, chi2 = sum rho.  The minimiser is g2o's Levenberg-Marquardt:
+ * lambda_0 = lambda_init or 1e-5 max diag H, ni = 2; per iteration one linearisation, then trials: solve (H + lambda I) d = b by the
+ * block envelope Cholesky (a pivot that is not positive or not finite: the trial's chi2 is +inf), apply d,
+ * rho = (chi2 - chi2_trial) / (d^T (lambda d + b) + 1e-3); accepted (rho > 0, chi2_trial finite): lambda *= max(1/3, min(1 - (2 rho - 1)^3, 2/3)),
+ * ni = 2; rejected: lambda *= ni, ni *= 2, poses restored; the trials of an iteration end when one is accepted, when rho == 0, after
+ * max_trials, or when lambda is not finite, and the optimisation ends after max_iterations or with the first iteration without an
+ * accepted trial.  PARITY UNPINNED against g2o (not installed; the contract is tests/pose_graph_model.py, checked against SciPy).
+ * No reordering: the free vertices keep their order and block row k is stored from its lowest-numbered free neighbour to the diagonal,
+ * so a graph costs its envelope - about the vertex count plus the sum of j - i over its non-consecutive edges, 144 bytes per block.
+ * Graphs are processed in chunks that keep the device scratch under 2000 MiB (ROAM_POSE_GRAPH_CHUNK_BYTES in the environment, read per
+ * call, lowers where a batch is cut - for tests; the refusal of a single graph stays at 2000 MiB); a graph's result is the same bits alone, anywhere in a
+ * batch and in any chunk.  A graph whose vertices are all fixed, or without edges, comes back unchanged with its chi2; a component
+ * without a fixed vertex is no error (the damping keeps the system definite).
+ * ROAM_E_ARG before any device call, the text naming graph and edge: n_graphs outside [1, 65535]; a graph with no vertex or more than
+ * 32768; an edge index out of range or i == j; a pose, measurement, information entry or Huber width that is not finite; a negative
+ * Huber width; a graph without a fixed vertex; max_iterations outside [0, 1000], max_trials outside [0, 1000], lambda_init negative
+ * or not finite; a single graph whose scratch exceeds a chunk (the text has its index and its envelope). */
+typedef struct roam_pose_graph_opts {
+    int32_t max_iterations;   /* 0 ... 1000; 0 = evaluate chi2 only, poses untouched */
+    int32_t max_trials;       /* 0 = 10 */
+    double  lambda_init;      /* 0 = 1e-5 * max diag(H) */
+} roam_pose_graph_opts;
+typedef struct roam_pose_graph_stats {
+    int32_t iterations, trials, rejected, stop;   /* stop: 0 max_iterations, 1 trials exhausted or rho == 0, 2 lambda not finite */
+    double chi2_initial, chi2_final, lambda_final;
+} roam_pose_graph_stats;
+/* host only: envelope blocks per graph and the scratch bytes of the call (its largest chunk).  The structural checks of
+ * roam_pose_graph_optimize (sizes, indices, a fixed vertex, the chunk limit): ROAM_E_ARG */
+int32_t roam_pose_graph_plan(int32_t n_graphs, const int32_t *vertex_off, const uint8_t *fixed, const int32_t *edge_off,
+                             const int32_t *edge_ij, int64_t *envelope_blocks, int64_t *scratch_bytes);
+int32_t roam_pose_graph_optimize(roam_ctx *ctx, int32_t n_graphs, const int32_t *vertex_off /* n + 1 */, double *poses /* V x 3, in and out */,
+                                 const uint8_t *fixed /* V */, const int32_t *edge_off /* n + 1 */, const int32_t *edge_ij /* E x 2, indices within the graph */,
+                                 const double *edge_meas /* E x 3 */, const double *edge_info /* E x 6: xx xy xt yy yt tt */,
+                                 const double *edge_huber /* E or NULL; 0 = no kernel on that edge */,
+                                 const roam_pose_graph_opts *opts, roam_pose_graph_stats *stats /* n */);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous

@@ -51,6 +51,21 @@ class AutoPriorCfg(C.Structure):
                 ("min_rot_response", C.c_double), ("min_trans_response", C.c_double)]
 
 
+class PoseGraphOpts(C.Structure):
+    """roam_abi.h roam_pose_graph_opts"""
+    _fields_ = [("max_iterations", C.c_int32), ("max_trials", C.c_int32), ("lambda_init", C.c_double)]
+
+
+# roam_abi.h roam_pose_graph_stats, one row per graph
+POSE_GRAPH_STATS = np.dtype([("iterations", np.int32), ("trials", np.int32), ("rejected", np.int32), ("stop", np.int32),
+                             ("chi2_initial", np.float64), ("chi2_final", np.float64), ("lambda_final", np.float64)])
+POSE_GRAPH_MAX_GRAPHS = 65535           # limits of roam_pose_graph_optimize
+POSE_GRAPH_MAX_VERTICES = 32768
+POSE_GRAPH_MAX_ITERATIONS = 1000
+POSE_GRAPH_MAX_TRIALS = 1000
+POSE_GRAPH_CHUNK_BYTES = 2000 << 20     # device scratch of one launch
+
+
 PRIOR_RECORD = np.dtype([("out6", np.float64, (6,)), ("affine", np.float32, (2, 3)), ("source", np.uint8)])     # Engine.step_prior's rows
 
 
@@ -105,6 +120,8 @@ _SIGS = {
     "roam_doh_maxima": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_double, _vp, _vp, C.c_int32, _P(C.c_int32)]),
     "roam_log_maxima": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_double, _vp, _vp, C.c_int32,
                                     _P(C.c_int32), _vp]),
+    "roam_pose_graph_plan": (C.c_int32, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(C.c_int64)]),
+    "roam_pose_graph_optimize": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PoseGraphOpts), _vp]),
     "roam_engine_create": (C.c_int32, [_vp, _P(EngineCfg)]),
     "roam_engine_destroy": (C.c_int32, [_vp]),
     "roam_engine_upload_scan": (C.c_int32, [_vp, C.c_int32, _vp]),
@@ -366,6 +383,122 @@ def auto_prior_args(cols, rows, clip_px, downsample, cart_downsample, min_rot_re
     if clip_px == 0 and downsample == 0 and cart_downsample == 0:        # (refused above: downsample < 1; never the ABI's "defaults")
         raise ValueError("set_auto_prior: downsample >= 1")
     return AutoPriorCfg(clip_px, downsample, cart_downsample, gates[0], gates[1])
+
+
+def pose_graph_args(graphs, max_iterations=20, max_trials=10, lambda_init=0.0):
+    """The argument checks of Context.pose_graph_optimize and pose_graph_plan, made before any library call -> (vertex_off, poses,
+    fixed, edge_off, edge_ij, meas, info6, huber or None, PoseGraphOpts): the graphs packed as roam_pose_graph_optimize takes them.
+    graphs: a list of (poses (V, 3), fixed (V,), edge_ij (E, 2), meas (E, 3), info (E, 3, 3) or (3, 3), huber (E,) or None).
+    ValueError: wrong shapes, an information matrix that is not exactly symmetric, and everything the ABI refuses - no graph or more
+    than 65535, a graph with no vertex or more than 32768, an edge index out of range or i == j, a pose / measurement / information
+    entry / Huber width that is not finite, a negative Huber width, a graph without a fixed vertex, options out of range."""
+    graphs = list(graphs)
+    if not 1 <= len(graphs) <= POSE_GRAPH_MAX_GRAPHS:
+        raise ValueError(f"pose_graph: 1 to {POSE_GRAPH_MAX_GRAPHS} graphs, not {len(graphs)}")
+    max_iterations, max_trials, lambda_init = int(max_iterations), int(max_trials), float(lambda_init)
+    if not 0 <= max_iterations <= POSE_GRAPH_MAX_ITERATIONS:
+        raise ValueError(f"pose_graph: max_iterations in [0, {POSE_GRAPH_MAX_ITERATIONS}], not {max_iterations}")
+    if not 0 <= max_trials <= POSE_GRAPH_MAX_TRIALS:
+        raise ValueError(f"pose_graph: max_trials in [0, {POSE_GRAPH_MAX_TRIALS}], not {max_trials}")
+    if not (np.isfinite(lambda_init) and lambda_init >= 0.0):
+        raise ValueError(f"pose_graph: lambda_init finite and >= 0, not {lambda_init}")
+    P, Fx, IJ, Z, O, Hb = [], [], [], [], [], []
+    any_huber = False
+    for g, graph in enumerate(graphs):
+        if len(graph) != 6:
+            raise ValueError(f"pose_graph: graph {g} is (poses, fixed, edge_ij, meas, info, huber), not {len(graph)} items")
+        poses, fixed, ij, meas, info, huber = graph
+        poses, fixed = np.asarray(poses, np.float64), np.asarray(fixed)
+        if poses.ndim != 2 or poses.shape[1] != 3 or fixed.shape != (poses.shape[0],):
+            raise ValueError(f"pose_graph: graph {g}: poses (V, 3) and fixed (V,), not {poses.shape} and {fixed.shape}")
+        V = poses.shape[0]
+        if not 1 <= V <= POSE_GRAPH_MAX_VERTICES:
+            raise ValueError(f"pose_graph: graph {g}: 1 to {POSE_GRAPH_MAX_VERTICES} vertices, not {V}")
+        if not np.isfinite(poses).all():
+            raise ValueError(f"pose_graph: graph {g}: a pose that is not finite")
+        fixed = fixed != 0
+        if not fixed.any():
+            raise ValueError(f"pose_graph: graph {g} has no fixed vertex")
+        ij = np.asarray(ij)
+        if ij.size == 0:                    # no edges, however the caller wrote that ([] is a float64 array)
+            ij = np.zeros((0, 2), np.int32)
+        if ij.ndim != 2 or ij.shape[1] != 2 or ij.dtype.kind not in "iu":
+            raise ValueError(f"pose_graph: graph {g}: edge_ij (E, 2) of integers, not {ij.dtype} {ij.shape}")
+        E = ij.shape[0]
+        meas = np.asarray(meas, np.float64)
+        meas = meas.reshape(0, 3) if meas.size == 0 else meas
+        if meas.shape != (E, 3):
+            raise ValueError(f"pose_graph: graph {g}: meas ({E}, 3), not {meas.shape}")
+        info = np.asarray(info, np.float64)
+        if info.shape == (3, 3):
+            info = np.broadcast_to(info, (E, 3, 3))
+        elif info.size == 0 and E == 0:
+            info = np.zeros((0, 3, 3))
+        if info.shape != (E, 3, 3):
+            raise ValueError(f"pose_graph: graph {g}: info ({E}, 3, 3) or (3, 3), not {info.shape}")
+        bad = np.flatnonzero(((ij < 0) | (ij >= V)).any(axis=1) | (ij[:, 0] == ij[:, 1]))
+        if bad.size:
+            t = int(bad[0])
+            raise ValueError(f"pose_graph: graph {g}, edge {t}: vertices ({int(ij[t, 0])}, {int(ij[t, 1])}) - two different indices in [0, {V})")
+        bad = np.flatnonzero(~(np.isfinite(meas).all(axis=1) & np.isfinite(info).all(axis=(1, 2))))
+        if bad.size:
+            raise ValueError(f"pose_graph: graph {g}, edge {int(bad[0])}: a measurement or information entry that is not finite")
+        bad = np.flatnonzero((info != info.transpose(0, 2, 1)).any(axis=(1, 2)))
+        if bad.size:
+            raise ValueError(f"pose_graph: graph {g}, edge {int(bad[0])}: the information matrix is not exactly symmetric")
+        if huber is None:
+            hb = np.zeros(E)
+        else:
+            any_huber = True
+            hb = np.asarray(huber, np.float64)
+            if hb.shape != (E,):
+                raise ValueError(f"pose_graph: graph {g}: huber ({E},) or None, not {hb.shape}")
+            bad = np.flatnonzero(~(np.isfinite(hb) & (hb >= 0.0)))
+            if bad.size:
+                raise ValueError(f"pose_graph: graph {g}, edge {int(bad[0])}: a Huber width that is negative or not finite")
+        P.append(poses)
+        Fx.append(fixed.astype(np.uint8))
+        IJ.append(ij.astype(np.int32))
+        Z.append(meas)
+        O.append(info.reshape(E, 9)[:, [0, 1, 2, 4, 5, 8]])
+        Hb.append(hb)
+    vertex_off = np.concatenate([[0], np.cumsum([len(p) for p in P])]).astype(np.int32)
+    edge_off = np.concatenate([[0], np.cumsum([len(e) for e in IJ])]).astype(np.int32)
+    return (vertex_off, np.ascontiguousarray(np.concatenate(P), np.float64), np.ascontiguousarray(np.concatenate(Fx)), edge_off,
+            np.ascontiguousarray(np.concatenate(IJ).reshape(-1, 2)), np.ascontiguousarray(np.concatenate(Z).reshape(-1, 3)),
+            np.ascontiguousarray(np.concatenate(O).reshape(-1, 6)), np.ascontiguousarray(np.concatenate(Hb)) if any_huber else None,
+            PoseGraphOpts(max_iterations, max_trials, lambda_init))
+
+
+def pose_graph_plan(graphs):
+    """roam_pose_graph_plan, host code only (no device, no context): the envelope of every graph in 3 x 3 blocks and the device
+    scratch (bytes) of the call's largest chunk -> (envelope_blocks (n,) int64, scratch_bytes).  There is no reordering: block row k
+    of the system runs from the lowest-numbered free neighbour of free vertex k to the diagonal, so a graph costs about its vertex
+    count plus the sum of j - i over its non-consecutive edges, 144 bytes per block.  ValueError: pose_graph_args's conditions, and a
+    single graph whose scratch exceeds a chunk of 2000 MiB."""
+    vertex_off, _, fixed, edge_off, ij, _, _, _, _ = pose_graph_args(graphs)
+    env = np.zeros(len(vertex_off) - 1, np.int64)
+    nbytes = C.c_int64(0)
+    rc = load_library().roam_pose_graph_plan(len(env), _ptr(vertex_off), _ptr(fixed), _ptr(edge_off), _ptr(ij), _ptr(env), C.byref(nbytes))
+    if rc != ROAM_OK:
+        # pose_graph_args has passed, so what the host half refuses is a graph too large for a launch; it has no context to leave a
+        # text in: find the graph here (one call each) and state its envelope as roam_pose_graph_optimize's text does
+        for g in range(len(env)):
+            v0, e0, e1 = vertex_off[g], edge_off[g], edge_off[g + 1]
+            one_v, one_e = np.array([0, vertex_off[g + 1] - v0], np.int32), np.array([0, e1 - e0], np.int32)
+            f, e = np.ascontiguousarray(fixed[v0:vertex_off[g + 1]]), np.ascontiguousarray(ij[e0:e1])
+            if load_library().roam_pose_graph_plan(1, _ptr(one_v), _ptr(f), _ptr(one_e), _ptr(e), None, None) != ROAM_OK:
+                cidx = np.cumsum(f == 0) - 1
+                a, b = cidx[e[:, 0]], cidx[e[:, 1]]
+                both = (f[e[:, 0]] == 0) & (f[e[:, 1]] == 0)
+                first = np.arange(int((f == 0).sum()))
+                np.minimum.at(first, np.maximum(a, b)[both], np.minimum(a, b)[both])
+                blocks = int((np.arange(len(first)) - first + 1).sum())
+                raise ValueError(f"pose_graph: graph {g}: an envelope of {blocks} blocks ({144 * blocks} bytes of matrix) needs more than "
+                                 f"the {POSE_GRAPH_CHUNK_BYTES} bytes of device scratch of a launch (no reordering: the envelope is "
+                                 "the vertex count plus the span of every loop edge)")
+        raise ValueError("pose_graph: roam_pose_graph_plan refused the graphs")
+    return env, int(nbytes.value)
 
 
 def _f32_rows_in_place(a):
@@ -700,6 +833,20 @@ class Context:
         self.check(self.lib.roam_fmt_register_batch_f32(self.h, _ptr(a3), _ptr(b3), n, rows, cols, row_stride, image_stride, int(clip_px),
                                                         int(downsample), int(cart_downsample), _ptr(out), _ptr(imgs)))
         return (out, imgs) if want_images else out
+
+    def pose_graph_optimize(self, graphs, max_iterations=20, max_trials=10, lambda_init=0.0):
+        """PoseGraphLib.PoseGraphOptimization.optimize for a batch of SE(2) pose graphs in one device pass
+        (roam_pose_graph_optimize: g2o's EdgeSE2 and Levenberg-Marquardt, one workgroup per graph, no host round trip inside a
+        solve).  graphs: a list of (poses (V, 3), fixed (V,), edge_ij (E, 2), meas (E, 3), info (E, 3, 3) or (3, 3), huber (E,) or
+        None) -> (list of optimised poses (V, 3), stats: POSE_GRAPH_STATS rows).  The inputs are not modified.  A graph's result does
+        not depend on the batch.  Arguments are checked by pose_graph_args before any library call; the cost of a graph is its
+        envelope (pose_graph_plan)."""
+        vertex_off, poses, fixed, edge_off, ij, meas, info, huber, opts = pose_graph_args(graphs, max_iterations, max_trials, lambda_init)
+        n = len(vertex_off) - 1
+        stats = np.zeros(n, POSE_GRAPH_STATS)
+        self.check(self.lib.roam_pose_graph_optimize(self.h, n, _ptr(vertex_off), _ptr(poses), _ptr(fixed), _ptr(edge_off), _ptr(ij),
+                                                     _ptr(meas), _ptr(info), _ptr(huber), C.byref(opts), _ptr(stats)))
+        return [poses[vertex_off[g]:vertex_off[g + 1]].copy() for g in range(n)], stats
 
     def phase_correlate(self, src, tgt, hanning=True):
         """FMT.getTranslationUsingPhaseCorrelation: cv2.phaseCorrelate(src, tgt[, cv2.createHanningWindow((cols, rows), CV_32F)])
