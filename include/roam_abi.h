@@ -334,6 +334,72 @@ int32_t roam_pose_graph_optimize(roam_ctx *ctx, int32_t n_graphs, const int32_t 
                                  const double *edge_huber /* E or NULL; 0 = no kernel on that edge */,
                                  const roam_pose_graph_opts *opts, roam_pose_graph_stats *stats /* n */);
 
+/* ---- loop-closure candidates: radar scan context (Kim et al., MulRan).  The reference has no place recognition (Mapping.py:7 is a
+ * commented-out "import m2dp", :61-62 an unused Keyframe.pointCloud): PARITY UNPINNED, the contract is tests/scan_context_model.py.
+ * Bins (integer arithmetic): clip = clip_px if 0 < clip_px < cols else cols; sector s = rows [floor(s rows / S), floor((s + 1) rows / S)),
+ * ring r = columns [floor(r clip / R), floor((r + 1) clip / R)); rows >= S and clip >= R, so no bin is empty.
+ * Descriptor D[s][r], float32: u8 record codes k with an integer floor f: (float)((double)sum max(k - f, 0) / (255.0 count)), the sum an
+ * exact integer; float32 values v with a float floor f >= 0: (float)(sum max((double)v - (double)f, 0) / count), summed in float64 in
+ * a fixed order (within 1 float32 ulp of any other order).  floor = 0 is the plain area mean.
+ * Distance of descriptors q, c: sector s is valid at shift k when |q[s]| |c[(s + k) mod S]| > 0 (float64 norms over the rings);
+ * d_k = 1 - (1 / count_k) sum over valid s of q[s] . c[(s + k) mod S] / (|q[s]| |c[(s + k) mod S]|), d_k = 1 when count_k = 0;
+ * distance = min_k d_k, shift = the lowest k of the minimum; yaw(query) - yaw(candidate) ~ 2 pi shift / S for rows = atan2(y, x) rows / 2 pi.
+ * The device sums normalised columns in float64 in one order per (S, R): the same pair gives the same bits wherever the candidate
+ * sits, whatever the database size, the number of queries and the chunk.
+ * Candidates of query i: the k smallest by (distance, then index) among the entries j < max_index[i] with distance <= max_distance;
+ * unused slots hold index -1, distance +inf, shift 0. */
+#define ROAM_SCAN_CONTEXT_MAX_SECTORS 256
+#define ROAM_SCAN_CONTEXT_MAX_RINGS 128
+#define ROAM_SCAN_CONTEXT_MAX_CLIP 4096     /* range bins kept (the sector's column sums live in LDS) */
+#define ROAM_LOOP_MAX_K 32
+typedef struct roam_loop_db roam_loop_db;
+/* host only, no context: the argument checks of the describing entries and the bin edges (either array may be NULL).  ROAM_E_ARG:
+ * sectors outside [2, 256], rings outside [1, 128], rows < sectors or > 65536, cols < 1, clip < rings or > 4096 */
+int32_t roam_scan_context_plan(int32_t rows, int32_t cols, int32_t clip_px, int32_t sectors, int32_t rings, int32_t *row_edges /* S + 1 */,
+                               int32_t *col_edges /* R + 1 */);
+/* stateless: n host float32 images (strides in floats, as roam_fmt_rotation_batch_f32) -> desc_out (n, S, R) float32.  Images are
+ * uploaded in chunks under 2000 MiB.  ROAM_E_ARG before any device call, the text naming the argument: null pointers, n < 1, what
+ * roam_scan_context_plan refuses, row_stride < cols, image_stride below an image's extent (n > 1), floor negative or not finite */
+int32_t roam_scan_context_f32(roam_ctx *ctx, const float *polar, int32_t n, int32_t rows, int32_t cols, int64_t row_stride,
+                              int64_t image_stride, int32_t clip_px, int32_t sectors, int32_t rings, double floor, float *desc_out);
+/* a database of descriptors in HBM: per entry the float32 descriptor, its columns divided by their float64 norms (what a query
+ * reads: stored entries are never normalised again) and a validity flag per sector.  ROAM_E_ARG: sectors / rings outside the limits,
+ * capacity < 1 or more than fits 2000 MiB */
+int32_t roam_loop_db_create(roam_ctx *ctx, int32_t capacity, int32_t sectors, int32_t rings, roam_loop_db **out);
+int32_t roam_loop_db_destroy(roam_ctx *ctx, roam_loop_db *db);
+int32_t roam_loop_db_count(const roam_loop_db *db, int32_t *count);
+/* describe n host float32 images as roam_scan_context_f32 does and append them on the device (the descriptor never visits the host);
+ * first_index_out (optional) = the index of the first new entry.  ROAM_E_CAPACITY when they do not fit: the database is unchanged */
+int32_t roam_loop_db_add_f32(roam_ctx *ctx, roam_loop_db *db, const float *polar, int32_t n, int32_t rows, int32_t cols, int64_t row_stride,
+                             int64_t image_stride, int32_t clip_px, double floor, int32_t *first_index_out);
+/* append n ready-made descriptors (n, S, R) float32 (finite values: ROAM_E_ARG otherwise) */
+int32_t roam_loop_db_add_desc(roam_ctx *ctx, roam_loop_db *db, const float *desc, int32_t n, int32_t *first_index_out);
+/* the stored descriptors first .. first + n - 1 -> desc_out (n, S, R) */
+int32_t roam_loop_db_get(roam_ctx *ctx, roam_loop_db *db, int32_t first, int32_t n, float *desc_out);
+/* describe n resident u8 records of the engine's pool (pool_idx[n], host) in place and append them: the integer form above with
+ * floor_code in [0, 254], clip = min(clip_px, cfg.clip), clip_px <= 0: cfg.clip.  Runs on the compute stream behind every step
+ * enqueued so far and the pool's pending uploads, blocks until done and leaves the engine's bookkeeping alone.  ROAM_E_ARG: null
+ * pointers, n < 1, a pool index out of range, cfg.rows < sectors, clip < rings or > 4096, floor_code outside [0, 254] */
+int32_t roam_engine_loop_db_add(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
+                                int32_t *first_index_out);
+/* queries are entries of the database (add first, then ask): for query_index[i], i < n_query, the distance and shift to every entry
+ * and its k candidates as defined above.  max_index[i] is clamped to [0, count].  dist_full / shift_full (optional, for tests):
+ * (n_query, count) float64 / int32, every pair whatever max_index says.  Queries are processed in chunks that keep the device scratch
+ * under 2000 MiB (ROAM_LOOP_CHUNK_BYTES in the environment, read per call, lowers where a batch is cut - for tests).
+ * ROAM_E_ARG before any device call: null pointers, n_query < 1, k outside [1, 32], max_distance NaN, a query index outside the
+ * database */
+int32_t roam_loop_db_query(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index, int32_t k,
+                           double max_distance, int32_t *cand_index /* n k */, double *cand_dist /* n k */, int32_t *cand_shift /* n k */,
+                           double *dist_full, int32_t *shift_full);
+/* measurement: HIP events on the context stream around `reps` launches, two warm ones first -> milliseconds per launch.
+ * roam_engine_time_loop_describe: the describing kernel of roam_engine_loop_db_add on the same n records, written into the free
+ * entries of db (they must fit; nothing is appended).  roam_time_loop_db_query: the distance kernel (with the max_index mask, as a
+ * query without the full outputs runs it) and the selection kernel of roam_loop_db_query, which must fit one launch */
+int32_t roam_engine_time_loop_describe(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
+                                       int32_t reps, float *ms_per_rep);
+int32_t roam_time_loop_db_query(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index, int32_t k,
+                                double max_distance, int32_t reps, float *distance_ms, float *select_ms);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous

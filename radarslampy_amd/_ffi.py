@@ -65,6 +65,11 @@ POSE_GRAPH_MAX_ITERATIONS = 1000
 POSE_GRAPH_MAX_TRIALS = 1000
 POSE_GRAPH_CHUNK_BYTES = 2000 << 20     # device scratch of one launch
 
+SCAN_CONTEXT_MAX_SECTORS, SCAN_CONTEXT_MAX_RINGS = 256, 128     # roam_abi.h ROAM_SCAN_CONTEXT_MAX_*
+SCAN_CONTEXT_MAX_ROWS, SCAN_CONTEXT_MAX_CLIP = 65536, 4096
+LOOP_MAX_K = 32                         # roam_abi.h ROAM_LOOP_MAX_K
+LOOP_DB_BYTES = 2000 << 20              # a database, and the device scratch of one launch
+
 
 PRIOR_RECORD = np.dtype([("out6", np.float64, (6,)), ("affine", np.float32, (2, 3)), ("source", np.uint8)])     # Engine.step_prior's rows
 
@@ -122,6 +127,20 @@ _SIGS = {
                                     _P(C.c_int32), _vp]),
     "roam_pose_graph_plan": (C.c_int32, [C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(C.c_int64)]),
     "roam_pose_graph_optimize": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PoseGraphOpts), _vp]),
+    "roam_scan_context_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "roam_scan_context_f32": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_double, _vp]),
+    "roam_loop_db_create": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, _P(_vp)]),
+    "roam_loop_db_destroy": (C.c_int32, [_vp, _vp]),
+    "roam_loop_db_count": (C.c_int32, [_vp, _P(C.c_int32)]),
+    "roam_loop_db_add_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_double,
+                                         _P(C.c_int32)]),
+    "roam_loop_db_add_desc": (C.c_int32, [_vp, _vp, _vp, C.c_int32, _P(C.c_int32)]),
+    "roam_loop_db_get": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "roam_engine_loop_db_add": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _P(C.c_int32)]),
+    "roam_loop_db_query": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "roam_engine_time_loop_describe": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
+    "roam_time_loop_db_query": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _P(C.c_float), _P(C.c_float)]),
     "roam_engine_create": (C.c_int32, [_vp, _P(EngineCfg)]),
     "roam_engine_destroy": (C.c_int32, [_vp]),
     "roam_engine_upload_scan": (C.c_int32, [_vp, C.c_int32, _vp]),
@@ -501,6 +520,71 @@ def pose_graph_plan(graphs):
     return env, int(nbytes.value)
 
 
+def scan_context_plan(rows, cols, clip_px, sectors, rings):
+    """roam_scan_context_plan, host code only (no device, no context): the argument checks of the describing entries and the bin
+    edges -> (clip, row_edges (S + 1,), col_edges (R + 1,)) int32.  Sector s covers the rows [row_edges[s], row_edges[s + 1]), ring r
+    the columns [col_edges[r], col_edges[r + 1]); clip = clip_px if 0 < clip_px < cols else cols.  ValueError: sectors outside [2, 256],
+    rings outside [1, 128], rows < sectors or > 65536, clip < rings or > 4096, or anything that is no integer."""
+    for name, v in (("rows", rows), ("cols", cols), ("sectors", sectors), ("rings", rings)):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool):
+            raise ValueError(f"scan context: {name} is an integer, not {v!r}")
+    if clip_px is not None and (not isinstance(clip_px, numbers.Integral) or isinstance(clip_px, bool)):
+        raise ValueError(f"scan context: clip_px is an integer or None, not {clip_px!r}")
+    if not 2 <= sectors <= SCAN_CONTEXT_MAX_SECTORS:
+        raise ValueError(f"scan context: sectors in [2, {SCAN_CONTEXT_MAX_SECTORS}], not {sectors}")
+    if not 1 <= rings <= SCAN_CONTEXT_MAX_RINGS:
+        raise ValueError(f"scan context: rings in [1, {SCAN_CONTEXT_MAX_RINGS}], not {rings}")
+    if not sectors <= rows <= SCAN_CONTEXT_MAX_ROWS:
+        raise ValueError(f"scan context: rows in [sectors = {sectors}, {SCAN_CONTEXT_MAX_ROWS}], not {rows}")
+    if not 1 <= cols < 2 ** 31:
+        raise ValueError(f"scan context: cols >= 1, not {cols}")
+    clip = int(clip_px) if clip_px is not None and 0 < clip_px < cols else int(cols)
+    if not rings <= clip <= SCAN_CONTEXT_MAX_CLIP:
+        raise ValueError(f"scan context: clip_px (the range bins kept) in [rings = {rings}, {SCAN_CONTEXT_MAX_CLIP}], not {clip}")
+    re, ce = np.empty(sectors + 1, np.int32), np.empty(rings + 1, np.int32)
+    rc = load_library().roam_scan_context_plan(int(rows), int(cols), clip, int(sectors), int(rings), _ptr(re), _ptr(ce))
+    if rc != ROAM_OK:
+        raise ValueError(f"scan context: roam_scan_context_plan refused rows {rows}, cols {cols}, clip_px {clip_px}, {sectors} x {rings}")
+    return clip, re, ce
+
+
+def scan_context_floor(floor):
+    """the float floor of the describing entries: finite and >= 0 (ValueError otherwise)"""
+    if not isinstance(floor, numbers.Real) or isinstance(floor, bool) or not np.isfinite(floor) or floor < 0:
+        raise ValueError(f"scan context: floor finite and >= 0, not {floor!r}")
+    return float(floor)
+
+
+def scan_context_images(polar, clip_px, sectors, rings):
+    """the image operand of the describing entries -> (a3, n, rows, cols, row_stride, image_stride, clip): a 2-D image or a 3-D batch
+    of float32, read in place where its strides allow (_f32_rows_in_place).  ValueError as scan_context_plan"""
+    a = np.asarray(polar)
+    if a.ndim not in (2, 3) or a.size == 0:
+        raise ValueError(f"scan context: a 2-D image or a 3-D batch, not shape {a.shape}")
+    a = _f32_rows_in_place(a)
+    a3 = a if a.ndim == 3 else a[None]
+    n, rows, cols = a3.shape
+    clip, _, _ = scan_context_plan(rows, cols, clip_px, sectors, rings)
+    row_stride = a3.strides[1] // 4
+    image_stride = a3.strides[0] // 4 if n > 1 else rows * row_stride
+    return a3, n, rows, cols, row_stride, image_stride, clip
+
+
+def loop_query_args(count, indices, max_index, k, max_distance):
+    """the checks of LoopDb.query before any library call -> (query_index, max_index) int32 arrays"""
+    q = np.ascontiguousarray(indices, np.int32).ravel()
+    m = np.ascontiguousarray(max_index, np.int32).ravel()
+    if len(q) < 1 or len(q) != len(m):
+        raise ValueError(f"loop query: query indices and max_index of one length >= 1, not {len(q)} and {len(m)}")
+    if q.min() < 0 or q.max() >= count:
+        raise ValueError(f"loop query: query indices in [0, {count})")
+    if not isinstance(k, numbers.Integral) or isinstance(k, bool) or not 1 <= k <= LOOP_MAX_K:
+        raise ValueError(f"loop query: k in [1, {LOOP_MAX_K}], not {k!r}")
+    if not isinstance(max_distance, numbers.Real) or np.isnan(max_distance):
+        raise ValueError(f"loop query: max_distance is a number, not {max_distance!r}")
+    return q, m
+
+
 def _f32_rows_in_place(a):
     """a float32 view with unit column stride and forward row / image strides is read in place; anything else is copied"""
     ok = a.dtype == np.float32 and a.strides[-1] == 4 and a.strides[-2] % 4 == 0 and a.strides[-2] >= 4 * a.shape[-1]
@@ -848,6 +932,16 @@ class Context:
                                                      _ptr(meas), _ptr(info), _ptr(huber), C.byref(opts), _ptr(stats)))
         return [poses[vertex_off[g]:vertex_off[g + 1]].copy() for g in range(n)], stats
 
+    def scan_context(self, polar, sectors=60, rings=20, clip_px=None, floor=0.0):
+        """the scan-context descriptors of a 2-D float32 polar image or a 3-D batch (roam_scan_context_f32) -> (n, sectors, rings)
+        float32: the area mean of max(v - floor, 0) over integer bins (scan_context_plan).  ValueError before any library call"""
+        a3, n, rows, cols, row_stride, image_stride, _ = scan_context_images(polar, clip_px, sectors, rings)
+        floor = scan_context_floor(floor)
+        out = np.empty((n, sectors, rings), np.float32)
+        self.check(self.lib.roam_scan_context_f32(self.h, _ptr(a3), n, rows, cols, row_stride, image_stride, int(clip_px or 0), int(sectors),
+                                                  int(rings), floor, _ptr(out)))
+        return out
+
     def phase_correlate(self, src, tgt, hanning=True):
         """FMT.getTranslationUsingPhaseCorrelation: cv2.phaseCorrelate(src, tgt[, cv2.createHanningWindow((cols, rows), CV_32F)])
         (roam_phase_correlate_f32).  Two 2-D images -> ((dx, dy), response); two 3-D batches of one shape -> (dxdy (n, 2),
@@ -936,6 +1030,91 @@ class Context:
 
 _default = {}
 _lock = threading.Lock()
+
+
+class LoopDb:
+    """A database of scan-context descriptors in HBM (roam_loop_db): add, then query.  Bound to the context it was made on (None: the
+    default context, asked for after the arguments have passed)."""
+
+    def __init__(self, ctx, capacity: int, sectors: int = 60, rings: int = 20):
+        for name, v, lo, hi in (("capacity", capacity, 1, 2 ** 31 - 1), ("sectors", sectors, 2, SCAN_CONTEXT_MAX_SECTORS),
+                                ("rings", rings, 1, SCAN_CONTEXT_MAX_RINGS)):
+            if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not lo <= v <= hi:
+                raise ValueError(f"loop db: {name} an integer in [{lo}, {hi}], not {v!r}")
+        per = sectors * (4 * rings + 8 * ((rings + 3) & ~3) + 4)
+        if capacity > LOOP_DB_BYTES // per:
+            raise ValueError(f"loop db: capacity at most {LOOP_DB_BYTES // per} ({per} bytes per entry, {LOOP_DB_BYTES} in all), not {capacity}")
+        ctx = ctx or default_context()
+        self.ctx, self.capacity, self.sectors, self.rings = ctx, int(capacity), int(sectors), int(rings)
+        h = _vp()
+        ctx.check(ctx.lib.roam_loop_db_create(ctx.h, self.capacity, self.sectors, self.rings, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.roam_loop_db_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        n = C.c_int32(0)
+        self.ctx.check(self.ctx.lib.roam_loop_db_count(self.h, C.byref(n)))
+        return n.value
+
+    def add_f32(self, polar, clip_px=None, floor=0.0):
+        """describe a 2-D float32 polar image or a 3-D batch on the device and append -> the index of the first new entry"""
+        a3, n, rows, cols, row_stride, image_stride, _ = scan_context_images(polar, clip_px, self.sectors, self.rings)
+        floor = scan_context_floor(floor)
+        first = C.c_int32(-1)
+        self.ctx.check(self.ctx.lib.roam_loop_db_add_f32(self.ctx.h, self.h, _ptr(a3), n, rows, cols, row_stride, image_stride,
+                                                         int(clip_px or 0), floor, C.byref(first)))
+        return first.value
+
+    def add_desc(self, desc):
+        """append ready-made descriptors, (S, R) or (n, S, R) -> the index of the first new entry"""
+        d = np.ascontiguousarray(desc, np.float32)
+        d = d[None] if d.ndim == 2 else d
+        if d.ndim != 3 or d.shape[0] < 1 or d.shape[1:] != (self.sectors, self.rings):
+            raise ValueError(f"loop db: descriptors (n, {self.sectors}, {self.rings}), not {d.shape}")
+        if not np.isfinite(d).all():
+            raise ValueError("loop db: a descriptor value that is not finite")
+        first = C.c_int32(-1)
+        self.ctx.check(self.ctx.lib.roam_loop_db_add_desc(self.ctx.h, self.h, _ptr(d), len(d), C.byref(first)))
+        return first.value
+
+    def get(self, first=0, n=None):
+        count = len(self)
+        n = count - first if n is None else n
+        if first < 0 or n < 1 or first + n > count:
+            raise ValueError(f"loop db: entries [{first}, {first} + {n}) outside the {count} stored")
+        out = np.empty((n, self.sectors, self.rings), np.float32)
+        self.ctx.check(self.ctx.lib.roam_loop_db_get(self.ctx.h, self.h, int(first), int(n), _ptr(out)))
+        return out
+
+    def query(self, indices, max_index, k=8, max_distance=np.inf, want_full=False):
+        """roam_loop_db_query: for each query entry the k candidates among the entries below its max_index with distance <=
+        max_distance -> (index (m, k) int32, distance (m, k) float64, shift (m, k) int32); unused slots -1, +inf, 0.  want_full: also
+        the (m, count) distance and shift to every entry"""
+        q, m = loop_query_args(len(self), indices, max_index, k, max_distance)
+        ci, cd, cs = np.empty((len(q), k), np.int32), np.empty((len(q), k), np.float64), np.empty((len(q), k), np.int32)
+        df = np.empty((len(q), len(self)), np.float64) if want_full else None
+        sf = np.empty((len(q), len(self)), np.int32) if want_full else None
+        self.ctx.check(self.ctx.lib.roam_loop_db_query(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance), _ptr(ci),
+                                                       _ptr(cd), _ptr(cs), _ptr(df), _ptr(sf)))
+        return (ci, cd, cs, df, sf) if want_full else (ci, cd, cs)
+
+    def time_query(self, indices, max_index, k=8, max_distance=np.inf, reps=20):
+        """(distance kernel ms, selection kernel ms) per launch of this query, HIP events around reps launches (roam_time_loop_db_query)"""
+        q, m = loop_query_args(len(self), indices, max_index, k, max_distance)
+        d_ms, s_ms = C.c_float(0), C.c_float(0)
+        self.ctx.check(self.ctx.lib.roam_time_loop_db_query(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance), int(reps),
+                                                            C.byref(d_ms), C.byref(s_ms)))
+        return float(d_ms.value), float(s_ms.value)
 
 
 def default_context(device_id: int = None) -> Context:

@@ -1803,6 +1803,27 @@ int32_t roam_engine_fmt_register(roam_ctx *ctx, int32_t n, const int32_t *prev_p
     return roam_fmt_register_run(ctx, in, n, e->cfg.rows, clip, R, Rc, out6, nullptr);
 }
 
+int32_t roam_engine_loop_db_add(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
+                                int32_t *first_index_out)
+{
+    ENGINE();
+    ARG_CHECK(ctx, db && n >= 1 && pool_idx);
+    for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
+    // as roam_engine_fmt_rotation: behind every step enqueued so far and the uploads of the pool, the engine's bookkeeping untouched
+    return roam_loop_db_add_records(ctx, db, e->pool, (int64_t)e->rec_bytes, e->cfg.stride, e->cfg.payload_off, e->cfg.rows, e->cfg.clip, n,
+                                    pool_idx, clip_px, floor_code, first_index_out, e->uploads_pending ? ctx->ev_up : nullptr, 0, nullptr);
+}
+
+int32_t roam_engine_time_loop_describe(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
+                                       int32_t reps, float *ms_per_rep)
+{
+    ENGINE();
+    ARG_CHECK(ctx, db && n >= 1 && pool_idx && ms_per_rep);
+    for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
+    return roam_loop_db_add_records(ctx, db, e->pool, (int64_t)e->rec_bytes, e->cfg.stride, e->cfg.payload_off, e->cfg.rows, e->cfg.clip, n,
+                                    pool_idx, clip_px, floor_code, nullptr, e->uploads_pending ? ctx->ev_up : nullptr, reps, ms_per_rep);
+}
+
 int32_t roam_engine_lane_image(roam_ctx *ctx, int32_t lane, int32_t level, uint8_t *out, int64_t cap)
 {
     ENGINE();

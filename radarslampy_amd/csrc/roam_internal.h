@@ -311,3 +311,11 @@ int32_t roam_fmt_auto_enqueue(roam_ctx *ctx, FmtAuto *a, hipStream_t st, const F
                               const int32_t *curr, const int32_t *pair_of, uint8_t *prior_slot, FmtPriorRec *rec_slot);
 // FMT.py:84-90 on the host, the blocking pass's own expressions: a record's raw shifts -> angle (what the device wrote) and scale
 double roam_fmt_scale(double log_base, double shift_x);
+
+// loopclosure.hip: roam_engine_loop_db_add (engine.hip) after its own checks (the engine, the pool indices): describe n resident u8
+// records of `cols` range bins (pool_idx: host) and append them to db, on ctx->stream, blocking.  after (optional): an event the
+// stream waits for once the arguments have passed - the pool's pending uploads.  time_ms (optional): nothing is appended; time_reps
+// launches of the describing kernel into the free entries are timed with events (roam_engine_time_loop_describe)
+int32_t roam_loop_db_add_records(roam_ctx *ctx, roam_loop_db *db, const uint8_t *pool, int64_t rec_bytes, int64_t row_stride, int32_t payload_off,
+                                 int32_t rows, int32_t cols, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
+                                 int32_t *first_index_out, hipEvent_t after, int32_t time_reps, float *time_ms);

@@ -295,6 +295,27 @@ class Engine:
                                                          int(downsample), int(cart_downsample), _ffi._ptr(out)))
         return out
 
+    def loop_db_add(self, detector, pool_idx, clip_px=None, floor_code=None):
+        """describe resident scans as scan contexts and store them in a LoopClosure.LoopDetector (or an _ffi.LoopDb) without moving
+        image data (roam_engine_loop_db_add): the u8 form, mean of max(code - floor_code, 0) / 255 over the bins -> the index of the
+        first new entry.  clip_px / floor_code default to the detector's.  Runs behind the steps enqueued so far, blocks until done and
+        leaves the engine's state alone.  ValueError before any device call for a bad index list, clip or floor."""
+        db = getattr(detector, "db", detector)
+        idx = np.ascontiguousarray(pool_idx, np.int32).ravel()
+        if len(idx) < 1 or idx.min() < 0 or idx.max() >= self.pool_scans:
+            raise ValueError(f"loop_db_add: at least one pool index, all in [0, {self.pool_scans})")
+        if clip_px is None:
+            clip_px = getattr(detector, "clip_px", None)
+        if floor_code is None:
+            floor_code = detector.floorCode() if hasattr(detector, "floorCode") else 0
+        if not isinstance(floor_code, (int, np.integer)) or isinstance(floor_code, bool) or not 0 <= floor_code <= 254:
+            raise ValueError(f"loop_db_add: floor_code an integer in [0, 254], not {floor_code!r}")
+        _ffi.scan_context_plan(self.rows, self.cfg.clip, clip_px, db.sectors, db.rings)
+        first = C.c_int32(-1)
+        self.ctx.check(self.lib.roam_engine_loop_db_add(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), int(clip_px or 0), int(floor_code),
+                                                        C.byref(first)))
+        return first.value
+
     def lane_image(self, lane: int, level: int = 0):
         W = 2 * (self.cfg.clip // 2)
         for _ in range(level):
