@@ -156,7 +156,7 @@ int32_t roam_comm_destroy(roam_ctx *ctx)
 
 }  // extern "C"
 
-// used by engine.hip (the keyframe payload lives in the engine's buffers)
+// used by engine_map.hip (the keyframe payload lives in the engine's buffers)
 int32_t roam_comm_bcast_bytes(roam_ctx *ctx, void *dev_buf, size_t bytes, int root)
 {
     if (!ctx->comm) { ROAM_SET_ERR(ctx, "communicator not initialised"); return ROAM_E_STATE; }

@@ -534,7 +534,7 @@ extern "C" int32_t roam_loop_db_get(roam_ctx *ctx, roam_loop_db *db, int32_t fir
     return ROAM_OK;
 }
 
-// engine.hip's roam_engine_loop_db_add after its own checks (the engine, the pool indices): n resident u8 records of `cols` range bins.
+// engine_lanes.hip's roam_engine_loop_db_add after its own checks (the engine, the pool indices): n resident u8 records of `cols` range bins.
 // after (optional): an event the stream waits for once the arguments have passed - the pool's pending uploads.  time_ms (optional):
 // instead of appending, time_reps launches of the describing kernel into the free entries between two events, two warm ones first
 int32_t roam_loop_db_add_records(roam_ctx *ctx, roam_loop_db *db, const uint8_t *pool, int64_t rec_bytes, int64_t row_stride, int32_t payload_off,

@@ -20,7 +20,7 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
-struct Engine;
+struct Engine;          // engine.h, private to the engine*.hip units
 struct Comm;
 struct FftTwiddles;
 
@@ -312,7 +312,7 @@ int32_t roam_fmt_auto_enqueue(roam_ctx *ctx, FmtAuto *a, hipStream_t st, const F
 // FMT.py:84-90 on the host, the blocking pass's own expressions: a record's raw shifts -> angle (what the device wrote) and scale
 double roam_fmt_scale(double log_base, double shift_x);
 
-// loopclosure.hip: roam_engine_loop_db_add (engine.hip) after its own checks (the engine, the pool indices): describe n resident u8
+// loopclosure.hip: roam_engine_loop_db_add (engine_lanes.hip) after its own checks (the engine, the pool indices): describe n resident u8
 // records of `cols` range bins (pool_idx: host) and append them to db, on ctx->stream, blocking.  after (optional): an event the
 // stream waits for once the arguments have passed - the pool's pending uploads.  time_ms (optional): nothing is appended; time_reps
 // launches of the describing kernel into the free entries are timed with events (roam_engine_time_loop_describe)
