@@ -253,8 +253,8 @@ int32_t roam_fmt_rotation(roam_ctx *ctx, const float *src_polar, const float *tg
 /* FMT.getTranslationUsingPhaseCorrelation (FMT.py:13-33): cv2.phaseCorrelate(src, tgt, createHanningWindow((cols, rows), CV_32F))
  * for `batch` pairs of rows x cols float32 images (row_stride / image_stride in elements).  hanning = 0: no window
  * (cv2.phaseCorrelate(src, tgt)).  out_dxdy (batch, 2) f64 [dx, dy], out_response (batch) f64 (may be NULL).
- * The images are zero-padded to the optimal DFT size (2^a 3^b 5^c) and transformed by the mixed-radix FFT of csrc/fft.hip; a large
- * batch is processed in chunks that keep the device scratch under 2 GB.  ROAM_E_ARG: rows or cols outside [2, 4096], batch < 1,
+ * The images are zero-padded to the optimal DFT size (2^a 3^b 5^c) and transformed by the mixed-radix FFT of csrc/fft.hip (the
+ * correlation on top of it: csrc/phasecorr.hip); a large batch is processed in chunks that keep the device scratch under 2 GB.  ROAM_E_ARG: rows or cols outside [2, 4096], batch < 1,
  * a null src / tgt / out_dxdy, row_stride < cols, image_stride smaller than one image's extent (batch > 1). */
 int32_t roam_phase_correlate_f32(roam_ctx *ctx, const float *src, const float *tgt, int32_t batch, int32_t rows, int32_t cols,
                                  int64_t row_stride, int64_t image_stride, int32_t hanning, double *out_dxdy, double *out_response);

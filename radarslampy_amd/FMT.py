@@ -1,5 +1,5 @@
 """Fourier-Mellin registration with the reference's names (reference FMT.py:10-100): the rotation prior (csrc/fmt_batch.hip, one pair
-or a batch of pairs in the same pass), the translation by phase correlation (csrc/fft.hip), the rotation of an image (csrc/warpaffine.hip) and the chain of the three in one
+or a batch of pairs in the same pass), the translation by phase correlation (csrc/phasecorr.hip), the rotation of an image (csrc/warpaffine.hip) and the chain of the three in one
 device pass (getTransformUsingFMT, csrc/fmt_register.hip);
 the computation runs on the MI355X.  SURVEY §8f-f4."""
 import math

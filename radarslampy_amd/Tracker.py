@@ -3,7 +3,7 @@ track()/getTransform() signatures, return orders and dtypes; the arithmetic runs
 
 The Fourier-Mellin rotation estimate that track() computes first and returns in slot 3 (Tracker.py:62-63; the reference
 only prints it, RawROAMSystem.py:187-188) runs on the GPU as well (FMT.getRotationUsingFMT: csrc/fmt_batch.hip and the
-correlation of csrc/fft.hip).
+correlation of csrc/phasecorr.hip, driven by csrc/fmt.hip).
 One documented difference: paramFlags["rejectOutliers"]=False returns an all-ones pruning mask where the reference raises
 NameError (Tracker.py:93-104).
 One addition: paramFlags["fmtPrior"] (default False) makes track() run the whole registration (FMT.getTransformUsingFMT) and start

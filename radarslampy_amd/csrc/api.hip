@@ -1,6 +1,7 @@
 // C-ABI: context management + "stage" entry points (host arrays in / out, one reference
 // function each).  See include/roam_abi.h for the contract and the reference citations.
 #include "roam_internal.h"
+#include "fft.h"
 #include <cmath>
 #include <cstdlib>
 #include <new>

@@ -1,6 +1,6 @@
 // OpenCV's coordinate maps and its bilinear remap (imgwarp.cpp: warpPolar, warpAffine, remap with INTER_LINEAR on CV_32F), one
 // definition of each piece for every unit that samples an image the way cv2 does: warp.hip, warppolar.hip, warpaffine.hip, fmt_batch.hip,
-// fmt_register.hip, fft.hip.  Bit-exactness with the oracle rests on these lines, so they are written with explicit
+// fmt_register.hip, phasecorr.hip.  Bit-exactness with the oracle rests on these lines, so they are written with explicit
 // IEEE round-to-nearest intrinsics and compiled without contraction (roam_internal.h).
 //   maps:   a float coordinate (mx, my) per output pixel - the inverse polar map (cartToPolar = sqrt + the degree-7 fastAtan
 //           polynomial, [log(mag + 1)], the two float64 divides, one wrapped border row above the source), the forward polar map from

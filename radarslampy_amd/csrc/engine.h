@@ -3,6 +3,7 @@
 // the other units of the library see the forward declaration of roam_internal.h.  Overview: engine.hip.
 #pragma once
 #include "roam_internal.h"
+#include "fmt.h"
 #include "retrack.h"
 #include <algorithm>
 
@@ -38,7 +39,7 @@ struct Engine {
     size_t prior_bytes = 0;             // of one slot
     bool prior_set = false;             // prior_host's slot of the next step holds a prior that no step has consumed
     int64_t nstep = 0;
-    // the prior as a mode (roam_engine_set_auto_prior): fft.hip's in-step registration on ap_stream writes the step's slot of prior_dev and
+    // the prior as a mode (roam_engine_set_auto_prior): fmt.hip's in-step registration on ap_stream writes the step's slot of prior_dev and
     // one record per lane into ap_rec (ring of RES_RING x B, behind the pass's buffers in ap_slab), mirrored to pinned memory behind the step
     FmtAuto *ap = nullptr;
     FmtAutoPlan ap_plan = {};

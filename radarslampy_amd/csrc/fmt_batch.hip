@@ -8,9 +8,10 @@
 //                         cv2.createHanningWindow factor, rounded to float32, zero-padded into the float64 M x N plane of the FFT
 // The maps, the remap and the window product are cvmap.h's, the same definitions warppolar.hip calls; like warppolar.hip the
 // radius, cos / sin and window tables come from the host's libm, so that the log-polar image equals the oracle's bit for bit.
-// The correlation behind it is fft.hip's (roam_fmt_batch_run): these kernels only fill its planes.  No atomics: every output element
+// The correlation behind it is phasecorr.hip's, the driver fmt.hip's (roam_fmt_batch_run): these kernels only fill its planes.  No atomics: every output element
 // has one writer, and an image's result does not depend on its place in the batch.
 #include "cvmap.h"
+#include "fmt.h"
 
 // grid (ceil(nw / 64), rows, images): out[z] = rows x nw, two taps per output column, rows untouched
 template <bool U8>
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(64) void fmtb_cart_kernel(const float *__restrict__
 }
 
 // grid (ceil(N / 64), M, images): cart[z] -> the M x N plane of image z (zero outside dh x dw).  Image z < nb writes plane z, the others
-// plane z + plane_gap (the targets' planes lie behind the work planes of the transforms, fft.hip).  tab: cos, sin per row (2 dh
+// plane z + plane_gap (the targets' planes lie behind the work planes of the transforms, phasecorr.hip).  tab: cos, sin per row (2 dh
 // doubles) | window factor per row (dh) | per column (dw); br: the radius per column (dw floats).  lp_out (optional): images x dh x dw.
 __global__ __launch_bounds__(64) void fmtb_logpolar_kernel(const float *__restrict__ cart, int R, int dw, int dh, int M, int N, int nb,
                                                            int64_t plane_gap, const double *__restrict__ tab, const float *__restrict__ br,

@@ -16,11 +16,12 @@
 //   fmtr_prior_kernel          the in-step pass only: FMT.flowPriorFromFMT behind the second correlation, one thread per lane - the
 //                              affine the lane's tracker starts from, its use byte and the lane's record.
 // The polar map, the affine fixed point, the remap and the window product are cvmap.h's, the same definitions warppolar.hip,
-// warpaffine.hip and pc_window_kernel call.  The correlation behind it is fft.hip's (roam_fmt_register_run): these kernels only fill
+// warpaffine.hip and pc_window_kernel call.  The correlation behind it is phasecorr.hip's, the driver fmt.hip's (roam_fmt_register_run): these kernels only fill
 // its planes.  No atomics: every output element has one writer, and an image's result does not depend on its place in the batch.
 // One thread per output pixel in a 32 x 8 tile, as warp_affine_kernel: a tile's taps lie in a compact patch of the source (a sector
 // of the polar image, a turned rectangle of the Cartesian one), so its lines are shared through the L1 and the L2; stores are coalesced.
 #include "cvmap.h"
+#include "fmt.h"
 
 #define FMTR_TILE_X 32
 #define FMTR_TILE_Y 8
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(FMTR_TILE_X * FMTR_TILE_Y) void fmtr_cart_kernel(Fm
 
 // grid (ceil(N / 32), ceil(M / 8), images): cart[z] (S x S) -> the M x N plane of image z (zero outside S x S).  Image z < nb is a
 // source: it is turned by Minv[z] (6 doubles, destination -> source) on the way and writes plane z; the others are targets and write
-// plane z + plane_gap (their planes lie behind the work planes of the transforms, fft.hip).  win: the window factor per row (S
+// plane z + plane_gap (their planes lie behind the work planes of the transforms, phasecorr.hip).  win: the window factor per row (S
 // doubles), then per column (S).  rot_out (optional): nb x S x S, the turned sources before the window.
 __global__ __launch_bounds__(FMTR_TILE_X * FMTR_TILE_Y) void fmtr_rotate_window_kernel(const float *__restrict__ cart, int S, int M, int N, int nb,
                                                                                         int64_t plane_gap, const double *__restrict__ Minv,
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(FMTR_TILE_X * FMTR_TILE_Y) void fmtr_rotate_window_
     planes[(plane * M + y) * N + x] = val;
 }
 
-// pair i: rot3[3 i + 1] = the shift along the angle axis of the log-polar correlation.  FMT.py:84-90 for the angle (fft.hip's blocking
+// pair i: rot3[3 i + 1] = the shift along the angle axis of the log-polar correlation.  FMT.py:84-90 for the angle (fmt.hip's blocking
 // pass: the same expression), then roam_rotation_inverse_map's arithmetic about (c, c) with the device's cos / sin
 __global__ __launch_bounds__(64) void fmtr_angle_matrix_kernel(const double *__restrict__ rot3, int n, int sz, double c, double *__restrict__ ang,
                                                                double *__restrict__ Minv)

@@ -7,7 +7,7 @@
 //   forward (Cartesian -> polar): dh rows of angle, dw columns of radius; the radius table br (dw floats) and cos / sin per row
 //     (2 dh doubles) come from the HOST's libm, as OpenCV computes them, so that they equal what the oracle's C computes.
 //   The maps and the remap are cvmap.h's, the definitions every unit that samples as OpenCV does calls; the host tables and the packed
-//   upload defined here (roam_warp_polar_tables, roam_upload_packed_f32) serve fft.hip and warpaffine.hip too.
+//   upload defined here (roam_warp_polar_tables, roam_upload_packed_f32) serve phasecorr.hip, fmt.hip and warpaffine.hip too.
 //   remap: coordinates rounded to 1/32 px (cvRound, half to even), tap index saturated to int16, bilinear weights
 //     wy * wx from the 32-entry tables, taps outside the (padded) source read 0, sum in OpenCV's order.
 // The inverse semilog mode takes (float)log((double)(mag + 1)) where OpenCV uses hal::log32f: parity with OpenCV is unpinned there

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the batched Fourier-Mellin rotation prior (roam_fmt_rotation_batch_f32, roam_engine_fmt_rotation; csrc/fmt_batch.hip
-and the correlation of csrc/fft.hip) against the oracle's restatement of FMT.getRotationUsingFMT.  The inputs and the oracle's
+and the correlation of csrc/phasecorr.hip, driven by csrc/fmt.hip) against the oracle's restatement of FMT.getRotationUsingFMT.  The inputs and the oracle's
 results are tests/fmt_batch_cases.py (four shapes, four pairs each; the CPU test asserts a unique correlation peak for every pair).
 
 Bounds: the angle to 1e-5 rad, the scale to 1e-5 and the response to 1e-4 max(1, |response|) - the bounds of

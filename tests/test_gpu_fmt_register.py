@@ -1,5 +1,5 @@
 """GPU (-m gpu): the Fourier-Mellin registration in one device pass (roam_fmt_register_batch_f32, roam_engine_fmt_register;
-csrc/fmt_register.hip and the correlations of csrc/fft.hip) against its parts and against the all-CPU chain of
+csrc/fmt_register.hip and the correlations of csrc/phasecorr.hip, driven by csrc/fmt.hip) against its parts and against the all-CPU chain of
 tests/fmt_register_cases.py (five shapes, four pairs each; the CPU test asserts a unique peak in both correlations of every pair).
 
   (a) columns 0-2 are fmt_rotation_batch's on the same input, bit for bit;

@@ -1,4 +1,4 @@
-"""Phase correlation at any image size (roam_phase_correlate_f32, csrc/fft.hip) against the oracle's float64 restatement of
+"""Phase correlation at any image size (roam_phase_correlate_f32, csrc/phasecorr.hip) against the oracle's float64 restatement of
 cv2.phaseCorrelate, and the mixed-radix FFT alone against numpy.  The inputs are tests/phase_correlate_cases.py.
 
 Tolerances.  The device and the oracle evaluate one float64 formula in different summation orders, so they agree to the rounding of
