@@ -687,6 +687,23 @@ int32_t roam_debug_fft2_f64(roam_ctx *ctx, const double *re_in, const double *im
 int32_t roam_debug_ssc_batch(roam_ctx *ctx, const double *kp, const int32_t *count, int32_t P, int32_t kp_cap, int32_t n_active,
                              int32_t first, int32_t num_ret, double tol, int32_t cols, int32_t rows, int32_t *sel_out,
                              int32_t *n_sel_out);
+/* test: the motion-distortion solve as the engine launches it.  B problems in the engine's layout: T_wj0 / T_wj_init (B x 9), p_w /
+ * p_jt (B x nstride x 2), count[b] live points (clamped to nmax by the kernels; fewer than 2: info -1, nfev 0, a zero solution), nmax
+ * <= nstride the host-side bound that picks the kernels.  use_big != 0: with the list through which the one-wavefront kernel leaves
+ * its large problems to the workgroup kernel (two slots, zeroed here).  The solve is launched `repeat` (1..8) times in a row on the
+ * context's stream, the list's slot alternating as in roam_engine_step.  out6 (repeat x B x 6), nfev and info (repeat x B) are
+ * prefilled with 0xff bytes on the device.  big_out (optional, 2 x (1 + B)): the list's two slots [n, ids...] after the last solve
+ * (zeros without the list). */
+int32_t roam_debug_mds_solve_batch(roam_ctx *ctx, const double *T_wj0, const double *p_w, const double *p_jt, const int32_t *count,
+                                   int32_t B, int32_t nstride, int32_t nmax, const double *T_wj_init, const double *sigma5,
+                                   double period, int32_t use_big, int32_t repeat, double *out6, int32_t *nfev, int32_t *info,
+                                   int32_t *big_out);
+/* test: More's lmpar alone, as each of the two solve kernels carries it.  n = 6; R (6 x 6 row-major, upper triangle read), ipvt (6),
+ * qtb (6), diag = 1, trust radius delta > 0, incoming par_in >= 0.  form 0: the workgroup kernel's copy on one thread -> par_out[1],
+ * x_out[6], sdiag_out[6].  form 1: the one-wavefront kernel's copy, every lane computing alike; lanes 0 and 63 both store ->
+ * par_out[2], x_out[12], sdiag_out[12].  sdiag is 0 where lmpar accepts the Gauss-Newton step (par = 0). */
+int32_t roam_debug_lm_lmpar(roam_ctx *ctx, int32_t n, const double *R, const int32_t *ipvt, const double *qtb, double delta,
+                            double par_in, int32_t form, double *par_out, double *x_out, double *sdiag_out);
 #define ROAM_TIME_FFT_FIVE      0   /* the five 2-D transforms of one phase correlation (two real forward, one inverse), transposes included */
 #define ROAM_TIME_DFT_FIVE      1   /* the same five as direct DFTs, a baseline only (rows * cols <= 131072) */
 #define ROAM_TIME_FFT_ROWS      2   /* one row pass: `rows` transforms of length cols, in place */

@@ -185,6 +185,9 @@ _SIGS = {
     "roam_time_fft2": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
     "roam_debug_ssc_batch": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                          _vp, _vp]),
+    "roam_debug_mds_solve_batch": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_double, C.c_int32,
+                                               C.c_int32, _vp, _vp, _vp, _vp]),
+    "roam_debug_lm_lmpar": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int32, _vp, _vp, _vp]),
     "roam_prune_blobs": (C.c_int32, [_vp, C.c_int32, C.c_double, _vp]),
     "roam_argsort_np122": (C.c_int32, [_vp, C.c_int32, _vp]),
     "roam_comm_available": (C.c_int32, []),
@@ -980,6 +983,41 @@ class Context:
         self.check(self.lib.roam_debug_ssc_batch(self.h, _ptr(kp), _ptr(count), P, kp_cap, P if n_active is None else int(n_active), int(first),
                                                  int(num_ret), float(tol), int(cols), int(rows), _ptr(sel), _ptr(n_sel)))
         return sel, n_sel
+
+    def debug_mds_solve_batch(self, T_wj0, p_w, p_jt, count, nmax, T_init, sigma5, period=0.25, big=False, repeat=1, want_list=False):
+        """test entry: the motion-distortion solve as the engine launches it (roam_debug_mds_solve_batch).  T_wj0, T_init (B, 3, 3),
+        p_w, p_jt (B, nstride, 2), count (B,), nmax <= nstride; big: with the list that hands the large problems to the workgroup
+        kernel; repeat consecutive solves -> (out6 (repeat, B, 6), nfev (repeat, B), info (repeat, B)); want_list: and the list's two
+        slots (2, 1 + B) [n, ids ...] as the last solve left them"""
+        T0 = np.ascontiguousarray(T_wj0, np.float64)
+        Ti = np.ascontiguousarray(T_init, np.float64)
+        pw = np.ascontiguousarray(p_w, np.float64)
+        pj = np.ascontiguousarray(p_jt, np.float64)
+        cnt = np.ascontiguousarray(count, np.int32)
+        sg = np.ascontiguousarray(sigma5, np.float64)
+        B, nstride, two = pw.shape
+        assert two == 2 and pj.shape == pw.shape and T0.shape == Ti.shape == (B, 3, 3) and cnt.shape == (B,) and sg.shape == (5,)
+        out = np.zeros((repeat, B, 6))
+        nfev = np.zeros((repeat, B), np.int32)
+        info = np.zeros((repeat, B), np.int32)
+        lists = np.zeros((2, 1 + B), np.int32) if want_list else None
+        self.check(self.lib.roam_debug_mds_solve_batch(self.h, _ptr(T0), _ptr(pw), _ptr(pj), _ptr(cnt), B, nstride, int(nmax), _ptr(Ti),
+                                                       _ptr(sg), float(period), 1 if big else 0, int(repeat), _ptr(out), _ptr(nfev),
+                                                       _ptr(info), _ptr(lists)))
+        return (out, nfev, info, lists) if want_list else (out, nfev, info)
+
+    def debug_lm_lmpar(self, R, ipvt, qtb, delta, par_in, form):
+        """test entry: lmpar alone (roam_debug_lm_lmpar), diag = 1.  form 0: the workgroup kernel's copy -> (par (1,), x (1, 6), sdiag
+        (1, 6)); form 1: the one-wavefront kernel's, as stored by lanes 0 and 63 -> (par (2,), x (2, 6), sdiag (2, 6))"""
+        R = np.ascontiguousarray(R, np.float64)
+        ip = np.ascontiguousarray(ipvt, np.int32)
+        q = np.ascontiguousarray(qtb, np.float64)
+        assert R.shape == (6, 6) and ip.shape == (6,) and q.shape == (6,)
+        k = 2 if form else 1
+        par, x, sd = np.zeros(k), np.zeros((k, 6)), np.zeros((k, 6))
+        self.check(self.lib.roam_debug_lm_lmpar(self.h, 6, _ptr(R), _ptr(ip), _ptr(q), float(delta), float(par_in), int(form), _ptr(par),
+                                                _ptr(x), _ptr(sd)))
+        return par, x, sd
 
     def time_fft2(self, rows, cols, what, reps=20):
         """milliseconds per repetition of `what` (TIME_*) at rows x cols, by HIP events after two warm runs"""

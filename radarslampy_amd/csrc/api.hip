@@ -521,6 +521,79 @@ extern "C" int32_t roam_mds_solve(roam_ctx *ctx, const double *T_wj0, const doub
     return ROAM_OK;
 }
 
+// test entry: launch_mds_solve on B problems laid out as the engine lays them out (problem b: nstride points at p_w / p_jt + b * 2 *
+// nstride, count[b] of them live, nmax the host-side bound), `repeat` times in a row on the context's stream with big_slot alternating
+// as the engine's step does.  Launch r writes out6 / nfev / info at r * B; all three are prefilled with 0xff bytes on the device.
+// big_out (optional): the two list slots as the last solve left them.
+extern "C" int32_t roam_debug_mds_solve_batch(roam_ctx *ctx, const double *T_wj0, const double *p_w, const double *p_jt, const int32_t *count,
+                                              int32_t B, int32_t nstride, int32_t nmax, const double *T_wj_init, const double *sigma5,
+                                              double period, int32_t use_big, int32_t repeat, double *out6, int32_t *nfev, int32_t *info,
+                                              int32_t *big_out)
+{
+    ENTER();
+    ARG_CHECK(ctx, T_wj0 && p_w && p_jt && count && T_wj_init && sigma5 && out6 && nfev && info && period > 0);
+    ARG_CHECK(ctx, B >= 1 && B <= 65535 && nmax >= 1 && nmax <= nstride && nmax <= 8 * ROAM_MAX_FEATURES && (int64_t)B * nstride <= (1 << 22) &&
+                       repeat >= 1 && repeat <= 8);
+    const size_t pts = (size_t)B * nstride * 2, mmax = 2 * (size_t)nmax + 3, nout = (size_t)repeat * B;
+    SCRATCH(dT, double, S_IN0, sizeof(double) * 18 * (size_t)B);
+    SCRATCH(dpw, double, S_IN1, sizeof(double) * pts);
+    SCRATCH(dpj, double, S_IN2, sizeof(double) * pts);
+    SCRATCH(dcnt, int32_t, S_IN3, sizeof(int32_t) * (size_t)B);
+    SCRATCH(dwork, double, S_TMP0, sizeof(double) * (size_t)B * (mmax * 9 + nmax));
+    SCRATCH(dbig, int32_t, S_TMP1, sizeof(int32_t) * 2 * (1 + (size_t)B));
+    SCRATCH(dout, double, S_OUT0, sizeof(double) * 6 * nout);
+    SCRATCH(dint, int32_t, S_OUT2, sizeof(int32_t) * 2 * nout);
+    H2D(dT, T_wj0, sizeof(double) * 9 * (size_t)B);
+    H2D(dT + 9 * (size_t)B, T_wj_init, sizeof(double) * 9 * (size_t)B);
+    H2D(dpw, p_w, sizeof(double) * pts);
+    H2D(dpj, p_jt, sizeof(double) * pts);
+    H2D(dcnt, count, sizeof(int32_t) * (size_t)B);
+    HIP_TRY(ctx, hipMemsetAsync(dbig, 0, sizeof(int32_t) * 2 * (1 + (size_t)B), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(dout, 0xff, sizeof(double) * 6 * nout, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(dint, 0xff, sizeof(int32_t) * 2 * nout, ctx->stream));
+    MdsProblemDesc P;
+    P.T_wj0 = dT; P.T_init = dT + 9 * (size_t)B; P.p_w = dpw; P.p_jt = dpj; P.count = dcnt;
+    P.N = nmax; P.nstride = nstride; P.nmax = nmax; P.B = B; P.period = period;
+    for (int i = 0; i < 5; i++) P.sigma5[i] = sigma5[i];
+    int slot = 0;
+    for (int r = 0; r < repeat; r++) {
+        if (use_big) { P.big = dbig; P.big_slot = slot; slot ^= 1; }
+        HIP_TRY(ctx, launch_mds_solve(ctx->stream, P, dwork, dout + 6 * (size_t)r * B, dint + (size_t)r * B, dint + nout + (size_t)r * B, nullptr, nullptr));
+    }
+    D2H(out6, dout, sizeof(double) * 6 * nout);
+    D2H(nfev, dint, sizeof(int32_t) * nout);
+    D2H(info, dint + nout, sizeof(int32_t) * nout);
+    if (big_out) D2H(big_out, dbig, sizeof(int32_t) * 2 * (1 + (size_t)B));
+    SYNC();
+    return ROAM_OK;
+}
+
+// test entry: lmpar alone (lm_debug_lmpar_kernel, kabsch_mds.hip).  form 0 fills one set of outputs, form 1 two (lane 0, lane 63)
+extern "C" int32_t roam_debug_lm_lmpar(roam_ctx *ctx, int32_t n, const double *R, const int32_t *ipvt, const double *qtb, double delta,
+                                       double par_in, int32_t form, double *par_out, double *x_out, double *sdiag_out)
+{
+    ENTER();
+    ARG_CHECK(ctx, n == 6 && R && ipvt && qtb && par_out && x_out && sdiag_out && (form == 0 || form == 1) && delta > 0 && par_in >= 0);
+    for (int j = 0; j < 6; j++) ARG_CHECK(ctx, ipvt[j] >= 0 && ipvt[j] < 6);
+    SCRATCH(dR, double, S_IN0, sizeof(double) * 42);
+    SCRATCH(dip, int32_t, S_IN1, sizeof(int32_t) * 6);
+    SCRATCH(dout, double, S_OUT0, sizeof(double) * 26);
+    H2D(dR, R, sizeof(double) * 36);
+    H2D(dR + 36, qtb, sizeof(double) * 6);
+    H2D(dip, ipvt, sizeof(int32_t) * 6);
+    HIP_TRY(ctx, hipMemsetAsync(dout, 0xff, sizeof(double) * 26, ctx->stream));
+    HIP_TRY(ctx, launch_lm_debug_lmpar(ctx->stream, dR, dip, dR + 36, delta, par_in, form, dout));
+    double o[26];
+    D2H(o, dout, sizeof(o));
+    SYNC();
+    for (int s = 0; s <= form; s++) {
+        par_out[s] = o[13 * s];
+        memcpy(x_out + 6 * s, o + 13 * s + 1, sizeof(double) * 6);
+        memcpy(sdiag_out + 6 * s, o + 13 * s + 7, sizeof(double) * 6);
+    }
+    return ROAM_OK;
+}
+
 extern "C" int32_t roam_mds_undistort(roam_ctx *ctx, const double *v3, const double *pts, int32_t N,
                                       double period, double *out_xy, double *dT_out)
 {

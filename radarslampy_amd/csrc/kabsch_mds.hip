@@ -178,128 +178,10 @@ __device__ void mds_jac(const LmShared *S, const double *x, const double *xp, co
     }
 }
 
-// serial 6x6 pieces (thread 0 only), operating on the first 6 rows of `a`
-__device__ void qrsolv6(int m, double *a, const int *ipvt, const double *diag, const double *qtb,
-                        double *x, double *sdiag, double *wa)
-{
-    const int n = 6;
-    for (int j = 0; j < n; j++) {
-        for (int i = j; i < n; i++) A_(i, j) = A_(j, i);
-        x[j] = A_(j, j); wa[j] = qtb[j];
-    }
-    for (int j = 0; j < n; j++) {
-        const int l = ipvt[j];
-        if (diag[l] != 0) {
-            for (int k = j; k < n; k++) sdiag[k] = 0;
-            sdiag[j] = diag[l];
-            double qtbpj = 0;
-            for (int k = j; k < n; k++) {
-                if (sdiag[k] == 0) continue;
-                double c, s;
-                if (fabs(A_(k, k)) < fabs(sdiag[k])) {
-                    double cot = A_(k, k) / sdiag[k];
-                    s = 0.5 / sqrt(0.25 + 0.25 * (cot * cot)); c = s * cot;
-                } else {
-                    double t = sdiag[k] / A_(k, k);
-                    c = 0.5 / sqrt(0.25 + 0.25 * (t * t)); s = c * t;
-                }
-                A_(k, k) = c * A_(k, k) + s * sdiag[k];
-                double temp = c * wa[k] + s * qtbpj;
-                qtbpj = -s * wa[k] + c * qtbpj;
-                wa[k] = temp;
-                for (int i = k + 1; i < n; i++) {
-                    temp = c * A_(i, k) + s * sdiag[i];
-                    sdiag[i] = -s * A_(i, k) + c * sdiag[i];
-                    A_(i, k) = temp;
-                }
-            }
-        }
-        sdiag[j] = A_(j, j);
-        A_(j, j) = x[j];
-    }
-    int nsing = n;
-    for (int j = 0; j < n; j++) {
-        if (sdiag[j] == 0 && nsing == n) nsing = j;
-        if (nsing < n) wa[j] = 0;
-    }
-    for (int k = 0; k < nsing; k++) {
-        const int j = nsing - 1 - k;
-        double sum = 0;
-        for (int i = j + 1; i < nsing; i++) sum += A_(i, j) * wa[i];
-        wa[j] = (wa[j] - sum) / sdiag[j];
-    }
-    for (int j = 0; j < n; j++) x[ipvt[j]] = wa[j];
-}
-
-__device__ void lmpar6(int m, double *a, const int *ipvt, const double *diag, const double *qtb,
-                       double delta, double *par, double *x, double *sdiag, double *wa1, double *wa2)
-{
-    const int n = 6;
-    int nsing = n;
-    for (int j = 0; j < n; j++) {
-        wa1[j] = qtb[j];
-        if (A_(j, j) == 0 && nsing == n) nsing = j;
-        if (nsing < n) wa1[j] = 0;
-    }
-    for (int k = 0; k < nsing; k++) {
-        const int j = nsing - 1 - k;
-        wa1[j] /= A_(j, j);
-        const double temp = wa1[j];
-        for (int i = 0; i < j; i++) wa1[i] -= A_(i, j) * temp;
-    }
-    for (int j = 0; j < n; j++) x[ipvt[j]] = wa1[j];
-    int iter = 0;
-    for (int j = 0; j < n; j++) wa2[j] = diag[j] * x[j];
-    double dxnorm = enorm6(wa2);
-    double fp = dxnorm - delta;
-    if (fp <= 0.1 * delta) { *par = 0; return; }
-    double parl = 0;
-    if (nsing >= n) {
-        for (int j = 0; j < n; j++) { const int l = ipvt[j]; wa1[j] = diag[l] * (wa2[l] / dxnorm); }
-        for (int j = 0; j < n; j++) {
-            double sum = 0;
-            for (int i = 0; i < j; i++) sum += A_(i, j) * wa1[i];
-            wa1[j] = (wa1[j] - sum) / A_(j, j);
-        }
-        const double temp = enorm6(wa1);
-        parl = ((fp / delta) / temp) / temp;
-    }
-    for (int j = 0; j < n; j++) {
-        double sum = 0;
-        for (int i = 0; i <= j; i++) sum += A_(i, j) * qtb[i];
-        wa1[j] = sum / diag[ipvt[j]];
-    }
-    const double gnorm = enorm6(wa1);
-    double paru = gnorm / delta;
-    if (paru == 0) paru = DWARF / (delta < 0.1 ? delta : 0.1);
-    if (*par < parl) *par = parl;
-    if (*par > paru) *par = paru;
-    if (*par == 0) *par = gnorm / dxnorm;
-    for (;;) {
-        iter++;
-        if (*par == 0) { const double t = 0.001 * paru; *par = DWARF > t ? DWARF : t; }
-        double temp = sqrt(*par);
-        for (int j = 0; j < n; j++) wa1[j] = temp * diag[j];
-        qrsolv6(m, a, ipvt, wa1, qtb, x, sdiag, wa2);
-        for (int j = 0; j < n; j++) wa2[j] = diag[j] * x[j];
-        dxnorm = enorm6(wa2);
-        temp = fp;
-        fp = dxnorm - delta;
-        if (fabs(fp) <= 0.1 * delta || (parl == 0 && fp <= temp && temp < 0) || iter == 10) break;
-        for (int j = 0; j < n; j++) { const int l = ipvt[j]; wa1[j] = diag[l] * (wa2[l] / dxnorm); }
-        for (int j = 0; j < n; j++) {
-            wa1[j] /= sdiag[j];
-            const double t = wa1[j];
-            for (int i = j + 1; i < n; i++) wa1[i] -= A_(i, j) * t;
-        }
-        temp = enorm6(wa1);
-        const double parc = ((fp / delta) / temp) / temp;
-        if (fp > 0 && *par > parl) parl = *par;
-        if (fp < 0 && *par < paru) paru = *par;
-        const double np_ = *par + parc;
-        *par = parl > np_ ? parl : np_;
-    }
-}
+// serial 6x6 pieces (thread 0 only), operating on the first 6 rows of `a`: qrsolv6, lmpar6
+#define LM6(f) f
+#include "lm_serial6.inc"
+#undef LM6
 
 #include "lm_wave.inc"
 
@@ -643,6 +525,59 @@ hipError_t launch_mds_solve(hipStream_t st, const MdsProblemDesc &p, double *wor
     const int threads = p.nmax <= 448 ? 128 : LM_TMAX;      // (above 254 points here)
     const int grid = p.big ? std::min(p.B, 512) : p.B;      // (a few workgroups walk the wave kernel's list when there is one)
     hipLaunchKernelGGL(mds_lm_kernel, dim3(grid), dim3(threads), lds, st, p, work, out6, nfev, info, x0_out, r0_out, (int)lds, wave_rows);
+    return hipGetLastError();
+}
+
+#define LM6(f) f##_alone
+#include "lm_serial6.inc"
+#undef LM6
+
+// test entry (roam_debug_lm_lmpar): lmpar alone on a 6 x 6 upper triangle R (row-major), diag = 1.  out = 13 doubles per stored set
+// [par, x(6), sdiag(6)]; sdiag stays 0 where lmpar returns before its loop (the Gauss-Newton step accepted).
+//   form 0: the workgroup form's lmpar6 (its second compilation, lm_serial6.inc) on thread 0, over a 6-row column-major matrix - one set
+//   form 1: lmw_lmpar of the wave form, computed by every lane of the wavefront alike - lane 0 stores set 0, lane 63 set 1
+__global__ __launch_bounds__(64) void lm_debug_lmpar_kernel(const double *__restrict__ R, const int32_t *__restrict__ ipvt_in,
+                                                            const double *__restrict__ qtb_in, double delta, double par_in, int form,
+                                                            double *__restrict__ out)
+{
+    const int t = threadIdx.x;
+    if (form == 0) {
+        if (t != 0) return;
+        double a[36], diag[6], qtb[6], x[6], sd[6], wa1[6], wa2[6];
+        int ipvt[6];
+        const int m = 6;
+        for (int j = 0; j < 6; j++) {
+            for (int i = 0; i < 6; i++) A_(i, j) = i <= j ? R[i * 6 + j] : 0.0;
+            diag[j] = 1.0; qtb[j] = qtb_in[j]; ipvt[j] = ipvt_in[j]; x[j] = 0; sd[j] = 0;
+        }
+        double par = par_in;
+        lmpar6_alone(m, a, ipvt, diag, qtb, delta, &par, x, sd, wa1, wa2);
+        out[0] = par;
+        for (int j = 0; j < 6; j++) { out[1 + j] = x[j]; out[7 + j] = sd[j]; }
+        return;
+    }
+    double Ru[6][6], Tl[6][6], qtb[6], x[6], sd[6];
+    int ipvt[6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) { Ru[i][j] = i <= j ? R[i * 6 + j] : 0.0; Tl[i][j] = 0; }
+        qtb[j] = qtb_in[j]; ipvt[j] = ipvt_in[j]; x[j] = 0; sd[j] = 0;
+    }
+    double par = par_in;
+    lmw_lmpar(Ru, Tl, ipvt, qtb, delta, par, x, sd);
+    if (t == 0 || t == 63) {
+        double *o = out + (t == 0 ? 0 : 13);
+        o[0] = par;
+#pragma unroll
+        for (int j = 0; j < 6; j++) { o[1 + j] = x[j]; o[7 + j] = sd[j]; }
+    }
+}
+
+hipError_t launch_lm_debug_lmpar(hipStream_t st, const double *R, const int32_t *ipvt, const double *qtb, double delta, double par_in,
+                                 int form, double *out)
+{
+    hipLaunchKernelGGL(lm_debug_lmpar_kernel, dim3(1), dim3(64), 0, st, R, ipvt, qtb, delta, par_in, form, out);
     return hipGetLastError();
 }
 

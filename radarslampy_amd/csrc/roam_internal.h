@@ -180,6 +180,10 @@ hipError_t launch_mds_solve(hipStream_t st, const MdsProblemDesc &p, double *wor
                             int32_t *nfev, int32_t *info, double *x0_out, double *r0_out);
 hipError_t launch_mds_undistort(hipStream_t st, const double *v3, const double *pts, int N,
                                 double period, double *out_xy, double *dT);
+// test entry: lmpar alone (lm_debug_lmpar_kernel).  R: 36 doubles row-major, ipvt / qtb: 6; out: 26 doubles = two sets of
+// [par, x(6), sdiag(6)] (form 0 writes the first only)
+hipError_t launch_lm_debug_lmpar(hipStream_t st, const double *R, const int32_t *ipvt, const double *qtb, double delta, double par_in,
+                                 int form, double *out);
 
 hipError_t launch_ssc(hipStream_t st, const double *kp, int B, int num_ret, double tol, int cols,
                       int rows, int32_t *work, int32_t *sel, int32_t *n_sel);
