@@ -238,6 +238,9 @@ int32_t roam_log_maxima(roam_ctx *ctx, const void *img, int32_t img_bytes_per_px
  * roam_argsort_np122 = np.argsort of the pinned NumPy 1.22.3 (unstable introsort) that adaptiveNMS applies to the
  *                      two-valued sigmas (getFeatures.py:69); order_out (n) i32. */
 int32_t roam_prune_blobs(const double *blobs, int32_t n, double overlap, uint8_t *keep_out);
+/* test: the candidate pairs behind roam_prune_blobs (its 16-bit form: n <= 32767 blobs, at most 32767 pairs), i << 16 | j with i < j, in
+ * the order scipy's cKDTree.query_pairs emits them.  ROAM_E_CAPACITY: more pairs than that, or than cap. */
+int32_t roam_debug_prune_pairs(const double *blobs, int32_t n, uint32_t *pairs_out, int32_t cap, int32_t *n_pairs);
 int32_t roam_argsort_np122(const double *keys, int32_t n, int32_t *order_out);
 
 /* ---- f4: FMT.getRotationUsingFMT (FMT.py:36-90; called first by Tracker.track, Tracker.py:62-63) ---------------------
@@ -617,6 +620,20 @@ int32_t roam_engine_time_kernel(roam_ctx *ctx, const char *name, int32_t reps, f
  * the integral image of slot s_slot as that form computed it.  Needs retrack_on_device and one step; n_slots <= retrack_slots, lanes. */
 int32_t roam_engine_debug_detect(roam_ctx *ctx, int32_t fused, int32_t n_slots, int32_t cap_per_slot, uint32_t *rc_out, double *val_out,
                                  int32_t *n_out, int32_t s_slot, double *S_out);
+/* test: the detector's blob bookkeeping alone (candidate order, skimage's _prune_blobs in its pair order, the sigma argsort of NumPy
+ * 1.22, SSC) on the caller's candidate lists, through the engine's own scratch and the one launch call a step makes, so that P picks the
+ * launch form (one kernel below 256 problems, three classes of kernels from 256, longest list first from 512).  P <= lanes problems;
+ * cand_rc / cand_val (host): P x rows_given, rows_given <= 2048; rc = row << 16 | col << 2 | layer with row, col < the Cartesian size W,
+ * layer 1 | 2 and distinct keys, in any order; cand_n[p] = the count a detection would have left, > rows_given only beyond 2048 (with
+ * rows_given = 2048: RT_F_CAND_OVERFLOW).  Bad arguments are refused (ROAM_E_ARG) before any device call.  Out, per problem: kp_n, kp
+ * (2048 x 3 float64 [row, col, sigma] in adaptiveNMS priority order), the flags (1 candidate, 2 tree / task, 4 pair overflow), sel_n
+ * and sel (2048 indices into kp); what a kernel left alone holds 0xff bytes (kp: NaN) or 0x7f bytes (the int32 arrays).  Needs
+ * retrack_on_device; leaves the scratch as a detection expects it.  pairs_out (optional, P x 32768): the candidate pairs i << 16 | j
+ * (i < j: indices in response order) in the order query_pairs emits them, from entry 0 on; the caller knows their number (at most
+ * 32767 are kept); not meaningful after a tree / task overflow. */
+int32_t roam_engine_debug_blobs(roam_ctx *ctx, int32_t P, int32_t rows_given, const uint32_t *cand_rc, const double *cand_val,
+                                const int32_t *cand_n, int32_t *kp_n_out, double *kp_out, int32_t *flags_out, int32_t *sel_n_out,
+                                int32_t *sel_out, uint32_t *pairs_out);
 
 /* ---- multi-GPU.  One process per GPU, sequences sharded by rank, no data-path collective.  The only exchange
  * of the path is handing a keyframe to a global map (reference Mapping.Map.addKeyframe, Mapping.py:118-147; BASELINE

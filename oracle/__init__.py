@@ -429,6 +429,8 @@ def ckdtree_pairs(pts, r):
     idx = np.empty(max(n, 1), np.int64)
     lib().oracle_ckdtree_pairs.restype = C.c_int64
     m = lib().oracle_ckdtree_pairs(_p(pts, C.c_double), C.c_int64(n), C.c_double(float(r)), C.byref(out), _p(idx, C.c_int64))
+    if m < 0:
+        raise RuntimeError("oracle_ckdtree_pairs: the dual-tree traversal is deeper than the tracker's stack")
     pairs = np.ctypeslib.as_array(out, shape=(m, 2)).copy() if m else np.empty((0, 2), np.int64)
     lib().oracle_free(out)
     return pairs, idx[:n]
@@ -447,7 +449,8 @@ def prune_blobs(blobs, overlap=0.5):
     """skimage.feature.blob._prune_blobs in scikit-image's own pair order (cKDTree.query_pairs -> Python set)"""
     bl = np.ascontiguousarray(blobs, np.float64).copy()
     lib().oracle_prune_blobs.restype = C.c_int64
-    lib().oracle_prune_blobs(_p(bl, C.c_double), C.c_int64(len(bl)), C.c_double(overlap))
+    if lib().oracle_prune_blobs(_p(bl, C.c_double), C.c_int64(len(bl)), C.c_double(overlap)) < 0:
+        raise RuntimeError("oracle_prune_blobs: the dual-tree traversal is deeper than the tracker's stack")
     return bl[bl[:, 2] > 0]
 
 

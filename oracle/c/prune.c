@@ -126,6 +126,18 @@ static int knew(KTree *t)
     return t->n++;
 }
 
+/* scipy's partition pass (std::partition with `key < split`): afterwards the keys below the split fill [start, p) */
+static int64_t ksplit(KTree *t, int64_t start, int64_t end, int d, double split)
+{
+    int64_t p = start, q = end - 1;
+    while (p <= q) {
+        if (t->data[t->idx[p] * 2 + d] < split) p++;
+        else if (t->data[t->idx[q] * 2 + d] >= split) q--;
+        else { int64_t s = t->idx[p]; t->idx[p] = t->idx[q]; t->idx[q] = s; p++; q--; }
+    }
+    return p;
+}
+
 static int kbuild(KTree *t, int64_t start, int64_t end)
 {
     const int me = knew(t);
@@ -146,22 +158,19 @@ static int kbuild(KTree *t, int64_t start, int64_t end)
             int64_t i = (end - start) / 2;
             nth_element_(t->idx + start, t->idx + start + i, t->idx + end, &c);
             double split = t->data[t->idx[start + i] * 2 + d];
-            int64_t p = start, q = end - 1;
-            while (p <= q) {
-                if (t->data[t->idx[p] * 2 + d] < split) p++;
-                else if (t->data[t->idx[q] * 2 + d] >= split) q--;
-                else { int64_t s = t->idx[p]; t->idx[p] = t->idx[q]; t->idx[q] = s; p++; q--; }
-            }
-            if (p == start) {                                           /* slide midpoint: no point below the split */
-                int64_t j = start; split = t->data[t->idx[j] * 2 + d];
-                for (int64_t k = start + 1; k < end; k++) if (t->data[t->idx[k] * 2 + d] < split) { j = k; split = t->data[t->idx[j] * 2 + d]; }
-                int64_t s = t->idx[start]; t->idx[start] = t->idx[j]; t->idx[j] = s;
-                p = start + 1;
-            } else if (p == end) {
-                int64_t j = end - 1; split = t->data[t->idx[j] * 2 + d];
-                for (int64_t k = start; k < end - 1; k++) if (t->data[t->idx[k] * 2 + d] > split) { j = k; split = t->data[t->idx[j] * 2 + d]; }
-                int64_t s = t->idx[end - 1]; t->idx[end - 1] = t->idx[j]; t->idx[j] = s;
-                p = end - 1;
+            int64_t p = ksplit(t, start, end, d, split);
+            if (p == start) {
+                /* no point below the median key: scipy (>= 1.6; checked against 1.15.3) does not peel one point off - it moves
+                 * the split to nextafter(smallest key, +inf) and partitions again, so EVERY point at the minimum goes to `less` */
+                double m = t->data[t->idx[start] * 2 + d];
+                for (int64_t k = start + 1; k < end; k++) { double v = t->data[t->idx[k] * 2 + d]; m = v < m ? v : m; }
+                split = nextafter(m, HUGE_VAL);
+                p = ksplit(t, start, end, d, split);
+            } else if (p == end) {                                      /* (never with a median split: the median itself is >= split) */
+                double m = t->data[t->idx[start] * 2 + d];
+                for (int64_t k = start + 1; k < end; k++) { double v = t->data[t->idx[k] * 2 + d]; m = v > m ? v : m; }
+                split = m;
+                p = ksplit(t, start, end, d, split);
             }
             nd.split_dim = d; nd.split = split;
             t->nodes[me] = nd;
@@ -176,7 +185,9 @@ static int kbuild(KTree *t, int64_t start, int64_t end)
 
 /* RectRectDistanceTracker<MinkowskiDistP2>: squared min / max distance between the two current boxes */
 typedef struct { int which, dim; double mind, maxd, lo, hi; } TItem;
-typedef struct { double r1[2][2], r2[2][2]; double mind, maxd, ub, limit; TItem st[256]; int sp; } Tracker;
+#define TRACKER_DEPTH 256
+/* over: pushes refused because st is full (each is matched by one pop); err: that has happened - the traversal is abandoned */
+typedef struct { double r1[2][2], r2[2][2]; double mind, maxd, ub, limit; TItem st[TRACKER_DEPTH]; int sp, over, err; } Tracker;
 
 static void tdim(const Tracker *t, int k, double *mn, double *mx)
 {
@@ -195,6 +206,7 @@ static void tfull(Tracker *t)
 static void tpush(Tracker *t, int which, int less, int dim, double split)
 {
     double (*rect)[2] = which == 1 ? t->r1 : t->r2;
+    if (t->sp >= TRACKER_DEPTH) { t->over++; t->err = 1; return; }
     TItem *it = &t->st[t->sp++];
     it->which = which; it->dim = dim; it->mind = t->mind; it->maxd = t->maxd; it->lo = rect[0][dim]; it->hi = rect[1][dim];
     double min1, max1, min2, max2;
@@ -207,6 +219,7 @@ static void tpush(Tracker *t, int which, int less, int dim, double split)
 }
 static void tpop(Tracker *t)
 {
+    if (t->over) { t->over--; return; }
     TItem *it = &t->st[--t->sp];
     double (*rect)[2] = it->which == 1 ? t->r1 : t->r2;
     t->mind = it->mind; t->maxd = it->maxd; rect[0][it->dim] = it->lo; rect[1][it->dim] = it->hi;
@@ -236,6 +249,7 @@ static void knocheck(const KTree *t, Pairs *o, int a, int b)
 static void kcheck(const KTree *t, Tracker *tr, Pairs *o, int a, int b)
 {
     const KNode *n1 = &t->nodes[a], *n2 = &t->nodes[b];
+    if (tr->err) return;
     if (tr->mind > tr->ub) return;
     if (tr->maxd < tr->ub) { knocheck(t, o, a, b); return; }
     if (n1->split_dim == -1) {
@@ -269,7 +283,8 @@ static void kcheck(const KTree *t, Tracker *tr, Pairs *o, int a, int b)
 }
 
 /* pts (n,2) f64 -> pairs in the order scipy.spatial.cKDTree(pts).query_pairs(r) emits them.
- * *pairs_out is malloc'ed ((count,2) int64); idx_out (n, optional) receives cKDTree.indices. */
+ * *pairs_out is malloc'ed ((count,2) int64); idx_out (n, optional) receives cKDTree.indices.
+ * returns the pair count, or -1 (nothing allocated) when the traversal is deeper than the tracker's TRACKER_DEPTH pushes. */
 int64_t oracle_ckdtree_pairs(const double *pts, int64_t n, double r, int64_t **pairs_out, int64_t *idx_out)
 {
     *pairs_out = NULL;
@@ -292,6 +307,7 @@ int64_t oracle_ckdtree_pairs(const double *pts, int64_t n, double r, int64_t **p
     kcheck(&t, &tr, &o, 0, 0);
     if (idx_out) memcpy(idx_out, t.idx, sizeof(int64_t) * (size_t)n);
     free(t.idx); free(t.nodes);
+    if (tr.err) { free(o.p); return -1; }
     *pairs_out = o.p;
     return o.n;
 }
@@ -392,7 +408,8 @@ static double blob_overlap(const double *b1, const double *b2)
 }
 
 /* blobs (n,3) f64 rows [row, col, sigma] in peak_local_max order (highest response first); sigmas of the
- * pruned blobs are zeroed IN PLACE exactly as _prune_blobs does.  returns the number of survivors. */
+ * pruned blobs are zeroed IN PLACE exactly as _prune_blobs does.  returns the number of survivors, or -1 (blobs untouched) when
+ * oracle_ckdtree_pairs gave up. */
 int64_t oracle_prune_blobs(double *blobs, int64_t n, double overlap)
 {
     if (n <= 0) return 0;
@@ -403,6 +420,7 @@ int64_t oracle_prune_blobs(double *blobs, int64_t n, double overlap)
     for (int64_t i = 0; i < n; i++) { pts[2 * i] = blobs[3 * i]; pts[2 * i + 1] = blobs[3 * i + 1]; }
     int64_t *pairs = NULL;
     const int64_t np_ = oracle_ckdtree_pairs(pts, n, distance, &pairs, NULL);
+    if (np_ < 0) { free(pts); return -1; }
     int64_t *order = (int64_t *)malloc(sizeof(int64_t) * (size_t)(np_ > 0 ? np_ : 1));
     const int64_t m = oracle_pyset_order(pairs, np_, order);
     for (int64_t k = 0; k < m; k++) {

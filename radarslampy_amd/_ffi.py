@@ -175,6 +175,7 @@ _SIGS = {
     "roam_engine_set_stage_events": (C.c_int32, [_vp, C.c_int32]),
     "roam_engine_time_kernel": (C.c_int32, [_vp, C.c_char_p, C.c_int32, _P(C.c_float), _P(C.c_double)]),
     "roam_engine_debug_detect": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp]),
+    "roam_engine_debug_blobs": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "roam_fmt_rotation": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "roam_phase_correlate_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp]),
     "roam_fmt_rotation_batch_f32": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
@@ -189,6 +190,7 @@ _SIGS = {
                                                C.c_int32, _vp, _vp, _vp, _vp]),
     "roam_debug_lm_lmpar": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int32, _vp, _vp, _vp]),
     "roam_prune_blobs": (C.c_int32, [_vp, C.c_int32, C.c_double, _vp]),
+    "roam_debug_prune_pairs": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, _vp]),
     "roam_argsort_np122": (C.c_int32, [_vp, C.c_int32, _vp]),
     "roam_comm_available": (C.c_int32, []),
     "roam_comm_unique_id": (C.c_int32, [_vp]),

@@ -35,6 +35,10 @@
 
 // NI / TI: index types of nodes and tasks.  int16_t for the device retrack (its LDS layout) and the host path within the limits
 // above; int32_t for the host-only wide instantiation (roam_prune_blobs beyond 32767 points or pairs)
+// split_dim: -1 = leaf, else the dimension, + BP_SLID when no point lay below the median key: scipy then moves the split plane to
+// nextafter(smallest key, +inf) and every point AT the minimum goes to `less`.  split holds the integer key either way; the
+// plane query_pairs' tracker sees is bp_split_plane()
+#define BP_SLID 2
 template <typename NI> struct BpNodeT { int32_t split; NI split_dim, start, end, less, greater; };
 template <typename TI> struct BpTaskT { TI a, b; int32_t mode; };   // leaf a x leaf b; mode 1 = every pair (no distance test)
 typedef BpNodeT<int16_t> BpNode;
@@ -45,6 +49,17 @@ typedef BpTaskT<int16_t> BpTask;
 // an element is either an index into xy (host, oracle-sized arrays) or a packed point {row:16, col:16, index:16} whose key needs no
 // second, dependent memory access (device: the sequential selection / partition passes run out of LDS, latency-bound)
 struct BpPt { uint64_t v; };
+// nextafter(m, +inf) of an integer-valued key m (one bit: 0 -> 4.9e-324, 500 -> 500 + 2^-44)
+BP_HD double bp_next_up(double m)
+{
+    if (m == 0) m = 0;                                      // (-0.0)
+    int64_t b;
+    __builtin_memcpy(&b, &m, 8);
+    b += m >= 0 ? 1 : -1;
+    __builtin_memcpy(&m, &b, 8);
+    return m;
+}
+template <typename NI> BP_HD double bp_split_plane(const BpNodeT<NI> &nd) { return nd.split_dim & BP_SLID ? bp_next_up((double)nd.split) : (double)nd.split; }
 BP_HD int bp_key(BpPt e, const int16_t *, int d) { return (int16_t)(e.v >> (16 * d)); }
 template <typename IDX> BP_HD int bp_key(IDX e, const int16_t *xy, int d) { return xy[2 * (int)e + d]; }
 #define BP_KEY(i) bp_key((i), xy, d)
@@ -122,8 +137,19 @@ BP_HDN void bp_nth_element(IDX *idx, int first, int nth, int last, const int16_t
 }
 
 // ------------------------------------------------------------------------------------------------ cKDTree build
-// xy: n x 2 int16 [row, col]; idx: n (filled 0..n-1 here); returns the node count or -1 on overflow.
-// stack: caller-provided scratch of 3 * 64 ints; node_cap: capacity of nodes (BP_MAX_NODES in LDS on the device).
+// scipy's partition pass (std::partition with key < split): afterwards the keys below the split fill [start, p)
+template <typename IDX>
+BP_HDN int bp_split_pass(const int16_t *xy, IDX *idx, int start, int end, int d, int split)
+{
+    int p = start, q = end - 1;
+    while (p <= q) {
+        if (BP_KEY(idx[p]) < split) p++;
+        else if (BP_KEY(idx[q]) >= split) q--;
+        else { IDX t = idx[p]; idx[p] = idx[q]; idx[q] = t; p++; q--; }
+    }
+    return p;
+}
+
 // one node of the build: bounds, split dimension, median split with scipy's partition passes.  Returns the first index of the
 // "greater" half (the node is split into [start, p) and [p, end)) or -1 for a leaf; nd receives split_dim / split.
 template <typename IDX, typename NI>
@@ -144,27 +170,21 @@ BP_HDN int bp_build_node(const int16_t *xy, IDX *idx, int start, int end, BpNode
     const int i = (end - start) / 2;
     bp_nth_element(idx, start, start + i, end, xy, d);
     int split = BP_KEY(idx[start + i]);
-    int p = start, q = end - 1;
-    while (p <= q) {
-        if (BP_KEY(idx[p]) < split) p++;
-        else if (BP_KEY(idx[q]) >= split) q--;
-        else { IDX t = idx[p]; idx[p] = idx[q]; idx[q] = t; p++; q--; }
-    }
-    if (p == start) {                           // no point below the split: slide to the smallest
-        int j = start; split = BP_KEY(idx[j]);
-        for (int k = start + 1; k < end; k++) if (BP_KEY(idx[k]) < split) { j = k; split = BP_KEY(idx[j]); }
-        IDX t = idx[start]; idx[start] = idx[j]; idx[j] = t;
-        p = start + 1;
-    } else if (p == end) {
-        int j = end - 1; split = BP_KEY(idx[j]);
-        for (int k = start; k < end - 1; k++) if (BP_KEY(idx[k]) > split) { j = k; split = BP_KEY(idx[j]); }
-        IDX t = idx[end - 1]; idx[end - 1] = idx[j]; idx[j] = t;
-        p = end - 1;
+    int p = bp_split_pass(xy, idx, start, end, d, split);
+    if (p == start) {                           // no point below the split: the plane moves just above the smallest key, the points AT it go to less
+        split = d ? mn1 : mn0;
+        p = bp_split_pass(xy, idx, start, end, d, split + 1);
+        d |= BP_SLID;
+    } else if (p == end) {                      // (never after a median split: the median itself is >= split)
+        split = d ? mx1 : mx0;
+        p = bp_split_pass(xy, idx, start, end, d, split);
     }
     nd.split_dim = (NI)d; nd.split = split;
     return p;
 }
 
+// xy: n x 2 int16 [row, col]; idx: n (filled 0..n-1 here); returns the node count or -1 on overflow.
+// stack: caller-provided scratch of 3 * 64 ints; node_cap: capacity of nodes (BP_MAX_NODES in LDS on the device).
 template <typename IDX, typename NI>
 BP_HDN int bp_build(const int16_t *xy, int n, IDX *idx, BpNodeT<NI> *nodes, int node_cap, int *stack)
 {
@@ -259,7 +279,7 @@ BP_HDN int bp_tasks(const int16_t *xy, int n, const BpNodeT<NI> *nodes, double r
         if (op == BP_POP) { bp_tpop(tr); continue; }
         if (op == BP_PUSH) {                                  // a = which | less << 1, b = node whose split plane is applied
             if (tr.sp >= 48) return -1;
-            bp_tpush(tr, a & 1 ? 1 : 2, (a >> 1) & 1, nodes[b].split_dim, (double)nodes[b].split);
+            bp_tpush(tr, a & 1 ? 1 : 2, (a >> 1) & 1, nodes[b].split_dim & 1, bp_split_plane(nodes[b]));
             continue;
         }
         const BpNodeT<NI> &n1 = nodes[a], &n2 = nodes[b];

@@ -59,29 +59,51 @@ static int32_t prune_blobs_wide(const double *blobs, int n, double overlap, cons
     return ROAM_OK;
 }
 
-// the 16-bit form: pair keys i << 16 | j, 16-bit set tables
-static int32_t prune_blobs_narrow(const double *blobs, int n, double overlap, const int16_t *xy, double distance, uint8_t *keep_out)
+// the candidate pairs of the 16-bit form (keys i << 16 | j) in query_pairs' emission order; -> their number or -1 (capacity)
+static int narrow_pairs(const int16_t *xy, int n, double distance, std::vector<uint32_t> &pairs)
 {
     std::vector<int16_t> idx(n);
     const int node_cap = 2 * n + 8;
     std::vector<BpNode> nodes(node_cap);
     int stack[3 * 64];
     const int nn = bp_build(xy, n, idx.data(), nodes.data(), node_cap, stack);
-    if (nn < 0) return ROAM_E_CAPACITY;
+    if (nn < 0) return -1;
     const int task_cap = 64 * nn + 64;
     std::vector<BpTask> tasks(task_cap);
     std::vector<int> st(3 * 1024);
     BpTracker tr;
     const int nt = bp_tasks(xy, n, nodes.data(), distance, tasks.data(), task_cap, st.data(), 1024, tr);
-    if (nt < 0) return ROAM_E_CAPACITY;
-    std::vector<uint32_t> pairs(BP_MAX_PAIRS);
-    const int np = bp_expand(xy, idx.data(), nodes.data(), tasks.data(), nt, tr.ub, pairs.data(), BP_MAX_PAIRS);
+    if (nt < 0) return -1;
+    pairs.resize(BP_MAX_PAIRS);
+    return bp_expand(xy, idx.data(), nodes.data(), tasks.data(), nt, tr.ub, pairs.data(), BP_MAX_PAIRS);
+}
+
+// the 16-bit form: 16-bit set tables
+static int32_t prune_blobs_narrow(const double *blobs, int n, double overlap, const int16_t *xy, double distance, uint8_t *keep_out)
+{
+    std::vector<uint32_t> pairs;
+    const int np = narrow_pairs(xy, n, distance, pairs);
     if (np < 0) return ROAM_E_CAPACITY;
     std::vector<uint16_t> tabA(131072), tabB(131072);
     std::vector<uint16_t> order(np > 0 ? np : 1);
     if (bp_pyset_order(pairs.data(), np, tabA.data(), 131072, tabB.data(), 131072, order.data()) != np) return ROAM_E_CAPACITY;
     prune_pass(blobs, n, overlap, pairs.data(), order.data(), np, 16, keep_out);
     return ROAM_OK;
+}
+
+// blobs -> integer pixel coordinates and _prune_blobs' distance; false: a coordinate is no integer in [0, 32767]
+static bool blob_points(const double *blobs, int n, std::vector<int16_t> &xy, double *distance)
+{
+    xy.resize(2 * (size_t)n);
+    double smax = blobs[2];
+    for (int i = 0; i < n; i++) {
+        const double r = blobs[3 * i], c = blobs[3 * i + 1];
+        if (!(r >= 0 && r <= 32767 && c >= 0 && c <= 32767) || r != floor(r) || c != floor(c)) return false;
+        xy[2 * i] = (int16_t)r; xy[2 * i + 1] = (int16_t)c;
+        smax = blobs[3 * i + 2] > smax ? blobs[3 * i + 2] : smax;
+    }
+    *distance = 2 * smax * sqrt(2.0);
+    return true;
 }
 
 extern "C" {
@@ -94,17 +116,27 @@ int32_t roam_prune_blobs(const double *blobs, int32_t n, double overlap, uint8_t
 {
     if (n < 0 || (n > 0 && (!blobs || !keep_out))) return ROAM_E_ARG;
     if (n == 0) return ROAM_OK;
-    std::vector<int16_t> xy(2 * (size_t)n);
-    double smax = blobs[2];
-    for (int i = 0; i < n; i++) {
-        const double r = blobs[3 * i], c = blobs[3 * i + 1];
-        if (!(r >= 0 && r <= 32767 && c >= 0 && c <= 32767) || r != floor(r) || c != floor(c)) return ROAM_E_ARG;
-        xy[2 * i] = (int16_t)r; xy[2 * i + 1] = (int16_t)c;
-        smax = blobs[3 * i + 2] > smax ? blobs[3 * i + 2] : smax;
-    }
-    const double distance = 2 * smax * sqrt(2.0);
+    std::vector<int16_t> xy;
+    double distance;
+    if (!blob_points(blobs, n, xy, &distance)) return ROAM_E_ARG;
     const int32_t rc = n > 32767 ? ROAM_E_CAPACITY : prune_blobs_narrow(blobs, n, overlap, xy.data(), distance, keep_out);
     return rc == ROAM_E_CAPACITY ? prune_blobs_wide(blobs, n, overlap, xy.data(), distance, keep_out) : rc;
+}
+
+// test: the candidate pairs of roam_prune_blobs' 16-bit form, i << 16 | j (i < j), in the order cKDTree.query_pairs emits them (what
+// the set is filled in).  n <= 32767 blobs; pairs_out holds cap entries; ROAM_E_CAPACITY beyond 32767 pairs or cap.
+int32_t roam_debug_prune_pairs(const double *blobs, int32_t n, uint32_t *pairs_out, int32_t cap, int32_t *n_pairs)
+{
+    if (n < 1 || n > 32767 || !blobs || !pairs_out || !n_pairs || cap < 0) return ROAM_E_ARG;
+    std::vector<int16_t> xy;
+    double distance;
+    if (!blob_points(blobs, n, xy, &distance)) return ROAM_E_ARG;
+    std::vector<uint32_t> pairs;
+    const int np = narrow_pairs(xy.data(), n, distance, pairs);
+    if (np < 0 || np > cap) return ROAM_E_CAPACITY;
+    for (int k = 0; k < np; k++) pairs_out[k] = pairs[k];
+    *n_pairs = np;
+    return ROAM_OK;
 }
 
 // np.argsort(keys) with the tie order of the reference's pinned NumPy 1.22.3 (adaptiveNMS, getFeatures.py:69)

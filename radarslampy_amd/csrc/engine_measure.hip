@@ -250,4 +250,64 @@ int32_t roam_engine_debug_detect(roam_ctx *ctx, int32_t fused, int32_t n_slots, 
     return ROAM_OK;
 }
 
+// test entry: the blob bookkeeping alone (K4-K6: candidate order, _prune_blobs with its pair order, sigma argsort, SSC) on the caller's
+// candidate lists, through the engine's own per-detection scratch and the ONE call a step makes - launch_retrack_bookkeeping(st, rt, P,
+// nullptr) with the device count rt_n = P - so P picks the launch form (rt_book_kernel below 256, emit + small + full class from 256,
+// longest list first from 512).  cand_rc / cand_val: P lists of `rows_given` rows each (rc = row << 16 | col << 2 | layer, any order,
+// keys distinct); cand_n[p] is the count the determinant kernel would have left: it may exceed rows_given only beyond BP_MAX_PTS
+// (then rows_given = BP_MAX_PTS).  Outputs (kp_out P x BP_MAX_PTS x 3, sel_out P x BP_MAX_PTS, the others P) are what the kernels left in
+// scratch prefilled with 0xff bytes (kp: NaN) / 0x7f bytes (the int32 arrays).  pairs_out (optional, P x (BP_MAX_PAIRS + 1)): the pair
+// scratch as the kernels left it - the candidate pairs i << 16 | j (i < j, response-order indices) in query_pairs' EMISSION order
+// from entry 0 on (the caller knows how many there are); meaningless after a tree / task overflow.
+int32_t roam_engine_debug_blobs(roam_ctx *ctx, int32_t P, int32_t rows_given, const uint32_t *cand_rc, const double *cand_val,
+                                const int32_t *cand_n, int32_t *kp_n_out, double *kp_out, int32_t *flags_out, int32_t *sel_n_out,
+                                int32_t *sel_out, uint32_t *pairs_out)
+{
+    ENGINE();
+    if (!e->rt_on) { ROAM_SET_ERR(ctx, "debug_blobs: needs retrack_on_device"); return ROAM_E_STATE; }
+    ARG_CHECK(ctx, P >= 1 && P <= e->B && rows_given >= 0 && rows_given <= BP_MAX_PTS && cand_n && kp_n_out && kp_out && flags_out && sel_n_out && sel_out);
+    ARG_CHECK(ctx, rows_given == 0 || (cand_rc && cand_val));
+    std::vector<uint32_t> keys;
+    for (int p = 0; p < P; p++) {
+        ARG_CHECK(ctx, cand_n[p] >= 0 && std::min(cand_n[p], BP_MAX_PTS) <= rows_given);
+        const int n = std::min(cand_n[p], BP_MAX_PTS);
+        keys.assign(cand_rc + (size_t)p * rows_given, cand_rc + (size_t)p * rows_given + n);
+        for (uint32_t k : keys) {
+            const int layer = (int)(k & 3u);
+            ARG_CHECK(ctx, (int)(k >> 16) < e->W && (int)((k >> 2) & 0x3fffu) < e->W && (layer == 1 || layer == 2));
+        }
+        std::sort(keys.begin(), keys.end());
+        ARG_CHECK(ctx, std::adjacent_find(keys.begin(), keys.end()) == keys.end());     // K4 ranks by key: a repeated key leaves a row unwritten
+    }
+    hipStream_t st = ctx->stream;
+    RtArgs &r = e->rt;
+    const size_t D = (size_t)P;
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (rows_given > 0) {
+        HIP_TRY(ctx, hipMemcpy2DAsync(r.cand_rc, sizeof(uint32_t) * BP_MAX_PTS, cand_rc, sizeof(uint32_t) * (size_t)rows_given,
+                                      sizeof(uint32_t) * (size_t)rows_given, D, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpy2DAsync(r.cand_val, sizeof(double) * BP_MAX_PTS, cand_val, sizeof(double) * (size_t)rows_given,
+                                      sizeof(double) * (size_t)rows_given, D, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(r.cand_n, cand_n, sizeof(int32_t) * D, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r.rt_n, &P, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(r.kp, 0xff, sizeof(double) * D * BP_MAX_PTS * 3, st));
+    HIP_TRY(ctx, hipMemsetAsync(r.sel, 0x7f, sizeof(int32_t) * D * BP_MAX_PTS, st));
+    for (int32_t *q : {r.kp_n, r.slot_flags, r.sel_n}) HIP_TRY(ctx, hipMemsetAsync(q, 0x7f, sizeof(int32_t) * D, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                                          // (the host arrays above are pageable)
+    HIP_TRY(ctx, launch_retrack_bookkeeping(st, r, P, nullptr));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpy(kp_out, r.kp, sizeof(double) * D * BP_MAX_PTS * 3, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(sel_out, r.sel, sizeof(int32_t) * D * BP_MAX_PTS, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(kp_n_out, r.kp_n, sizeof(int32_t) * D, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(flags_out, r.slot_flags, sizeof(int32_t) * D, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(sel_n_out, r.sel_n, sizeof(int32_t) * D, hipMemcpyDeviceToHost));
+    if (pairs_out) HIP_TRY(ctx, hipMemcpy(pairs_out, r.pairs, sizeof(uint32_t) * D * (BP_MAX_PAIRS + 1), hipMemcpyDeviceToHost));
+    // the scratch as a detection expects it: empty lists (rt_append_kernel clears them in a step), no count left at RT_BLOBS_REDO
+    for (int32_t *q : {r.cand_n, r.kp_n, r.slot_flags, r.sel_n}) HIP_TRY(ctx, hipMemset(q, 0, sizeof(int32_t) * D));
+    const int32_t zero = 0;
+    HIP_TRY(ctx, hipMemcpy(r.rt_n, &zero, sizeof(int32_t), hipMemcpyHostToDevice));
+    return ROAM_OK;
+}
+
 }  // extern "C"

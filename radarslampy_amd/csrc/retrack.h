@@ -77,6 +77,9 @@ hipError_t launch_ssc_batch(hipStream_t st, const double *kp, int64_t kp_stride,
 hipError_t launch_retrack_part(hipStream_t st, const RtArgs &a, int P, int which);
 // candidates of the first P slots sorted into (row, column, layer) order (diagnostics: the lists stay as they are)
 hipError_t launch_retrack_emit(hipStream_t st, const RtArgs &a, int P);
+// K4-K6 over the first B detections exactly as launch_retrack calls them (retrack_blobs.hip; the test entry roam_engine_debug_blobs makes
+// this call alone)
+__attribute__((visibility("hidden"))) hipError_t launch_retrack_bookkeeping(hipStream_t st, const RtArgs &a, int B, hipEvent_t after_order);
 hipError_t retrack_init();
 // fills boxtab (retrack_boxtab_words(W) uint32 words) from the sampling map: geometry only, once per engine
 size_t retrack_boxtab_words(int W);

@@ -51,6 +51,7 @@ template <bool SMALL> struct RtBlobLds {
     int st[3 * 256];
     int16_t nbox[CP::NNODE][4];       // query_pairs' tracker box of every node: the root's bounds cut by the split planes on the way down
                                       // ({min0, max0, min1, max1}; filled as the nodes are built)
+    uint8_t nslid[CP::NNODE];         // bit k: bound k of nbox lies on a slid split (BP_SLID): the tracker's bound is bp_next_up(nbox[k])
     uint16_t tabA[CP::CAPA];
     alignas(8) uint16_t tabB[CP::CAPB];   // hash table of the set order; before that the packed points of the tree build (NP x 8 B)
     uint32_t ovbits[(CP::LDS_PAIRS + 31) / 32 + 1];
@@ -65,7 +66,7 @@ template <bool SMALL> struct RtBlobLds {
 // touched before the pointers get there, so the two ordered lists of misplaced POSITIONS can be taken from the array as it stands (ballot +
 // prefix count per 64 positions), the number of swaps is the number of i with L[i] < R[i], and the swaps are independent of each other:
 // the same array, element for element, as the sequential code (an element equal to the pivot sits in both lists; it stops the scan from
-// whichever side reaches it first, exactly as there; checked against the sequential algorithms on 20 000 random arrays with heavy ties).  Median-of-three, the <= 3-element insertion sort and the rare heap-select
+// whichever side reaches it first, exactly as there; checked against the sequential algorithms on 20 000 random arrays with heavy ties: tests/test_blob_book_cpu.py).  Median-of-three, the <= 3-element insertion sort and the rare heap-select
 // fallback stay sequential (uniform values / lane 0).  Lp, Rp: scratch of (end - start) uint16 each.
 #define RB_WAVE_MIN 100                     // nodes with more elements take this path (a level of eight 66-element nodes is faster lane by lane)
 __device__ __forceinline__ int rb_key(const BpPt *pt, int i, int d) { return (int16_t)(pt[i].v >> (16 * d)); }
@@ -162,21 +163,21 @@ __device__ int rb_build_node_wave(BpPt *pt, int start, int end, BpNode &nd, int 
     const int half = (end - start) / 2;
     rb_nth_element_wave(pt, start, start + half, end, d, lane, Lp, Rp);
     int split = rb_key(pt, start + half, d);
-    // scipy's partition pass: p advances over keys < split, q retreats over keys >= split, misplaced pairs are swapped: afterwards the
-    // keys below the split fill [start, p)
+    // scipy's partition pass: p advances over keys < thr, q retreats over keys >= thr, misplaced pairs are swapped: afterwards the
+    // keys below thr fill [start, start + the count returned)
     const uint64_t below = (1ull << lane) - 1ull;
-    int nL = 0, nR = 0;
-    for (int c0 = start; c0 < end; c0 += 64) {
-        const int pos = c0 + lane;
-        const int k = pos < end ? rb_key(pt, pos, d) : 0;
-        const bool ge = pos < end && k >= split, lt = pos < end && k < split;
-        const uint64_t bl = __ballot(ge), br = __ballot(lt);
-        if (ge) Lp[nL + __popcll(bl & below)] = (uint16_t)pos;
-        if (lt) Rp[nR + __popcll(br & below)] = (uint16_t)pos;
-        nL += __popcll(bl); nR += __popcll(br);
-    }
-    __syncthreads();
-    {
+    auto split_pass = [&](int thr) {
+        int nL = 0, nR = 0;
+        for (int c0 = start; c0 < end; c0 += 64) {
+            const int pos = c0 + lane;
+            const int k = pos < end ? rb_key(pt, pos, d) : 0;
+            const bool ge = pos < end && k >= thr, lt = pos < end && k < thr;
+            const uint64_t bl = __ballot(ge), br = __ballot(lt);
+            if (ge) Lp[nL + __popcll(bl & below)] = (uint16_t)pos;
+            if (lt) Rp[nR + __popcll(br & below)] = (uint16_t)pos;
+            nL += __popcll(bl); nR += __popcll(br);
+        }
+        __syncthreads();
         const int nm = min(nL, nR);
         int kk = 0;
         for (int i0 = 0; i0 < nm; i0 += 64) {
@@ -186,25 +187,16 @@ __device__ int rb_build_node_wave(BpPt *pt, int start, int end, BpNode &nd, int 
             if (__popcll(bal) < min(64, nm - i0)) break;
         }
         for (int i = lane; i < kk; i += 64) { const int x = Lp[i], y = Rp[nR - 1 - i]; const BpPt t = pt[x]; pt[x] = pt[y]; pt[y] = t; }
-    }
-    __syncthreads();
-    int p = start + nR;                                                     // = start + the number of keys below the split
-    if (p == start || p == end) {                                           // (no point on one side: slide to the smallest / largest - sequential, rare)
-        if (lane == 0) {
-            if (p == start) {
-                int j = start; split = rb_key(pt, j, d);
-                for (int k = start + 1; k < end; k++) if (rb_key(pt, k, d) < split) { j = k; split = rb_key(pt, j, d); }
-                const BpPt t = pt[start]; pt[start] = pt[j]; pt[j] = t;
-            } else {
-                int j = end - 1; split = rb_key(pt, j, d);
-                for (int k = start; k < end - 1; k++) if (rb_key(pt, k, d) > split) { j = k; split = rb_key(pt, j, d); }
-                const BpPt t = pt[end - 1]; pt[end - 1] = pt[j]; pt[j] = t;
-            }
-        }
         __syncthreads();
-        split = rb_key(pt, p == start ? start : end - 1, d);
-        p = p == start ? start + 1 : end - 1;
+        return nR;
+    };
+    int p = start + split_pass(split);
+    if (p == start) {                           // no point below the median key: the plane slides just above the smallest key and the
+        split = d ? mn1 : mn0;                  // points AT it go to less (bp_build_node; rare)
+        p = start + split_pass(split + 1);
+        d |= BP_SLID;
     }
+    // (p == end cannot happen: the median itself is >= split)
     nd.split_dim = (int16_t)d; nd.split = split;
     return p;
 }
@@ -372,7 +364,7 @@ __device__ int rt_blobs_body(const RtArgs &a, int first, RtBlobLds<SMALL> &L, bo
                 mn0 = min(mn0, __shfl_xor(mn0, d)); mx0 = max(mx0, __shfl_xor(mx0, d));
                 mn1 = min(mn1, __shfl_xor(mn1, d)); mx1 = max(mx1, __shfl_xor(mx1, d));
             }
-            if (lane == 0) { L.nbox[0][0] = (int16_t)mn0; L.nbox[0][1] = (int16_t)mx0; L.nbox[0][2] = (int16_t)mn1; L.nbox[0][3] = (int16_t)mx1; }
+            if (lane == 0) { L.nbox[0][0] = (int16_t)mn0; L.nbox[0][1] = (int16_t)mx0; L.nbox[0][2] = (int16_t)mn1; L.nbox[0][3] = (int16_t)mx1; L.nslid[0] = 0; }
         }
         if (lane == 0) { L.nodes[0].start = 0; L.nodes[0].end = (int16_t)n; }
         nn = 1;
@@ -406,8 +398,11 @@ __device__ int rt_blobs_body(const RtArgs &a, int first, RtBlobLds<SMALL> &L, bo
                         L.nodes[c0].start = (int16_t)start; L.nodes[c0].end = (int16_t)p;
                         L.nodes[c0 + 1].start = (int16_t)p; L.nodes[c0 + 1].end = (int16_t)end;
                         for (int k = 0; k < 4; k++) L.nbox[c0][k] = L.nbox[c0 + 1][k] = L.nbox[me][k];
-                        L.nbox[c0][2 * nd.split_dim + 1] = (int16_t)nd.split;      // less: max = split
-                        L.nbox[c0 + 1][2 * nd.split_dim] = (int16_t)nd.split;      // greater: min = split
+                        const int sd = nd.split_dim & 1, slid = nd.split_dim & BP_SLID ? 1 : 0, ps = L.nslid[me];
+                        L.nbox[c0][2 * sd + 1] = (int16_t)nd.split;                // less: max = split
+                        L.nbox[c0 + 1][2 * sd] = (int16_t)nd.split;                // greater: min = split
+                        L.nslid[c0] = (uint8_t)((ps & ~(2 << (2 * sd))) | (slid << (2 * sd + 1)));
+                        L.nslid[c0 + 1] = (uint8_t)((ps & ~(1 << (2 * sd))) | (slid << (2 * sd)));
                     }
                     L.nodes[me] = nd;
                 }
@@ -426,9 +421,14 @@ __device__ int rt_blobs_body(const RtArgs &a, int first, RtBlobLds<SMALL> &L, bo
     for (int i = lane; i < n; i += 64) L.idx[i] = (int16_t)(pt[i].v >> 32);          // cKDTree.indices
     __syncthreads();
     RB_P(1)
-    // dual-tree traversal -> ordered leaf x leaf blocks.  query_pairs recurses over node pairs with a distance tracker it pushes and pops; on
-    // integer pixel coordinates every quantity of that tracker is an exact integer, so its state at a node pair is a function of the two
-    // nodes' boxes alone (nbox) and the recursion needs no stack: the pairs are expanded LEVEL BY LEVEL, every item replaced in place by its
+    // dual-tree traversal -> ordered leaf x leaf blocks.  query_pairs recurses over node pairs with a distance tracker it pushes and pops.
+    // The tracker updates mind / maxd incrementally only when all of mind, maxd and the changed dimension's terms are at least its
+    // inaccurate_distance_limit - which scipy sets to the ROOT pair's maxd, so that practically every push recomputes both sums from
+    // the two boxes (bp_tpush); and where it does update incrementally the terms are integers on integer pixel bounds, exact either
+    // way.  So the tracker's state at a node pair is a function of the two nodes' boxes alone (nbox, nslid) and the recursion needs
+    // no stack.  A box bound on a slid split is nextafter(m), no integer: such node pairs take the from-scratch float64 sums in
+    // bp_tfull's order below (an incremental update of them could round differently, but needs mind >= the root's maxd >= ub, a pair
+    // that is pruned whatever the last bit says); all others compare exact integers.  The pairs are expanded LEVEL BY LEVEL, every item replaced in place by its
     // children in the recursion's order (a finished leaf x leaf block is its own child), so that the list stays in emission order throughout.
     // One lane per item, ballots for the offsets; two lists of BP_MAX_TASKS packed items ping-pong in the detection's pair scratch.  (On lane 0
     // the recursion was 45 % of this kernel: ~230 us of a lone detection.)  item = a | b << 10 | m << 20; m: 0 check, 1 no check, 2 / 3 block
@@ -467,7 +467,8 @@ __device__ int rt_blobs_body(const RtArgs &a, int first, RtBlobLds<SMALL> &L, bo
                     const BpNode n1 = L.nodes[na], n2 = L.nodes[nb];
                     const bool l1 = n1.split_dim == -1, l2 = n2.split_dim == -1;
                     bool pruned = false;
-                    if (m == 0) {
+                    const int sa = L.nslid[na], sb = L.nslid[nb];
+                    if (m == 0 && !(sa | sb)) {
                         int mind = 0, maxd = 0;
                         for (int k = 0; k < 2; k++) {
                             const int a0 = L.nbox[na][2 * k], a1 = L.nbox[na][2 * k + 1], b0 = L.nbox[nb][2 * k], b1 = L.nbox[nb][2 * k + 1];
@@ -476,6 +477,23 @@ __device__ int rt_blobs_body(const RtArgs &a, int first, RtBlobLds<SMALL> &L, bo
                         }
                         if (mind > t_gt) pruned = true;
                         else if (maxd < t_lt) m = 1;
+                    } else if (m == 0) {
+                        // a bound on a slid split is not an integer: the tracker's float64 arithmetic as it stands (bp_tdim / bp_tfull:
+                        // every product and sum rounded on its own)
+                        double mind = 0, maxd = 0;
+                        for (int k = 0; k < 2; k++) {
+                            double a0 = (double)L.nbox[na][2 * k], a1 = (double)L.nbox[na][2 * k + 1], b0 = (double)L.nbox[nb][2 * k], b1 = (double)L.nbox[nb][2 * k + 1];
+                            if ((sa >> (2 * k)) & 1) a0 = bp_next_up(a0);
+                            if ((sa >> (2 * k + 1)) & 1) a1 = bp_next_up(a1);
+                            if ((sb >> (2 * k)) & 1) b0 = bp_next_up(b0);
+                            if ((sb >> (2 * k + 1)) & 1) b1 = bp_next_up(b1);
+                            double lo = a0 - b1 > b0 - a1 ? a0 - b1 : b0 - a1;
+                            if (lo < 0) lo = 0;
+                            const double hi = a1 - b0 > b1 - a0 ? a1 - b0 : b1 - a0;
+                            mind = __dadd_rn(mind, __dmul_rn(lo, lo)); maxd = __dadd_rn(maxd, __dmul_rn(hi, hi));
+                        }
+                        if (mind > ub) pruned = true;
+                        else if (maxd < ub) m = 1;
                     }
                     const uint32_t mm = (uint32_t)m << 20;
                     if (pruned) cnt = 0;

@@ -364,6 +364,27 @@ class Engine:
                                                          _ffi._ptr(n), int(s_slot or 0), _ffi._ptr(S) if S is not None else None))
         return (n, rc, val) if S is None else (n, rc, val, S)
 
+    def debug_blobs(self, rc, val, cand_n=None, want_pairs=False):
+        """test entry (roam_engine_debug_blobs): the blob bookkeeping alone on P candidate lists.  rc (P, rows) uint32 = row << 16 |
+        col << 2 | layer, val (P, rows) float64, cand_n (P,) (default: rows) -> dict(kp_n (P,), kp (P, 2048, 3), flags (P,), sel_n (P,),
+        sel (P, 2048)); untouched outputs hold NaN (kp) / 0x7f7f7f7f.  want_pairs: also pairs (P, 32768) uint32, the candidate pairs
+        i << 16 | j in query_pairs' emission order from entry 0 on"""
+        rc = np.ascontiguousarray(rc, np.uint32)
+        val = np.ascontiguousarray(val, np.float64)
+        P, rows = rc.shape
+        assert val.shape == rc.shape
+        cand_n = np.full(P, rows, np.int32) if cand_n is None else np.ascontiguousarray(cand_n, np.int32)
+        assert cand_n.shape == (P,)
+        out = dict(kp_n=np.zeros(P, np.int32), kp=np.zeros((P, 2048, 3), np.float64), flags=np.zeros(P, np.int32),
+                   sel_n=np.zeros(P, np.int32), sel=np.zeros((P, 2048), np.int32))
+        pairs = np.zeros((P, 32768), np.uint32) if want_pairs else None
+        self.ctx.check(self.lib.roam_engine_debug_blobs(self.ctx.h, P, rows, _ffi._ptr(rc) if rows else None, _ffi._ptr(val) if rows else None,
+                                                        _ffi._ptr(cand_n), _ffi._ptr(out["kp_n"]), _ffi._ptr(out["kp"]), _ffi._ptr(out["flags"]),
+                                                        _ffi._ptr(out["sel_n"]), _ffi._ptr(out["sel"]), _ffi._ptr(pairs) if want_pairs else None))
+        if want_pairs:
+            out["pairs"] = pairs
+        return out
+
     def time_kernel(self, name: str, reps: int = 20):
         ms = C.c_float(0)
         by = C.c_double(0)
