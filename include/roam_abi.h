@@ -403,6 +403,54 @@ int32_t roam_engine_time_loop_describe(roam_ctx *ctx, roam_loop_db *db, int32_t 
 int32_t roam_time_loop_db_query(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index, int32_t k,
                                 double max_distance, int32_t reps, float *distance_ms, float *select_ms);
 
+/* ---- loop-closure verification: batched trimmed point-to-point ICP in the plane (csrc/icp.hip).  The reference has no such step
+ * (its Keyframe.pointCloud, Mapping.py:61-62, is never read): PARITY UNPINNED, the contract is tests/icp_model.py.
+ * Pair p aligns src (the points src_off[p] .. src_off[p + 1], float64 metres, x y interleaved) to dst (dst_off likewise) from the pose
+ * init[p] = (theta, tx, ty) and returns the pose with dst ~ R(theta) src + t.  One workgroup per pair, the iteration loop inside the
+ * kernel.  Iteration k, gate g_k (g_0 = gate_start, g_{k+1} = max(gate_end, g_k gate_decay)):
+ *   q_i = R(theta) src_i + t in float64, rounded to float32; dst rounded to float32; the partner j(i) minimises
+ *   d2 = fl32(fl32(dx dx) + fl32(dy dy)) over the float32 differences (no fused multiply-add), the lowest j of the minimum, by
+ *   exhaustive search; pair i is kept when d2 <= fl32(g_k g_k).  Fewer than min_pairs kept: FEW_PAIRS, the pose stays, the loop ends.
+ *   Over the kept pairs, float64, from the float64 coordinates: the centroids am, bm, then S_cos = sum (a - am) . (b - bm) and
+ *   S_sin = sum (a - am) x (b - bm) in a second pass; theta' = atan2(S_sin, S_cos), or theta when both sums are exactly 0;
+ *   t' = bm - R(theta') am.  After the update: OK when g_k == gate_end, |wrap(theta' - theta)| < eps_rot and |t' - t| < eps_trans;
+ *   MAX_ITERATIONS after max_iterations updates.
+ * One scoring pass at the final pose with gate_end (also after FEW_PAIRS): n_inliers = the kept pairs, rms = sqrt(mean d2) with d2 in
+ * float64 between the float64 transformed point and its partner's float64 coordinates, +inf when n_inliers = 0.  An empty src or dst:
+ * FEW_PAIRS, the initial pose, 0 inliers.  iterations = the updates made; n_pairs_last = the pairs kept by the loop's last search.
+ * Sums run in one order per pair (a lane over its points i = lane, lane + 512, ...; the wave's xor butterfly; the waves in order), no
+ * floating-point atomics: a pair's result is the same bits alone, anywhere in a batch, in any chunk and in any call.  Pairs are
+ * processed in chunks that keep the device scratch under 2000 MiB (ROAM_ICP_CHUNK_BYTES in the environment, read per call, lowers
+ * where a batch is cut - for tests).
+ * Limits: 1 .. 65535 pairs, 0 .. 8192 points per cloud, coordinates, translations and gates within 1e6 m (float32 then holds every
+ * squared distance), max_iterations in [1, 1000].
+ * ROAM_E_ARG before any device call: a null pointer (opts may be NULL: the defaults 3.0 m, 0.5 m, 0.8, 40, 1e-4 m, 1e-5 rad, 3),
+ * a limit exceeded, a negative first or a decreasing offset, a coordinate or pose that is not finite, gates not
+ * 0 < gate_end <= gate_start, gate_decay outside (0, 1], min_pairs < 2, a negative or NaN eps. */
+#define ROAM_ICP_MAX_PAIRS 65535
+#define ROAM_ICP_MAX_POINTS 8192
+#define ROAM_ICP_MAX_COORD 1e6
+#define ROAM_ICP_ITERATION_LIMIT 1000
+enum { ROAM_ICP_OK = 0, ROAM_ICP_MAX_ITERATIONS = 1, ROAM_ICP_FEW_PAIRS = 2 };
+typedef struct roam_icp_opts {
+    double  gate_start, gate_end;   /* metres */
+    double  gate_decay;
+    int32_t max_iterations;
+    double  eps_trans, eps_rot;     /* metres, radians */
+    int32_t min_pairs;
+} roam_icp_opts;
+typedef struct roam_icp_stats {
+    int32_t status, iterations, n_pairs_last, n_inliers;
+    double  rms;
+} roam_icp_stats;
+int32_t roam_icp2d_batch(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off /* n + 1 */, const double *src /* N x 2 */,
+                         const int32_t *dst_off /* n + 1 */, const double *dst /* M x 2 */, const double *init /* n x 3: theta tx ty */,
+                         const roam_icp_opts *opts, double *pose_out /* n x 3: theta tx ty */, roam_icp_stats *stats /* n */);
+/* measurement: the pairs are uploaded once, then HIP events on the context stream around `reps` launches of the kernel, two warm
+ * ones first -> milliseconds per launch.  The pairs must fit one launch */
+int32_t roam_time_icp2d_batch(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off, const double *src, const int32_t *dst_off,
+                              const double *dst, const double *init, const roam_icp_opts *opts, int32_t reps, float *ms_per_rep);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous

@@ -7,15 +7,25 @@ of their sector columns, minimised over all circular sector shifts; the best shi
 the candidate ~ 2 pi shift / sectors).  The device compares a query with every stored keyframe at every shift exactly: no ring-key
 tree, no coarse sector-key alignment.
 
-What comes out are CANDIDATES and a yaw.  The method's reach is short: on the synthetic worlds a revisit 2.5 m off the stored place
-still ranks first but at 0.79 of the next place's distance, and at 5 m it is not recognised (the point reflectors move to other
-rings).  Verifying a candidate metrically and measuring its edge (FMT.getTransformUsingFMT after a pre-rotation by the yaw is the
-obvious route), and feeding edges to PoseGraphLib.PoseGraphOptimization, are not done here."""
+What comes out of LoopDetector are CANDIDATES and a yaw.  The method's reach is short: on the synthetic worlds a revisit 2.5 m off the
+stored place still ranks first but at 0.79 of the next place's distance, and at 5 m it is not recognised (the point reflectors move to
+other rings).
+
+Verification.  A candidate is verified metrically by a trimmed point-to-point ICP of the two keyframes' polar peak clouds
+(Keyframe.pointCloud, which the reference stores and never reads), seeded with the candidate's yaw: csrc/icp.hip, every pair of a
+call in one device pass; contract tests/icp_model.py.  alignPointClouds aligns clouds, verifyCandidates turns LoopDetector.query's
+arrays into accepted SE(2) edges, closeLoops feeds them to PoseGraphLib.graphFromKeyframes and optimises.  The Fourier-Mellin route
+(FMT.getTransformUsingFMT after a pre-rotation by the yaw) is independent of this one and not used here."""
 import numbers
 
 import numpy as np
 
 from . import _ffi
+from .parseData import RANGE_RESOLUTION_M
+
+# verifyCandidates' default minInlierFraction: the geometric mean of the smallest true-place fraction (0.4741) and the largest
+# wrong-place fraction (0.1880) that tests/icp_model.py measures on the revisit world at full density (docs/PARITY.md)
+MIN_INLIER_FRACTION = 0.2985
 
 
 def _yaw(shift, sectors):
@@ -108,3 +118,126 @@ class LoopDetector:
     def descriptors(self):
         """the stored descriptors (n, sectors, rings) float32"""
         return self.db.get() if len(self.db) else np.empty((0, self.sectors, self.rings), np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- verification
+def polarIndToLocalMetres(pointCloud, rows, rangeResolutionM=RANGE_RESOLUTION_M):
+    """The (K, 2) [thetaInd, rInd] rows of getPointCloudPolarInd -> (K, 2) float64 metres in the sensor-centred frame of
+    Keyframe.featurePointsLocal: r res (cos phi, sin phi) with phi = 2 pi thetaInd / rows - (pixel - centre) resolution of the image
+    convertPolarImageToCartesian makes, x along its columns and y along its rows.  Host code."""
+    pc = np.asarray(pointCloud)
+    if pc.size == 0:
+        return np.zeros((0, 2), np.float64)
+    if pc.ndim != 2 or pc.shape[1] != 2:
+        raise ValueError(f"polarIndToLocalMetres: (K, 2) rows [thetaInd, rInd], not {pc.shape}")
+    if not isinstance(rows, numbers.Integral) or isinstance(rows, bool) or rows < 1:
+        raise ValueError(f"polarIndToLocalMetres: rows (the azimuths of the polar image) an integer >= 1, not {rows!r}")
+    pc = pc.astype(np.float64)
+    phi = 2.0 * np.pi * pc[:, 0] / rows
+    r = pc[:, 1] * float(rangeResolutionM)
+    return np.stack([r * np.cos(phi), r * np.sin(phi)], axis=1)
+
+
+def _align_batch(pairs, init, opts):
+    """the one device call of this module (the tests patch it) -> (poses (n, 3) rows (theta, tx, ty), stats: _ffi.ICP_STATS rows)"""
+    args = _ffi.icp2d_args(pairs, init, opts)        # the argument checks come before a device is asked for
+    return _ffi.default_context().icp2d_batch(pairs, args[4], args[5])
+
+
+def alignPointClouds(src, dst, init=(0.0, 0.0, 0.0), **opts):
+    """Trimmed point-to-point ICP of src (n, 2) onto dst (m, 2), metres, from the pose init = (theta, tx, ty) ->
+    (pose (3,) (theta, tx, ty) with dst ~ R(theta) src + t, stats dict: status, iterations, n_pairs_last, n_inliers, rms).  Lists of
+    clouds (one init for all, or one row each) -> (poses (N, 3), stats: a structured array with those fields), every pair in one
+    device call.  opts: gate_start, gate_end, gate_decay, max_iterations, eps_trans, eps_rot, min_pairs (_ffi.ICP_DEFAULTS).  status:
+    _ffi.ICP_OK, ICP_MAX_ITERATIONS or ICP_FEW_PAIRS.  ValueError before the device is touched for a bad argument."""
+    one = isinstance(src, np.ndarray) and src.ndim == 2 or len(src) == 0 or np.ndim(src[0]) < 2 and np.shape(src[0]) in ((2,), (0,))
+    if one:                                       # one cloud: an (n, 2) array, or a list of (x, y) rows
+        poses, stats = _align_batch([(src, dst)], init, opts)
+        return poses[0], {name: stats[0][name].item() for name in stats.dtype.names}
+    if len(src) != len(dst):
+        raise ValueError(f"alignPointClouds: {len(src)} src clouds and {len(dst)} dst clouds")
+    return _align_batch(list(zip(src, dst)), init, opts)
+
+
+VERIFY_TABLE = np.dtype([("query", np.int32), ("candidate", np.int32), ("slot", np.int32), ("yaw", np.float64), ("theta", np.float64),
+                         ("tx", np.float64), ("ty", np.float64), ("status", np.int32), ("iterations", np.int32), ("n_pairs_last", np.int32),
+                         ("n_inliers", np.int32), ("fraction", np.float64), ("rms", np.float64), ("accepted", np.bool_)])
+
+
+def verifyCandidates(clouds, queryIndex, candIndex, candYaw, *, minInlierFraction=MIN_INLIER_FRACTION, maxRmsM=None, maxTranslationM=5.0,
+                     allPerQuery=False, **opts):
+    """Verify loop-closure candidates by ICP and measure their edges.  clouds: one (K, 2) metre cloud per keyframe
+    (polarIndToLocalMetres); queryIndex (Q,), candIndex (Q, k) and candYaw (Q, k): what went into and came out of
+    LoopDetector.query - slots with index -1 are skipped.  Each candidate aligns src = clouds[query] to dst = clouds[candidate] from
+    (candYaw, 0, 0), all in one device call, and is accepted when its status is OK or MAX_ITERATIONS,
+    n_inliers / min(n, m) >= minInlierFraction, rms <= maxRmsM (None: gate_end) and |t| <= maxTranslationM.
+    -> (edges, table).  edges: (candidate, query, (tx, ty, theta)) tuples, the measurement x_candidate^-1 x_query in the form
+    PoseGraphLib.graphFromKeyframes(loopEdges=...) takes; per query the accepted candidate with the largest inlier fraction (the
+    lowest rms, then the lowest slot on ties), or every accepted one with allPerQuery.  table: one row per tried candidate, a
+    structured array (query, candidate, slot, yaw, theta, tx, ty, status, iterations, n_pairs_last, n_inliers, fraction, rms,
+    accepted)."""
+    q = np.asarray(queryIndex).reshape(-1)
+    ci = np.asarray(candIndex)
+    ci = ci.reshape(len(q), -1) if ci.size else ci.reshape(len(q), 0)
+    yaw = np.asarray(candYaw, np.float64).reshape(ci.shape)
+    if q.dtype.kind not in "iu" or ci.dtype.kind not in "iu":
+        raise ValueError("verifyCandidates: queryIndex and candIndex of integers")
+    o = _ffi.icp2d_opts(opts)
+    max_rms = o.gate_end if maxRmsM is None else float(maxRmsM)
+    if not (0.0 <= float(minInlierFraction) <= 1.0) or not max_rms >= 0.0 or not float(maxTranslationM) >= 0.0:
+        raise ValueError("verifyCandidates: minInlierFraction in [0, 1], maxRmsM and maxTranslationM >= 0")
+    rows = [(int(q[a]), int(ci[a, b]), b) for a in range(len(q)) for b in range(ci.shape[1]) if ci[a, b] >= 0]
+    for qi, cj, _ in rows:
+        if not (0 <= qi < len(clouds) and cj < len(clouds)):
+            raise ValueError(f"verifyCandidates: query {qi} / candidate {cj} outside the {len(clouds)} clouds")
+    table = np.zeros(len(rows), VERIFY_TABLE)
+    if not rows:
+        return [], table
+    pos = np.array([a for a in range(len(q)) for b in range(ci.shape[1]) if ci[a, b] >= 0])      # the row's position in queryIndex
+    seeds = np.array([[yaw[a, slot], 0.0, 0.0] for a, (_, _, slot) in zip(pos, rows)])
+    poses, stats = _align_batch([(clouds[qi], clouds[cj]) for qi, cj, _ in rows], seeds, o)
+    sizes = np.array([min(len(clouds[qi]), len(clouds[cj])) for qi, cj, _ in rows])
+    table["query"], table["candidate"], table["slot"] = [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
+    table["yaw"], table["theta"], table["tx"], table["ty"] = seeds[:, 0], poses[:, 0], poses[:, 1], poses[:, 2]
+    for name in ("status", "iterations", "n_pairs_last", "n_inliers", "rms"):
+        table[name] = stats[name]
+    table["fraction"] = np.where(sizes > 0, stats["n_inliers"] / np.maximum(sizes, 1), 0.0)
+    table["accepted"] = ((stats["status"] != _ffi.ICP_FEW_PAIRS) & (table["fraction"] >= float(minInlierFraction)) & (stats["rms"] <= max_rms)
+                         & (np.hypot(poses[:, 1], poses[:, 2]) <= float(maxTranslationM)))
+    edges = []
+    for a in range(len(q)):
+        acc = [r for r in np.flatnonzero(pos == a) if table["accepted"][r]]
+        if not allPerQuery and acc:
+            acc = [min(acc, key=lambda r: (-table["fraction"][r], table["rms"][r], table["slot"][r]))]
+        for r in acc:
+            edges.append((int(table["candidate"][r]), int(table["query"][r]),
+                          np.array([table["tx"][r], table["ty"][r], table["theta"][r]])))
+    return edges, table
+
+
+def closeLoops(keyframes, detector, clouds=None, *, rows=None, rangeResolutionM=RANGE_RESOLUTION_M, loopInformation=np.eye(3), huber=None,
+               odomInformation=np.eye(3), max_iterations=20, ctx=None, **verify):
+    """Close the loops of a keyframe list: keyframes with .pose and .pointCloud (Mapping.Map.keyframes) and a LoopDetector that already
+    holds their scans, entry k = keyframe k.  The peak clouds are converted to metres (rows: the azimuths of the polar images, by default
+    those of keyframes[0].radarPolarImg; or pass ready clouds), every keyframe is queried, the candidates are verified in one device
+    call (verify: verifyCandidates' keywords and the ICP options), PoseGraphLib.graphFromKeyframes is called with the accepted edges
+    and optimised.  -> (graph, edges, table); graph.get_pose(k) is keyframe k's optimised pose.  Without an accepted edge the graph is
+    returned un-optimised (odometry alone has nothing to correct)."""
+    from . import PoseGraphLib
+    keyframes = list(keyframes)
+    if len(detector) != len(keyframes):
+        raise ValueError(f"closeLoops: the detector holds {len(detector)} scans for {len(keyframes)} keyframes")
+    if clouds is None:
+        if rows is None:
+            rows = int(np.asarray(keyframes[0].radarPolarImg).shape[0])
+        clouds = [polarIndToLocalMetres(k.pointCloud, rows, rangeResolutionM) for k in keyframes]
+    elif len(clouds) != len(keyframes):
+        raise ValueError(f"closeLoops: {len(clouds)} clouds for {len(keyframes)} keyframes")
+    idx = np.arange(len(keyframes), dtype=np.int32)
+    ci, _, yaw = detector.query(idx)
+    edges, table = verifyCandidates(clouds, idx, ci, yaw, **verify)
+    loop = [(i, j, z, loopInformation) + ((huber,) if huber is not None else ()) for i, j, z in edges]
+    graph = PoseGraphLib.graphFromKeyframes(keyframes, loopEdges=loop, odomInformation=odomInformation, loopInformation=loopInformation, ctx=ctx)
+    if edges:
+        graph.optimize(max_iterations)
+    return graph, edges, table

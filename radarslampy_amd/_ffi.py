@@ -65,6 +65,22 @@ POSE_GRAPH_MAX_ITERATIONS = 1000
 POSE_GRAPH_MAX_TRIALS = 1000
 POSE_GRAPH_CHUNK_BYTES = 2000 << 20     # device scratch of one launch
 
+class IcpOpts(C.Structure):
+    """roam_abi.h roam_icp_opts"""
+    _fields_ = [("gate_start", C.c_double), ("gate_end", C.c_double), ("gate_decay", C.c_double), ("max_iterations", C.c_int32),
+                ("eps_trans", C.c_double), ("eps_rot", C.c_double), ("min_pairs", C.c_int32)]
+
+
+# roam_abi.h roam_icp_stats, one row per pair
+ICP_STATS = np.dtype([("status", np.int32), ("iterations", np.int32), ("n_pairs_last", np.int32), ("n_inliers", np.int32),
+                      ("rms", np.float64)])
+IcpStats = ICP_STATS
+ICP_OK, ICP_MAX_ITERATIONS, ICP_FEW_PAIRS = 0, 1, 2     # roam_abi.h ROAM_ICP_*: the status of a pair
+ICP_MAX_PAIRS, ICP_MAX_POINTS = 65535, 8192             # limits of roam_icp2d_batch
+ICP_MAX_COORD = 1e6
+ICP_ITERATION_LIMIT = 1000
+ICP_DEFAULTS = dict(gate_start=3.0, gate_end=0.5, gate_decay=0.8, max_iterations=40, eps_trans=1e-4, eps_rot=1e-5, min_pairs=3)
+
 SCAN_CONTEXT_MAX_SECTORS, SCAN_CONTEXT_MAX_RINGS = 256, 128     # roam_abi.h ROAM_SCAN_CONTEXT_MAX_*
 SCAN_CONTEXT_MAX_ROWS, SCAN_CONTEXT_MAX_CLIP = 65536, 4096
 LOOP_MAX_K = 32                         # roam_abi.h ROAM_LOOP_MAX_K
@@ -141,6 +157,8 @@ _SIGS = {
     "roam_loop_db_query": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "roam_engine_time_loop_describe": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
     "roam_time_loop_db_query": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _P(C.c_float), _P(C.c_float)]),
+    "roam_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), _vp, _vp]),
+    "roam_time_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), C.c_int32, _P(C.c_float)]),
     "roam_engine_create": (C.c_int32, [_vp, _P(EngineCfg)]),
     "roam_engine_destroy": (C.c_int32, [_vp]),
     "roam_engine_upload_scan": (C.c_int32, [_vp, C.c_int32, _vp]),
@@ -590,6 +608,78 @@ def loop_query_args(count, indices, max_index, k, max_distance):
     return q, m
 
 
+def icp2d_opts(opts=None):
+    """the options of roam_icp2d_batch: None, a dict over ICP_DEFAULTS or an IcpOpts -> IcpOpts, checked.  ValueError: an unknown
+    name, gates not 0 < gate_end <= gate_start (<= 1e6 m), gate_decay outside (0, 1], max_iterations outside [1, 1000],
+    min_pairs < 2, an eps that is negative or not a number"""
+    if isinstance(opts, IcpOpts):
+        o = {name: getattr(opts, name) for name, _ in IcpOpts._fields_}
+    else:
+        unknown = set(opts or ()) - set(ICP_DEFAULTS)
+        if unknown:
+            raise ValueError(f"icp2d: unknown option(s) {sorted(unknown)}; known: {sorted(ICP_DEFAULTS)}")
+        o = dict(ICP_DEFAULTS, **(opts or {}))
+    for name in ("max_iterations", "min_pairs"):
+        if not isinstance(o[name], numbers.Integral) or isinstance(o[name], bool):
+            raise ValueError(f"icp2d: {name} an integer, not {o[name]!r}")
+    for name in ("gate_start", "gate_end", "gate_decay", "eps_trans", "eps_rot"):
+        if not isinstance(o[name], numbers.Real) or isinstance(o[name], bool):
+            raise ValueError(f"icp2d: {name} a number, not {o[name]!r}")
+    if not (np.isfinite(o["gate_start"]) and 0.0 < o["gate_end"] <= o["gate_start"] <= ICP_MAX_COORD):
+        raise ValueError(f"icp2d: gates 0 < gate_end <= gate_start <= {ICP_MAX_COORD:g}, not {o['gate_end']} and {o['gate_start']}")
+    if not 0.0 < o["gate_decay"] <= 1.0:
+        raise ValueError(f"icp2d: gate_decay in (0, 1], not {o['gate_decay']}")
+    if not 1 <= o["max_iterations"] <= ICP_ITERATION_LIMIT:
+        raise ValueError(f"icp2d: max_iterations in [1, {ICP_ITERATION_LIMIT}], not {o['max_iterations']}")
+    if o["min_pairs"] < 2 or o["min_pairs"] > 2 ** 31 - 1:
+        raise ValueError(f"icp2d: min_pairs an int32 >= 2, not {o['min_pairs']}")
+    if not (o["eps_trans"] >= 0.0 and o["eps_rot"] >= 0.0):
+        raise ValueError(f"icp2d: eps_trans and eps_rot >= 0, not {o['eps_trans']} and {o['eps_rot']}")
+    return IcpOpts(float(o["gate_start"]), float(o["gate_end"]), float(o["gate_decay"]), int(o["max_iterations"]), float(o["eps_trans"]),
+                   float(o["eps_rot"]), int(o["min_pairs"]))
+
+
+def icp2d_args(pairs, init=None, opts=None):
+    """The argument checks of Context.icp2d_batch, made before a device is asked for -> (src_off, src, dst_off, dst, init, IcpOpts):
+    the pairs packed as roam_icp2d_batch takes them.  pairs: a list of (src (n, 2), dst (m, 2)) in metres, n and m from 0 to 8192;
+    init: (3,) for every pair or (len(pairs), 3) rows (theta, tx, ty), None = zeros; opts: see icp2d_opts.  ValueError: no pair or more
+    than 65535, a cloud that is not (k, 2) or larger than the limit, a coordinate or pose that is not finite or beyond 1e6 m, an init
+    of another shape, and what icp2d_opts refuses."""
+    o = icp2d_opts(opts)
+    pairs = list(pairs)
+    if not 1 <= len(pairs) <= ICP_MAX_PAIRS:
+        raise ValueError(f"icp2d: 1 to {ICP_MAX_PAIRS} pairs, not {len(pairs)}")
+    S, D = [], []
+    for p, pair in enumerate(pairs):
+        if len(pair) != 2:
+            raise ValueError(f"icp2d: pair {p} is (src, dst), not {len(pair)} items")
+        for name, cloud, out in (("src", pair[0], S), ("dst", pair[1], D)):
+            a = np.asarray(cloud)
+            if a.dtype.kind not in "fiu":
+                raise ValueError(f"icp2d: pair {p}: {name} of numbers, not {a.dtype}")
+            a = a.astype(np.float64, copy=False)
+            if a.size == 0 and a.ndim <= 2:
+                a = a.reshape(0, 2)
+            if a.ndim != 2 or a.shape[1] != 2:
+                raise ValueError(f"icp2d: pair {p}: {name} (k, 2), not {a.shape}")
+            if len(a) > ICP_MAX_POINTS:
+                raise ValueError(f"icp2d: pair {p}: {name} has {len(a)} points, more than {ICP_MAX_POINTS}")
+            if not np.all(np.abs(a) <= ICP_MAX_COORD):              # NaN fails too
+                raise ValueError(f"icp2d: pair {p}: {name} has a coordinate that is not finite or beyond {ICP_MAX_COORD:g} m")
+            out.append(a)
+    x0 = np.zeros((len(pairs), 3)) if init is None else np.asarray(init, np.float64)
+    if x0.shape == (3,):
+        x0 = np.tile(x0, (len(pairs), 1))
+    if x0.shape != (len(pairs), 3):
+        raise ValueError(f"icp2d: init (3,) or ({len(pairs)}, 3) rows (theta, tx, ty), not {x0.shape}")
+    if not (np.all(np.isfinite(x0)) and np.all(np.abs(x0[:, 1:]) <= ICP_MAX_COORD)):
+        raise ValueError(f"icp2d: an initial pose that is not finite or beyond {ICP_MAX_COORD:g} m")
+    src_off = np.concatenate([[0], np.cumsum([len(a) for a in S])]).astype(np.int32)
+    dst_off = np.concatenate([[0], np.cumsum([len(a) for a in D])]).astype(np.int32)
+    return (src_off, np.ascontiguousarray(np.concatenate(S).reshape(-1, 2)), dst_off, np.ascontiguousarray(np.concatenate(D).reshape(-1, 2)),
+            np.ascontiguousarray(x0), o)
+
+
 def _f32_rows_in_place(a):
     """a float32 view with unit column stride and forward row / image strides is read in place; anything else is copied"""
     ok = a.dtype == np.float32 and a.strides[-1] == 4 and a.strides[-2] % 4 == 0 and a.strides[-2] >= 4 * a.shape[-1]
@@ -936,6 +1026,27 @@ class Context:
         self.check(self.lib.roam_pose_graph_optimize(self.h, n, _ptr(vertex_off), _ptr(poses), _ptr(fixed), _ptr(edge_off), _ptr(ij),
                                                      _ptr(meas), _ptr(info), _ptr(huber), C.byref(opts), _ptr(stats)))
         return [poses[vertex_off[g]:vertex_off[g + 1]].copy() for g in range(n)], stats
+
+    def icp2d_batch(self, pairs, init=None, opts=None):
+        """Trimmed point-to-point ICP in the plane for a batch of cloud pairs in one device pass (roam_icp2d_batch: one workgroup per
+        pair, exhaustive float32 nearest-neighbour search, float64 closed-form update, the gate shrinking from gate_start to gate_end).
+        pairs: a list of (src (n, 2), dst (m, 2)); init: (3,) or (len(pairs), 3) rows (theta, tx, ty); opts: None, a dict over
+        ICP_DEFAULTS or an IcpOpts -> (poses (len(pairs), 3) rows (theta, tx, ty) with dst ~ R(theta) src + t, stats: ICP_STATS rows).
+        A pair's result does not depend on the batch.  Arguments are checked by icp2d_args before any library call."""
+        src_off, src, dst_off, dst, x0, o = icp2d_args(pairs, init, opts)
+        n = len(src_off) - 1
+        poses, stats = np.empty((n, 3), np.float64), np.zeros(n, ICP_STATS)
+        self.check(self.lib.roam_icp2d_batch(self.h, n, _ptr(src_off), _ptr(src), _ptr(dst_off), _ptr(dst), _ptr(x0), C.byref(o), _ptr(poses),
+                                             _ptr(stats)))
+        return poses, stats
+
+    def time_icp2d_batch(self, pairs, init=None, opts=None, reps=5):
+        """milliseconds per launch of the ICP kernel on these pairs (roam_time_icp2d_batch: events, two warm launches first)"""
+        src_off, src, dst_off, dst, x0, o = icp2d_args(pairs, init, opts)
+        ms = C.c_float()
+        self.check(self.lib.roam_time_icp2d_batch(self.h, len(src_off) - 1, _ptr(src_off), _ptr(src), _ptr(dst_off), _ptr(dst), _ptr(x0),
+                                                  C.byref(o), int(reps), C.byref(ms)))
+        return ms.value
 
     def scan_context(self, polar, sectors=60, rings=20, clip_px=None, floor=0.0):
         """the scan-context descriptors of a 2-D float32 polar image or a 3-D batch (roam_scan_context_f32) -> (n, sectors, rings)
