@@ -451,6 +451,59 @@ int32_t roam_icp2d_batch(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off 
 int32_t roam_time_icp2d_batch(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off, const double *src, const int32_t *dst_off,
                               const double *dst, const double *init, const roam_icp_opts *opts, int32_t reps, float *ms_per_rep);
 
+/* ---- loop database with resident peak clouds: verification from the store (csrc/loopclosure.hip, csrc/icp.hip).  PARITY UNPINNED as
+ * the two sections above; the contract is tests/loop_cloud_model.py on top of tests/icp_model.py.
+ * A database that keeps clouds stores beside every descriptor the scan's polar peaks in metres.  The peaks are those of
+ * roam_peaks_record_u8 / roam_peaks_polar_f32 in their azimuth-major order (a record: the engine's cfg.clip columns; an image: all its
+ * columns, whatever clip_px the descriptor uses), N of them.  step = max(point_stride, ceil(N / max_points)); the entry keeps the peaks
+ * q = 0, step, 2 step, ... (ceil(N / step) points) as x = fl64(fl64(r range_resolution_m) cos_t[theta]), y likewise with sin_t, every
+ * multiply rounded once; N stays readable.  cos_t / sin_t are roam_polar_cloud_table's: the host's libm, the device only multiplies.
+ * What is stored depends on the scan alone - not on the batch, the position or the chunk (ROAM_LOOP_CHUNK_BYTES also cuts these).
+ *
+ * roam_polar_cloud_table: host only, no context.  phi_t = (2.0 * M_PI * t) / rows in float64 (two rounded operations), t < rows <=
+ * 65536; ROAM_E_ARG outside the limits or for a null pointer.
+ * roam_loop_db_keep_clouds: once, on an empty database; every later roam_loop_db_add_f32 / roam_engine_loop_db_add must have `rows`
+ * azimuths (and at most ROAM_MAX_COLS columns) and stores the cloud with the descriptor; roam_loop_db_add_desc stores an empty cloud.
+ * ROAM_E_ARG, the text naming the argument: db not empty or keeping clouds already, max_points outside [1, ROAM_ICP_MAX_POINTS],
+ * point_stride < 1, range_resolution_m not finite or <= 0, rows outside [1, 65536], capacity x max_points x 16 bytes beyond 2000 MiB.
+ * A failed add leaves descriptors and clouds as they were.
+ * roam_loop_db_set_cloud replaces the cloud of a stored entry from the host (n <= max_points points, coordinates within
+ * ROAM_ICP_MAX_COORD; the entry's peak count becomes n); roam_loop_db_get_cloud reads it back: *n_out points stored, *n_peaks_out
+ * peaks the scan had, the first min(n, cap) points in xy_out, ROAM_E_CAPACITY when n > cap.  roam_loop_db_cloud_counts: the two counts
+ * of the entries first .. first + n - 1 from the host's copy, no device call.  ROAM_E_STATE: the database keeps no clouds. */
+int32_t roam_polar_cloud_table(int32_t rows, double *cos_out /* rows */, double *sin_out /* rows */);
+int32_t roam_loop_db_keep_clouds(roam_ctx *ctx, roam_loop_db *db, int32_t rows, int32_t max_points, int32_t point_stride,
+                                 double range_resolution_m);
+int32_t roam_loop_db_set_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t index, const double *xy /* n x 2 */, int32_t n);
+int32_t roam_loop_db_get_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t index, double *xy_out /* cap x 2 */, int32_t cap, int32_t *n_out,
+                               int32_t *n_peaks_out);
+int32_t roam_loop_db_cloud_counts(const roam_loop_db *db, int32_t first, int32_t n, int32_t *n_out, int32_t *n_peaks_out);
+/* roam_icp2d_batch's iteration on pairs of stored clouds: pair p aligns the cloud of entry src_index[p] to that of entry dst_index[p]
+ * from init[p]; an empty cloud on either side is FEW_PAIRS with the pose equal to the seed.  Options, their checks and every bit of
+ * a pair's result are roam_icp2d_batch's on the same clouds.  The partner scratch is per pair, so one entry may be the source of any
+ * number of pairs of a call.  1 .. 65535 pairs, cut into launches under 2000 MiB of scratch (ROAM_LOOP_CHUNK_BYTES lowers it).
+ * ROAM_E_ARG before any device call: null pointers, an index outside the stored entries, a seed that is not finite, bad options.
+ *
+ * roam_loop_db_query_verify: roam_loop_db_query's distance and selection kernels, a kernel that turns slot (i, s) into the pair
+ * (source = entry query_index[i], destination = candidate (i, s), seed (yaw, 0, 0) with yaw = (6.283185307179586 shift) / S, minus
+ * 6.283185307179586 when that exceeds 3.141592653589793) and the ICP kernel, enqueued on the context's stream with no host
+ * synchronisation between them, then one read-back.  cand_* are what roam_loop_db_query returns for the same arguments; pose_out /
+ * stats row i k + s belongs to slot (i, s), an unused slot (index -1) is FEW_PAIRS at its seed (0, 0, 0). */
+int32_t roam_loop_db_verify(roam_ctx *ctx, roam_loop_db *db, int32_t n_pairs, const int32_t *src_index, const int32_t *dst_index,
+                            const double *init /* n x 3 */, const roam_icp_opts *opts, double *pose_out /* n x 3 */, roam_icp_stats *stats /* n */);
+int32_t roam_loop_db_query_verify(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index,
+                                  int32_t k, double max_distance, const roam_icp_opts *opts, int32_t *cand_index /* n k */,
+                                  double *cand_dist /* n k */, int32_t *cand_shift /* n k */, double *pose_out /* n k 3 */,
+                                  roam_icp_stats *stats /* n k */);
+/* measurement, as roam_engine_time_loop_describe / roam_time_icp2d_batch: HIP events on the context's stream, two warm launches, `reps`
+ * timed -> milliseconds per launch.  roam_engine_time_loop_cloud: the cloud build of n resident records into the free entries of db
+ * (nothing is appended), its two kernels apart - the peak row kernel and the cloud gather.  roam_time_loop_db_verify: the ICP launch
+ * on these stored pairs, which must fit one launch */
+int32_t roam_engine_time_loop_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t reps, float *rows_ms,
+                                    float *gather_ms);
+int32_t roam_time_loop_db_verify(roam_ctx *ctx, roam_loop_db *db, int32_t n_pairs, const int32_t *src_index, const int32_t *dst_index,
+                                 const double *init, const roam_icp_opts *opts, int32_t reps, float *ms_per_rep);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous

@@ -15,7 +15,13 @@ Verification.  A candidate is verified metrically by a trimmed point-to-point IC
 (Keyframe.pointCloud, which the reference stores and never reads), seeded with the candidate's yaw: csrc/icp.hip, every pair of a
 call in one device pass; contract tests/icp_model.py.  alignPointClouds aligns clouds, verifyCandidates turns LoopDetector.query's
 arrays into accepted SE(2) edges, closeLoops feeds them to PoseGraphLib.graphFromKeyframes and optimises.  The Fourier-Mellin route
-(FMT.getTransformUsingFMT after a pre-rotation by the yaw) is independent of this one and not used here."""
+(FMT.getTransformUsingFMT after a pre-rotation by the yaw) is independent of this one and not used here.
+
+Resident clouds.  LoopDetector(keepClouds=True, rows=...) makes the database the owner of the clouds: every scan that is described
+(add, Engine.loop_db_add) leaves its polar peaks in metres beside its descriptor, built on the device at that moment - an engine's
+pool has forgotten the scan long before a revisit is recognised.  verify and queryAndVerify run the same ICP from that store, the
+second with no host round trip between the query and the verification; closeLoops uses it when the detector keeps clouds.  The
+rule of the stored points (every step-th peak, tables from the host's libm) is tests/loop_cloud_model.py."""
 import numbers
 
 import numpy as np
@@ -66,7 +72,10 @@ class LoopDetector:
     query(i) returns the k stored entries most like entry i among those at least min_gap entries older, with their distances and
     yaw differences."""
 
-    def __init__(self, capacity, sectors=60, rings=20, clip_px=None, floor=0.0, min_gap=50, max_distance=0.2, k=8, ctx=None):
+    def __init__(self, capacity, sectors=60, rings=20, clip_px=None, floor=0.0, min_gap=50, max_distance=0.2, k=8, ctx=None, keepClouds=False,
+                 rows=None, maxPoints=8192, pointStride=1, rangeResolutionM=RANGE_RESOLUTION_M):
+        """keepClouds: every added scan also stores its polar peak cloud in metres (rows: the azimuths of every scan to come; at most
+        maxPoints points per entry, every step-th peak with step = max(pointStride, ceil(peaks / maxPoints)))"""
         if not isinstance(min_gap, numbers.Integral) or isinstance(min_gap, bool) or min_gap < 1:
             raise ValueError(f"LoopDetector: min_gap an integer >= 1, not {min_gap!r}")
         if clip_px is not None and (not isinstance(clip_px, numbers.Integral) or isinstance(clip_px, bool) or clip_px < 0):
@@ -74,8 +83,17 @@ class LoopDetector:
         self.floor = _ffi.scan_context_floor(floor)
         _ffi.loop_query_args(1, [0], [0], k, max_distance)
         self.clip_px, self.min_gap, self.max_distance, self.k = clip_px, int(min_gap), float(max_distance), int(k)
+        self.keepClouds = bool(keepClouds)
+        if self.keepClouds:
+            if rows is None:
+                raise ValueError("LoopDetector: keepClouds needs rows, the azimuths of the scans")
+            if not isinstance(capacity, numbers.Integral) or isinstance(capacity, bool) or capacity < 1:
+                raise ValueError(f"LoopDetector: capacity an integer >= 1, not {capacity!r}")
+            _ffi.loop_cloud_args(capacity, rows, maxPoints, pointStride, rangeResolutionM)
         self.db = _ffi.LoopDb(ctx, capacity, sectors, rings)
         self.sectors, self.rings = self.db.sectors, self.db.rings
+        if self.keepClouds:
+            self.db.keep_clouds(rows, maxPoints, pointStride, rangeResolutionM)
 
     def close(self):
         self.db.close()
@@ -84,12 +102,56 @@ class LoopDetector:
         return len(self.db)
 
     def add(self, polarImg):
-        """describe a float32 polar image (or a 3-D batch) on the device and store it -> the index of the (first) new entry"""
+        """describe a float32 polar image (or a 3-D batch) on the device and store it -> the index of the (first) new entry.  With
+        keepClouds the image's peak cloud (all its columns) is stored too"""
         return self.db.add_f32(polarImg, self.clip_px, self.floor)
 
-    def addDescriptors(self, desc):
-        """store ready-made descriptors, (sectors, rings) or (n, sectors, rings) -> the index of the first new entry"""
-        return self.db.add_desc(desc)
+    def addDescriptors(self, desc, clouds=None):
+        """store ready-made descriptors, (sectors, rings) or (n, sectors, rings) -> the index of the first new entry.  clouds (with
+        keepClouds): one (K, 2) metre cloud per descriptor; without them the entries hold empty clouds"""
+        if clouds is not None:
+            if not self.keepClouds:
+                raise ValueError("LoopDetector.addDescriptors: clouds for a detector that keeps none")
+            n = 1 if np.ndim(desc) == 2 else len(desc)
+            if len(clouds) != n:
+                raise ValueError(f"LoopDetector.addDescriptors: {len(clouds)} clouds for {n} descriptors")
+            clouds = [_ffi.loop_cloud_points(c, self.db.max_points) for c in clouds]
+        first = self.db.add_desc(desc)
+        for i, c in enumerate(clouds or ()):
+            self.db.set_cloud(first + i, c)
+        return first
+
+    def cloud(self, i):
+        """-> (xy (n, 2) float64 metres: the stored cloud of entry i, the scan's full peak count)"""
+        return self.db.get_cloud(i)
+
+    def verify(self, queryIndex, candIndex, candYaw, **verify):
+        """verifyCandidates from the stored clouds: the arguments, keywords and results are verifyCandidates' without `clouds`"""
+        q, ci, yaw, o, accept = _verify_args(queryIndex, candIndex, candYaw, verify)
+        rows, pos = _verify_rows(q, ci, len(self.db), "entries")
+        if not rows:
+            return [], np.zeros(0, VERIFY_TABLE)
+        seeds = np.array([[yaw[a, slot], 0.0, 0.0] for a, (_, _, slot) in zip(pos, rows)])
+        poses, stats = self.db.verify([r[0] for r in rows], [r[1] for r in rows], seeds, o)
+        n, _ = self.db.cloud_counts()
+        sizes = np.array([min(n[qi], n[cj]) for qi, cj, _ in rows])
+        return _accept(len(q), rows, pos, seeds, poses, stats, sizes, *accept)
+
+    def queryAndVerify(self, indices=None, **verify):
+        """query the entries `indices` (None: the newest) and verify every candidate from the stored clouds in the same device pass
+        (roam_loop_db_query_verify) -> (edges, table) as verifyCandidates returns them"""
+        idx = np.array([len(self.db) - 1], np.int32) if indices is None else np.ascontiguousarray(indices, np.int32).ravel()
+        o, accept = _verify_opts(verify)
+        ci, _, cs, poses, stats = self.db.query_verify(idx, idx - self.min_gap + 1, self.k, self.max_distance, o)
+        rows, pos = _verify_rows(idx, ci, len(self.db), "entries")
+        if not rows:
+            return [], np.zeros(0, VERIFY_TABLE)
+        flat = np.array([a * self.k + slot for a, (_, _, slot) in zip(pos, rows)])
+        yaw = _yaw(cs, self.sectors).reshape(-1)[flat]
+        seeds = np.stack([yaw, np.zeros(len(rows)), np.zeros(len(rows))], axis=1)
+        n, _ = self.db.cloud_counts()
+        sizes = np.array([min(n[qi], n[cj]) for qi, cj, _ in rows])
+        return _accept(len(idx), rows, pos, seeds, poses.reshape(-1, 3)[flat], stats.reshape(-1)[flat], sizes, *accept)
 
     def floorCode(self):
         """the integer floor of the u8 record form that equals this detector's floor (Engine.loop_db_add): floor * 255, which must be
@@ -176,36 +238,65 @@ def verifyCandidates(clouds, queryIndex, candIndex, candYaw, *, minInlierFractio
     lowest rms, then the lowest slot on ties), or every accepted one with allPerQuery.  table: one row per tried candidate, a
     structured array (query, candidate, slot, yaw, theta, tx, ty, status, iterations, n_pairs_last, n_inliers, fraction, rms,
     accepted)."""
+    opts.update(minInlierFraction=minInlierFraction, maxRmsM=maxRmsM, maxTranslationM=maxTranslationM, allPerQuery=allPerQuery)
+    q, ci, yaw, o, accept = _verify_args(queryIndex, candIndex, candYaw, opts)
+    rows, pos = _verify_rows(q, ci, len(clouds), "clouds")
+    if not rows:
+        return [], np.zeros(0, VERIFY_TABLE)
+    seeds = np.array([[yaw[a, slot], 0.0, 0.0] for a, (_, _, slot) in zip(pos, rows)])
+    poses, stats = _align_batch([(clouds[qi], clouds[cj]) for qi, cj, _ in rows], seeds, o)
+    sizes = np.array([min(len(clouds[qi]), len(clouds[cj])) for qi, cj, _ in rows])
+    return _accept(len(q), rows, pos, seeds, poses, stats, sizes, *accept)
+
+
+def _verify_opts(keywords):
+    """verifyCandidates' keywords -> (IcpOpts, (minInlierFraction, max_rms, maxTranslationM, allPerQuery)); ValueError as there"""
+    kw = dict(keywords)
+    minInlierFraction = kw.pop("minInlierFraction", MIN_INLIER_FRACTION)
+    maxRmsM = kw.pop("maxRmsM", None)
+    maxTranslationM = kw.pop("maxTranslationM", 5.0)
+    allPerQuery = kw.pop("allPerQuery", False)
+    o = _ffi.icp2d_opts(kw)
+    max_rms = o.gate_end if maxRmsM is None else float(maxRmsM)
+    if not (0.0 <= float(minInlierFraction) <= 1.0) or not max_rms >= 0.0 or not float(maxTranslationM) >= 0.0:
+        raise ValueError("verifyCandidates: minInlierFraction in [0, 1], maxRmsM and maxTranslationM >= 0")
+    return o, (float(minInlierFraction), max_rms, float(maxTranslationM), bool(allPerQuery))
+
+
+def _verify_args(queryIndex, candIndex, candYaw, keywords):
+    """-> (q (Q,), ci (Q, k), yaw (Q, k), IcpOpts, the acceptance's parameters)"""
     q = np.asarray(queryIndex).reshape(-1)
     ci = np.asarray(candIndex)
     ci = ci.reshape(len(q), -1) if ci.size else ci.reshape(len(q), 0)
     yaw = np.asarray(candYaw, np.float64).reshape(ci.shape)
     if q.dtype.kind not in "iu" or ci.dtype.kind not in "iu":
         raise ValueError("verifyCandidates: queryIndex and candIndex of integers")
-    o = _ffi.icp2d_opts(opts)
-    max_rms = o.gate_end if maxRmsM is None else float(maxRmsM)
-    if not (0.0 <= float(minInlierFraction) <= 1.0) or not max_rms >= 0.0 or not float(maxTranslationM) >= 0.0:
-        raise ValueError("verifyCandidates: minInlierFraction in [0, 1], maxRmsM and maxTranslationM >= 0")
+    return (q, ci, yaw) + _verify_opts(keywords)
+
+
+def _verify_rows(q, ci, count, what):
+    """the candidates to try -> (rows: (query, candidate, slot) of every slot that holds one, pos: the row's position in q)"""
     rows = [(int(q[a]), int(ci[a, b]), b) for a in range(len(q)) for b in range(ci.shape[1]) if ci[a, b] >= 0]
     for qi, cj, _ in rows:
-        if not (0 <= qi < len(clouds) and cj < len(clouds)):
-            raise ValueError(f"verifyCandidates: query {qi} / candidate {cj} outside the {len(clouds)} clouds")
+        if not (0 <= qi < count and cj < count):
+            raise ValueError(f"verifyCandidates: query {qi} / candidate {cj} outside the {count} {what}")
+    pos = np.array([a for a in range(len(q)) for b in range(ci.shape[1]) if ci[a, b] >= 0], dtype=np.int64)
+    return rows, pos
+
+
+def _accept(n_query, rows, pos, seeds, poses, stats, sizes, minInlierFraction, max_rms, maxTranslationM, allPerQuery):
+    """The acceptance, written once for verifyCandidates, LoopDetector.verify and LoopDetector.queryAndVerify: the tried candidates
+    (rows, pos: _verify_rows), their seeds, ICP poses and statistics, sizes = min(n, m) of each pair's clouds -> (edges, table)"""
     table = np.zeros(len(rows), VERIFY_TABLE)
-    if not rows:
-        return [], table
-    pos = np.array([a for a in range(len(q)) for b in range(ci.shape[1]) if ci[a, b] >= 0])      # the row's position in queryIndex
-    seeds = np.array([[yaw[a, slot], 0.0, 0.0] for a, (_, _, slot) in zip(pos, rows)])
-    poses, stats = _align_batch([(clouds[qi], clouds[cj]) for qi, cj, _ in rows], seeds, o)
-    sizes = np.array([min(len(clouds[qi]), len(clouds[cj])) for qi, cj, _ in rows])
     table["query"], table["candidate"], table["slot"] = [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
     table["yaw"], table["theta"], table["tx"], table["ty"] = seeds[:, 0], poses[:, 0], poses[:, 1], poses[:, 2]
     for name in ("status", "iterations", "n_pairs_last", "n_inliers", "rms"):
         table[name] = stats[name]
     table["fraction"] = np.where(sizes > 0, stats["n_inliers"] / np.maximum(sizes, 1), 0.0)
-    table["accepted"] = ((stats["status"] != _ffi.ICP_FEW_PAIRS) & (table["fraction"] >= float(minInlierFraction)) & (stats["rms"] <= max_rms)
-                         & (np.hypot(poses[:, 1], poses[:, 2]) <= float(maxTranslationM)))
+    table["accepted"] = ((stats["status"] != _ffi.ICP_FEW_PAIRS) & (table["fraction"] >= minInlierFraction) & (stats["rms"] <= max_rms)
+                         & (np.hypot(poses[:, 1], poses[:, 2]) <= maxTranslationM))
     edges = []
-    for a in range(len(q)):
+    for a in range(n_query):
         acc = [r for r in np.flatnonzero(pos == a) if table["accepted"][r]]
         if not allPerQuery and acc:
             acc = [min(acc, key=lambda r: (-table["fraction"][r], table["rms"][r], table["slot"][r]))]
@@ -222,11 +313,15 @@ def closeLoops(keyframes, detector, clouds=None, *, rows=None, rangeResolutionM=
     those of keyframes[0].radarPolarImg; or pass ready clouds), every keyframe is queried, the candidates are verified in one device
     call (verify: verifyCandidates' keywords and the ICP options), PoseGraphLib.graphFromKeyframes is called with the accepted edges
     and optimised.  -> (graph, edges, table); graph.get_pose(k) is keyframe k's optimised pose.  Without an accepted edge the graph is
-    returned un-optimised (odometry alone has nothing to correct)."""
-    from . import PoseGraphLib
+    returned un-optimised (odometry alone has nothing to correct).  A detector that keeps clouds (LoopDetector(keepClouds=True)) and
+    clouds = None: the candidates are found and verified from the detector's own store in one device pass (queryAndVerify) and
+    keyframe.pointCloud, rows and rangeResolutionM are not used."""
     keyframes = list(keyframes)
     if len(detector) != len(keyframes):
         raise ValueError(f"closeLoops: the detector holds {len(detector)} scans for {len(keyframes)} keyframes")
+    if clouds is None and getattr(detector, "keepClouds", False):      # the detector owns the clouds: keyframe.pointCloud is not read
+        edges, table = detector.queryAndVerify(np.arange(len(keyframes), dtype=np.int32), **verify)
+        return _optimise(keyframes, edges, table, loopInformation, huber, odomInformation, max_iterations, ctx)
     if clouds is None:
         if rows is None:
             rows = int(np.asarray(keyframes[0].radarPolarImg).shape[0])
@@ -236,6 +331,12 @@ def closeLoops(keyframes, detector, clouds=None, *, rows=None, rangeResolutionM=
     idx = np.arange(len(keyframes), dtype=np.int32)
     ci, _, yaw = detector.query(idx)
     edges, table = verifyCandidates(clouds, idx, ci, yaw, **verify)
+    return _optimise(keyframes, edges, table, loopInformation, huber, odomInformation, max_iterations, ctx)
+
+
+def _optimise(keyframes, edges, table, loopInformation, huber, odomInformation, max_iterations, ctx):
+    """closeLoops' second half: the accepted edges into PoseGraphLib.graphFromKeyframes, optimised -> (graph, edges, table)"""
+    from . import PoseGraphLib
     loop = [(i, j, z, loopInformation) + ((huber,) if huber is not None else ()) for i, j, z in edges]
     graph = PoseGraphLib.graphFromKeyframes(keyframes, loopEdges=loop, odomInformation=odomInformation, loopInformation=loopInformation, ctx=ctx)
     if edges:

@@ -157,6 +157,15 @@ _SIGS = {
     "roam_loop_db_query": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "roam_engine_time_loop_describe": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
     "roam_time_loop_db_query": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _P(C.c_float), _P(C.c_float)]),
+    "roam_polar_cloud_table": (C.c_int32, [C.c_int32, _vp, _vp]),
+    "roam_loop_db_keep_clouds": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
+    "roam_loop_db_set_cloud": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32]),
+    "roam_loop_db_get_cloud": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "roam_loop_db_cloud_counts": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
+    "roam_loop_db_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _P(IcpOpts), _vp, _vp]),
+    "roam_loop_db_query_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, _P(IcpOpts), _vp, _vp, _vp, _vp, _vp]),
+    "roam_engine_time_loop_cloud": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, _P(C.c_float), _P(C.c_float)]),
+    "roam_time_loop_db_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _P(IcpOpts), C.c_int32, _P(C.c_float)]),
     "roam_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), _vp, _vp]),
     "roam_time_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), C.c_int32, _P(C.c_float)]),
     "roam_engine_create": (C.c_int32, [_vp, _P(EngineCfg)]),
@@ -606,6 +615,69 @@ def loop_query_args(count, indices, max_index, k, max_distance):
     if not isinstance(max_distance, numbers.Real) or np.isnan(max_distance):
         raise ValueError(f"loop query: max_distance is a number, not {max_distance!r}")
     return q, m
+
+
+def polar_cloud_table(rows):
+    """roam_polar_cloud_table, host code only (no device, no context): (cos, sin) float64 of phi_t = (2 pi t) / rows, t < rows, by the
+    host's libm - the table a cloud-keeping loop database multiplies with.  ValueError: rows no integer in [1, 65536]"""
+    if not isinstance(rows, numbers.Integral) or isinstance(rows, bool) or not 1 <= rows <= SCAN_CONTEXT_MAX_ROWS:
+        raise ValueError(f"loop db: rows an integer in [1, {SCAN_CONTEXT_MAX_ROWS}], not {rows!r}")
+    c, s = np.empty(rows, np.float64), np.empty(rows, np.float64)
+    if load_library().roam_polar_cloud_table(int(rows), _ptr(c), _ptr(s)) != ROAM_OK:
+        raise ValueError(f"loop db: roam_polar_cloud_table refused rows {rows}")
+    return c, s
+
+
+def loop_cloud_args(capacity, rows, max_points, point_stride, range_resolution_m):
+    """the checks of LoopDb.keep_clouds before any library call -> (rows, max_points, point_stride, range_resolution_m)"""
+    if not isinstance(rows, numbers.Integral) or isinstance(rows, bool) or not 1 <= rows <= SCAN_CONTEXT_MAX_ROWS:
+        raise ValueError(f"loop db: rows an integer in [1, {SCAN_CONTEXT_MAX_ROWS}], not {rows!r}")
+    if not isinstance(max_points, numbers.Integral) or isinstance(max_points, bool) or not 1 <= max_points <= ICP_MAX_POINTS:
+        raise ValueError(f"loop db: max_points an integer in [1, {ICP_MAX_POINTS}], not {max_points!r}")
+    if not isinstance(point_stride, numbers.Integral) or isinstance(point_stride, bool) or not 1 <= point_stride < 2 ** 31:
+        raise ValueError(f"loop db: point_stride an integer >= 1, not {point_stride!r}")
+    res = range_resolution_m
+    if not isinstance(res, numbers.Real) or isinstance(res, bool) or not np.isfinite(res) or not res > 0:
+        raise ValueError(f"loop db: range_resolution_m finite and > 0, not {res!r}")
+    if capacity * max_points * 16 > LOOP_DB_BYTES:
+        raise ValueError(f"loop db: capacity {capacity} x max_points {max_points} x 16 bytes is beyond the {LOOP_DB_BYTES} bytes of a database")
+    return int(rows), int(max_points), int(point_stride), float(res)
+
+
+def loop_cloud_points(xy, max_points):
+    """a cloud for LoopDb.set_cloud -> (n, 2) float64, C order.  ValueError: not (n, 2) numbers, n > max_points, a coordinate that is not
+    finite or beyond 1e6 m"""
+    a = np.asarray(xy)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"loop db: a cloud of numbers, not {a.dtype}")
+    if a.size == 0 and a.ndim <= 2:
+        a = a.reshape(0, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"loop db: a cloud (n, 2), not {a.shape}")
+    if len(a) > max_points:
+        raise ValueError(f"loop db: a cloud of {len(a)} points, more than max_points = {max_points}")
+    a = np.ascontiguousarray(a, np.float64)
+    if not np.all(np.abs(a) <= ICP_MAX_COORD):
+        raise ValueError(f"loop db: a coordinate that is not finite or beyond {ICP_MAX_COORD:g} m")
+    return a
+
+
+def loop_verify_args(count, src_index, dst_index, init):
+    """the checks of LoopDb.verify before any library call -> (src_index, dst_index int32, init (n, 3) float64)"""
+    si = np.ascontiguousarray(src_index, np.int32).ravel()
+    di = np.ascontiguousarray(dst_index, np.int32).ravel()
+    if not 1 <= len(si) <= ICP_MAX_PAIRS or len(si) != len(di):
+        raise ValueError(f"loop verify: src_index and dst_index of one length in [1, {ICP_MAX_PAIRS}], not {len(si)} and {len(di)}")
+    if min(si.min(), di.min()) < 0 or max(si.max(), di.max()) >= count:
+        raise ValueError(f"loop verify: entry indices in [0, {count})")
+    x0 = np.zeros((len(si), 3)) if init is None else np.asarray(init, np.float64)
+    if x0.shape == (3,):
+        x0 = np.tile(x0, (len(si), 1))
+    if x0.shape != (len(si), 3):
+        raise ValueError(f"loop verify: init (3,) or ({len(si)}, 3) rows (theta, tx, ty), not {x0.shape}")
+    if not (np.all(np.isfinite(x0)) and np.all(np.abs(x0[:, 1:]) <= ICP_MAX_COORD)):
+        raise ValueError(f"loop verify: an initial pose that is not finite or beyond {ICP_MAX_COORD:g} m")
+    return si, di, np.ascontiguousarray(x0)
 
 
 def icp2d_opts(opts=None):
@@ -1185,7 +1257,8 @@ _lock = threading.Lock()
 
 class LoopDb:
     """A database of scan-context descriptors in HBM (roam_loop_db): add, then query.  Bound to the context it was made on (None: the
-    default context, asked for after the arguments have passed)."""
+    default context, asked for after the arguments have passed).  After keep_clouds every described scan also stores its polar peak
+    cloud in metres, and verify / query_verify run the ICP of Context.icp2d_batch from that store."""
 
     def __init__(self, ctx, capacity: int, sectors: int = 60, rings: int = 20):
         for name, v, lo, hi in (("capacity", capacity, 1, 2 ** 31 - 1), ("sectors", sectors, 2, SCAN_CONTEXT_MAX_SECTORS),
@@ -1200,6 +1273,7 @@ class LoopDb:
         h = _vp()
         ctx.check(ctx.lib.roam_loop_db_create(ctx.h, self.capacity, self.sectors, self.rings, C.byref(h)))
         self.h = h
+        self.cloud_rows = self.max_points = None             # set by keep_clouds
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -1258,6 +1332,78 @@ class LoopDb:
         self.ctx.check(self.ctx.lib.roam_loop_db_query(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance), _ptr(ci),
                                                        _ptr(cd), _ptr(cs), _ptr(df), _ptr(sf)))
         return (ci, cd, cs, df, sf) if want_full else (ci, cd, cs)
+
+    # ---- peak clouds
+    def keep_clouds(self, rows, max_points=ICP_MAX_POINTS, point_stride=1, range_resolution_m=0.0432):
+        """roam_loop_db_keep_clouds: once, on an empty database - from here on every described scan (`rows` azimuths) stores its polar
+        peaks in metres beside the descriptor: every step-th peak, step = max(point_stride, ceil(peaks / max_points))"""
+        rows, mp, ps, res = loop_cloud_args(self.capacity, rows, max_points, point_stride, range_resolution_m)
+        if self.cloud_rows is not None:
+            raise ValueError("loop db: keeps clouds already")
+        self.ctx.check(self.ctx.lib.roam_loop_db_keep_clouds(self.ctx.h, self.h, rows, mp, ps, res))
+        self.cloud_rows, self.max_points = rows, mp
+
+    def _needs_clouds(self):
+        if self.cloud_rows is None:
+            raise ValueError("loop db: keeps no clouds (keep_clouds)")
+
+    def set_cloud(self, index, xy):
+        """replace the cloud of the stored entry `index` by xy (n, 2) metres, n <= max_points"""
+        self._needs_clouds()
+        a = loop_cloud_points(xy, self.max_points)
+        if not isinstance(index, numbers.Integral) or isinstance(index, bool) or not 0 <= index < len(self):
+            raise ValueError(f"loop db: index in [0, {len(self)}), not {index!r}")
+        self.ctx.check(self.ctx.lib.roam_loop_db_set_cloud(self.ctx.h, self.h, int(index), _ptr(a), len(a)))
+
+    def cloud_counts(self):
+        """-> (points stored (count,), peaks of the scan (count,)) int32 of every entry; no device call"""
+        self._needs_clouds()
+        n = len(self)
+        a, b = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.ctx.check(self.ctx.lib.roam_loop_db_cloud_counts(self.h, 0, n, _ptr(a), _ptr(b)))
+        return a, b
+
+    def get_cloud(self, index):
+        """-> (xy (n, 2) float64 metres, the scan's full peak count)"""
+        self._needs_clouds()
+        if not isinstance(index, numbers.Integral) or isinstance(index, bool) or not 0 <= index < len(self):
+            raise ValueError(f"loop db: index in [0, {len(self)}), not {index!r}")
+        xy = np.empty((self.max_points, 2), np.float64)
+        n, n_peaks = C.c_int32(0), C.c_int32(0)
+        self.ctx.check(self.ctx.lib.roam_loop_db_get_cloud(self.ctx.h, self.h, int(index), _ptr(xy), self.max_points, C.byref(n), C.byref(n_peaks)))
+        return xy[:n.value].copy(), n_peaks.value
+
+    def verify(self, src_index, dst_index, init=None, opts=None):
+        """roam_loop_db_verify: the ICP of Context.icp2d_batch on pairs of stored clouds, entry src_index[p] onto entry dst_index[p] from
+        init -> (poses (n, 3), stats: ICP_STATS rows), bit for bit what icp2d_batch gives on the same clouds"""
+        self._needs_clouds()
+        o = icp2d_opts(opts)
+        si, di, x0 = loop_verify_args(len(self), src_index, dst_index, init)
+        poses, stats = np.empty((len(si), 3), np.float64), np.zeros(len(si), ICP_STATS)
+        self.ctx.check(self.ctx.lib.roam_loop_db_verify(self.ctx.h, self.h, len(si), _ptr(si), _ptr(di), _ptr(x0), C.byref(o), _ptr(poses), _ptr(stats)))
+        return poses, stats
+
+    def time_verify(self, src_index, dst_index, init=None, opts=None, reps=5):
+        """milliseconds per launch of the ICP kernel on these stored pairs (roam_time_loop_db_verify)"""
+        self._needs_clouds()
+        o = icp2d_opts(opts)
+        si, di, x0 = loop_verify_args(len(self), src_index, dst_index, init)
+        ms = C.c_float(0)
+        self.ctx.check(self.ctx.lib.roam_time_loop_db_verify(self.ctx.h, self.h, len(si), _ptr(si), _ptr(di), _ptr(x0), C.byref(o), int(reps), C.byref(ms)))
+        return float(ms.value)
+
+    def query_verify(self, indices, max_index, k=8, max_distance=np.inf, opts=None):
+        """roam_loop_db_query_verify: query, then every (query, slot) verified from the stored clouds with the seed (yaw of the shift,
+        0, 0), one device pass and one read-back -> (index (m, k), distance (m, k), shift (m, k), poses (m, k, 3), stats (m, k)
+        ICP_STATS); an unused slot is ICP_FEW_PAIRS at the seed (0, 0, 0)"""
+        self._needs_clouds()
+        o = icp2d_opts(opts)
+        q, m = loop_query_args(len(self), indices, max_index, k, max_distance)
+        ci, cd, cs = np.empty((len(q), k), np.int32), np.empty((len(q), k), np.float64), np.empty((len(q), k), np.int32)
+        poses, stats = np.empty((len(q), k, 3), np.float64), np.zeros((len(q), k), ICP_STATS)
+        self.ctx.check(self.ctx.lib.roam_loop_db_query_verify(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance), C.byref(o),
+                                                              _ptr(ci), _ptr(cd), _ptr(cs), _ptr(poses), _ptr(stats)))
+        return ci, cd, cs, poses, stats
 
     def time_query(self, indices, max_index, k=8, max_distance=np.inf, reps=20):
         """(distance kernel ms, selection kernel ms) per launch of this query, HIP events around reps launches (roam_time_loop_db_query)"""

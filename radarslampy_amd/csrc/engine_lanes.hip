@@ -237,6 +237,20 @@ int32_t roam_engine_time_loop_describe(roam_ctx *ctx, roam_loop_db *db, int32_t 
                                     pool_idx, clip_px, floor_code, nullptr, e->uploads_pending ? ctx->ev_up : nullptr, reps, ms_per_rep);
 }
 
+int32_t roam_engine_time_loop_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t reps, float *rows_ms,
+                                    float *gather_ms)
+{
+    ENGINE();
+    ARG_CHECK(ctx, db && n >= 1 && pool_idx && rows_ms && gather_ms);
+    for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
+    float ms[2] = {0, 0};
+    const int32_t rc = roam_loop_db_add_records(ctx, db, e->pool, (int64_t)e->rec_bytes, e->cfg.stride, e->cfg.payload_off, e->cfg.rows, e->cfg.clip,
+                                                n, pool_idx, 0, 0, nullptr, e->uploads_pending ? ctx->ev_up : nullptr, reps, nullptr, ms);
+    *rows_ms = ms[0];
+    *gather_ms = ms[1];
+    return rc;
+}
+
 int32_t roam_engine_lane_image(roam_ctx *ctx, int32_t lane, int32_t level, uint8_t *out, int64_t cap)
 {
     ENGINE();

@@ -135,18 +135,17 @@ __device__ static void icp_search(const double *src, int n, const double *dst, i
     }
 }
 
-__global__ __launch_bounds__(ICP_THREADS) void icp2d_kernel(IcpArgs A)
+// one pair, by the whole workgroup: src (n points) onto dst (m points) from the pose init[0 .. 3), partner = n ints of global scratch
+// that no other workgroup touches -> pose[0 .. 3), *stats (written by lane 0).  The LDS is declared here, once for every kernel that
+// runs a pair: the search then reads its tile at an address the compiler knows (ds_read_b128), not through a generic pointer
+__device__ static void icp2d_pair(const double *__restrict__ src, int n, const double *__restrict__ dst, int m, int32_t *__restrict__ partner,
+                                  const double *__restrict__ init, const roam_icp_opts &o, double *__restrict__ pose,
+                                  roam_icp_stats *__restrict__ stats)
 {
     __shared__ float4 tile[ICP_TILE / 2];
     __shared__ double red[ICP_WAVES][ICP_NRED];
-    const int p = blockIdx.x;
-    const int64_t s0 = (int64_t)A.src_off[p] - A.src_off[0], d0 = (int64_t)A.dst_off[p] - A.dst_off[0];
-    const int n = A.src_off[p + 1] - A.src_off[p], m = A.dst_off[p + 1] - A.dst_off[p];
-    const double *src = A.src + 2 * s0, *dst = A.dst + 2 * d0;
-    int32_t *partner = A.partner + s0;
-    const roam_icp_opts o = A.o;
     const double inf = std::numeric_limits<double>::infinity();
-    double th = A.init[3 * p], tx = A.init[3 * p + 1], ty = A.init[3 * p + 2];
+    double th = init[0], tx = init[1], ty = init[2];
     int status = ROAM_ICP_MAX_ITERATIONS, iterations = 0, n_last = 0;
     double v[ICP_NRED];
 
@@ -215,17 +214,36 @@ __global__ __launch_bounds__(ICP_THREADS) void icp2d_kernel(IcpArgs A)
         if (n_in > 0) rms = sqrt(v[1] / v[0]);
     }
     if (threadIdx.x == 0) {
-        A.pose[3 * p] = th;
-        A.pose[3 * p + 1] = tx;
-        A.pose[3 * p + 2] = ty;
+        pose[0] = th;
+        pose[1] = tx;
+        pose[2] = ty;
         roam_icp_stats st;
         st.status = status;
         st.iterations = iterations;
         st.n_pairs_last = n_last;
         st.n_inliers = n_in;
         st.rms = rms;
-        A.stats[p] = st;
+        *stats = st;
     }
+}
+
+__global__ __launch_bounds__(ICP_THREADS) void icp2d_kernel(IcpArgs A)
+{
+    const int p = blockIdx.x;
+    const int64_t s0 = (int64_t)A.src_off[p] - A.src_off[0], d0 = (int64_t)A.dst_off[p] - A.dst_off[0];
+    const int n = A.src_off[p + 1] - A.src_off[p], m = A.dst_off[p + 1] - A.dst_off[p];
+    icp2d_pair(A.src + 2 * s0, n, A.dst + 2 * d0, m, A.partner + s0, A.init + 3 * (int64_t)p, A.o, A.pose + 3 * (int64_t)p, A.stats + p);
+}
+
+// the pairs of the loop database's cloud store.  The partner scratch is per PAIR (p max_points): one stored cloud may be the source of
+// several pairs of a launch - a query against its k candidates - and each workgroup needs partners of its own
+__global__ __launch_bounds__(ICP_THREADS) void icp2d_store_kernel(IcpStoreArgs A)
+{
+    const int p = blockIdx.x;
+    const int si = A.src_index[p], di = A.dst_index[p];
+    const int n = si >= 0 ? A.cloud_n[si] : 0, m = di >= 0 ? A.cloud_n[di] : 0;
+    const double *src = A.cloud + 2 * (int64_t)(si >= 0 ? si : 0) * A.max_points, *dst = A.cloud + 2 * (int64_t)(di >= 0 ? di : 0) * A.max_points;
+    icp2d_pair(src, n, dst, m, A.partner + (int64_t)p * A.max_points, A.init + 3 * (int64_t)p, A.o, A.pose + 3 * (int64_t)p, A.stats + p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
@@ -241,19 +259,9 @@ static int64_t icp_chunk_limit()
 
 static const roam_icp_opts ICP_DEFAULTS = {3.0, 0.5, 0.8, 40, 1e-4, 1e-5, 3};
 
-// everything roam_icp2d_batch refuses, before any device call
-static int32_t icp_check(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off, const double *src, const int32_t *dst_off, const double *dst,
-                         const double *init, const roam_icp_opts *o, const double *pose_out, const roam_icp_stats *stats)
+// the options' limits, shared with the loop database's verification
+static int32_t icp_check_opts(roam_ctx *ctx, const roam_icp_opts *o)
 {
-    if (!src_off || !src || !dst_off || !dst || !init || !pose_out || !stats) {
-        ROAM_SET_ERR(ctx, "icp2d: %s is null", !src_off ? "src_off" : !src ? "src" : !dst_off ? "dst_off" : !dst ? "dst" : !init ? "init"
-                                               : !pose_out ? "pose_out" : "stats");
-        return ROAM_E_ARG;
-    }
-    if (n_pairs < 1 || n_pairs > ROAM_ICP_MAX_PAIRS) {
-        ROAM_SET_ERR(ctx, "icp2d: n_pairs in [1, %d], not %d", ROAM_ICP_MAX_PAIRS, n_pairs);
-        return ROAM_E_ARG;
-    }
     if (!(std::isfinite(o->gate_start) && std::isfinite(o->gate_end) && o->gate_end > 0.0 && o->gate_end <= o->gate_start &&
           o->gate_start <= ROAM_ICP_MAX_COORD)) {
         ROAM_SET_ERR(ctx, "icp2d: gates 0 < gate_end <= gate_start <= %g, not %g and %g", ROAM_ICP_MAX_COORD, o->gate_end, o->gate_start);
@@ -269,6 +277,30 @@ static int32_t icp_check(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off,
         ROAM_SET_ERR(ctx, "icp2d: eps_trans and eps_rot >= 0, not %g and %g", o->eps_trans, o->eps_rot);
         return ROAM_E_ARG;
     }
+    return ROAM_OK;
+}
+
+int32_t roam_icp_resolve_opts(roam_ctx *ctx, const roam_icp_opts *opts, roam_icp_opts *o)
+{
+    *o = opts ? *opts : ICP_DEFAULTS;
+    return icp_check_opts(ctx, o);
+}
+
+// everything roam_icp2d_batch refuses, before any device call
+static int32_t icp_check(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off, const double *src, const int32_t *dst_off, const double *dst,
+                         const double *init, const roam_icp_opts *o, const double *pose_out, const roam_icp_stats *stats)
+{
+    if (!src_off || !src || !dst_off || !dst || !init || !pose_out || !stats) {
+        ROAM_SET_ERR(ctx, "icp2d: %s is null", !src_off ? "src_off" : !src ? "src" : !dst_off ? "dst_off" : !dst ? "dst" : !init ? "init"
+                                               : !pose_out ? "pose_out" : "stats");
+        return ROAM_E_ARG;
+    }
+    if (n_pairs < 1 || n_pairs > ROAM_ICP_MAX_PAIRS) {
+        ROAM_SET_ERR(ctx, "icp2d: n_pairs in [1, %d], not %d", ROAM_ICP_MAX_PAIRS, n_pairs);
+        return ROAM_E_ARG;
+    }
+    const int32_t ro = icp_check_opts(ctx, o);
+    if (ro != ROAM_OK) return ro;
     for (int side = 0; side < 2; ++side) {
         const int32_t *off = side ? dst_off : src_off;
         const double *xy = side ? dst : src;
@@ -331,6 +363,12 @@ static int32_t icp_stage(roam_ctx *ctx, int p0, int p1, const int32_t *src_off, 
 static hipError_t icp_launch(hipStream_t st, const IcpArgs &A, int np)
 {
     hipLaunchKernelGGL(icp2d_kernel, dim3(np), dim3(ICP_THREADS), 0, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_icp2d_store(hipStream_t st, const IcpStoreArgs &A, int np)
+{
+    hipLaunchKernelGGL(icp2d_store_kernel, dim3(np), dim3(ICP_THREADS), 0, st, A);
     return hipGetLastError();
 }
 

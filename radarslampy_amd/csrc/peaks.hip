@@ -310,8 +310,8 @@ __global__ __launch_bounds__(PK_T) void peaks_gather_kernel(const uint16_t *__re
     }
 }
 
-hipError_t launch_peaks(hipStream_t st, PeakSrc src, int B, int rows, int cols, uint16_t *row_stage,
-                        int stage_cap, int32_t *row_count, int32_t *out, int32_t cap, int32_t *n_out)
+// the row kernel alone: row_stage / row_count of B scans, for a caller with a gather of its own (loopclosure.hip's cloud store)
+hipError_t launch_peaks_rows(hipStream_t st, PeakSrc src, int B, int rows, int cols, uint16_t *row_stage, int stage_cap, int32_t *row_count)
 {
     const int half = (cols + 1) / 2;
     size_t lds = sizeof(float) * (size_t)(cols + cols / 8 + 2 + 2 * half) + sizeof(uint16_t) * (size_t)half + 16;
@@ -323,7 +323,13 @@ hipError_t launch_peaks(hipStream_t st, PeakSrc src, int B, int rows, int cols, 
         hipLaunchKernelGGL(peaks_rows_kernel<true>, grid, block, lds, st, src, rows, cols, row_stage, stage_cap, row_count);
     else
         hipLaunchKernelGGL(peaks_rows_kernel<false>, grid, block, lds, st, src, rows, cols, row_stage, stage_cap, row_count);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_peaks(hipStream_t st, PeakSrc src, int B, int rows, int cols, uint16_t *row_stage,
+                        int stage_cap, int32_t *row_count, int32_t *out, int32_t cap, int32_t *n_out)
+{
+    hipError_t e = launch_peaks_rows(st, src, B, rows, cols, row_stage, stage_cap, row_count);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(peaks_gather_kernel, dim3(B), dim3(PK_T), sizeof(int) * (size_t)(rows + 1), st,
                        row_stage, stage_cap, row_count, rows, out, cap, n_out);

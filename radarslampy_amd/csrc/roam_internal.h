@@ -83,6 +83,8 @@ struct PeakSrc {
 // row_stage: B x rows x stage_cap u16; row_count: B x rows i32; out: B x cap x 2 i32; n_out: B i32
 hipError_t launch_peaks(hipStream_t st, PeakSrc src, int B, int rows, int cols, uint16_t *row_stage,
                         int stage_cap, int32_t *row_count, int32_t *out, int32_t cap, int32_t *n_out);
+// launch_peaks' first kernel alone: row_stage / row_count and nothing else
+hipError_t launch_peaks_rows(hipStream_t st, PeakSrc src, int B, int rows, int cols, uint16_t *row_stage, int stage_cap, int32_t *row_count);
 // launch_peaks' second kernel alone (row_stage / row_count already filled)
 hipError_t launch_peaks_gather(hipStream_t st, int B, int rows, const uint16_t *row_stage, int stage_cap, const int32_t *row_count,
                                int32_t *out, int32_t cap, int32_t *n_out);
@@ -219,9 +221,28 @@ __host__ __device__ inline double roam_normalize_angle(double th)
 }
 
 // loopclosure.hip: roam_engine_loop_db_add (engine_lanes.hip) after its own checks (the engine, the pool indices): describe n resident u8
-// records of `cols` range bins (pool_idx: host) and append them to db, on ctx->stream, blocking.  after (optional): an event the
-// stream waits for once the arguments have passed - the pool's pending uploads.  time_ms (optional): nothing is appended; time_reps
-// launches of the describing kernel into the free entries are timed with events (roam_engine_time_loop_describe)
+// records of `cols` range bins (pool_idx: host) and append them to db, on ctx->stream, blocking; a database that keeps clouds gets the
+// records' peak clouds too.  after (optional): an event the stream waits for once the arguments have passed - the pool's pending
+// uploads.  time_ms (optional): nothing is appended; time_reps launches of the describing kernel into the free entries are timed with
+// events (roam_engine_time_loop_describe).  cloud_ms (optional, two floats): likewise the peak row kernel and the cloud gather kernel
+// (roam_engine_time_loop_cloud)
 int32_t roam_loop_db_add_records(roam_ctx *ctx, roam_loop_db *db, const uint8_t *pool, int64_t rec_bytes, int64_t row_stride, int32_t payload_off,
                                  int32_t rows, int32_t cols, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
-                                 int32_t *first_index_out, hipEvent_t after, int32_t time_reps, float *time_ms);
+                                 int32_t *first_index_out, hipEvent_t after, int32_t time_reps, float *time_ms, float *cloud_ms = nullptr);
+
+// icp.hip, for the loop database's verification (loopclosure.hip).  Pair p aligns the stored cloud of entry src_index[p] to that of
+// entry dst_index[p]: slot e = cloud + 2 e max_points, cloud_n[e] points; an index of -1 is an empty cloud.  partner: np x max_points
+struct IcpStoreArgs {
+    const double *cloud;
+    const int32_t *cloud_n;
+    int32_t max_points;
+    const int32_t *src_index, *dst_index;         // np each
+    const double *init;                           // np x 3
+    int32_t *partner;
+    double *pose;                                 // np x 3
+    roam_icp_stats *stats;
+    roam_icp_opts o;
+};
+hipError_t launch_icp2d_store(hipStream_t st, const IcpStoreArgs &A, int np);
+// opts (NULL: the defaults) -> *o, checked as roam_icp2d_batch checks them
+int32_t roam_icp_resolve_opts(roam_ctx *ctx, const roam_icp_opts *opts, roam_icp_opts *o);

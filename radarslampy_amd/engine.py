@@ -298,7 +298,7 @@ class Engine:
     def loop_db_add(self, detector, pool_idx, clip_px=None, floor_code=None):
         """describe resident scans as scan contexts and store them in a LoopClosure.LoopDetector (or an _ffi.LoopDb) without moving
         image data (roam_engine_loop_db_add): the u8 form, mean of max(code - floor_code, 0) / 255 over the bins -> the index of the
-        first new entry.  clip_px / floor_code default to the detector's.  Runs behind the steps enqueued so far, blocks until done and
+        first new entry; a detector that keeps clouds gets the scans' peak clouds too.  clip_px / floor_code default to the detector's.  Runs behind the steps enqueued so far, blocks until done and
         leaves the engine's state alone.  ValueError before any device call for a bad index list, clip or floor."""
         db = getattr(detector, "db", detector)
         idx = np.ascontiguousarray(pool_idx, np.int32).ravel()
@@ -315,6 +315,17 @@ class Engine:
         self.ctx.check(self.lib.roam_engine_loop_db_add(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), int(clip_px or 0), int(floor_code),
                                                         C.byref(first)))
         return first.value
+
+    def time_loop_cloud(self, detector, pool_idx, reps=20):
+        """(peak row kernel ms, cloud gather kernel ms) per launch of the cloud build of these resident scans into the free entries of a
+        cloud-keeping LoopDetector / LoopDb; nothing is appended (roam_engine_time_loop_cloud)"""
+        db = getattr(detector, "db", detector)
+        idx = np.ascontiguousarray(pool_idx, np.int32).ravel()
+        if len(idx) < 1 or idx.min() < 0 or idx.max() >= self.pool_scans:
+            raise ValueError(f"time_loop_cloud: at least one pool index, all in [0, {self.pool_scans})")
+        a, b = C.c_float(0), C.c_float(0)
+        self.ctx.check(self.lib.roam_engine_time_loop_cloud(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), int(reps), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
 
     def lane_image(self, lane: int, level: int = 0):
         W = 2 * (self.cfg.clip // 2)
