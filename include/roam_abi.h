@@ -451,7 +451,7 @@ int32_t roam_icp2d_batch(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off 
 int32_t roam_time_icp2d_batch(roam_ctx *ctx, int32_t n_pairs, const int32_t *src_off, const double *src, const int32_t *dst_off,
                               const double *dst, const double *init, const roam_icp_opts *opts, int32_t reps, float *ms_per_rep);
 
-/* ---- loop database with resident peak clouds: verification from the store (csrc/loopclosure.hip, csrc/icp.hip).  PARITY UNPINNED as
+/* ---- loop database with resident peak clouds: verification from the store (csrc/loop_cloud.hip, csrc/loop_verify.hip, csrc/icp.hip).  PARITY UNPINNED as
  * the two sections above; the contract is tests/loop_cloud_model.py on top of tests/icp_model.py.
  * A database that keeps clouds stores beside every descriptor the scan's polar peaks in metres.  The peaks are those of
  * roam_peaks_record_u8 / roam_peaks_polar_f32 in their azimuth-major order (a record: the engine's cfg.clip columns; an image: all its

@@ -1,4 +1,4 @@
-"""Times of the loop-closure candidates (csrc/loopclosure.hip) on the GPU, each workload in a process of its own under its own
+"""Times of the loop-closure candidates (csrc/loop_describe.hip, csrc/loop_query.hip) on the GPU, each workload in a process of its own under its own
 `timeout`; the first that fails ends the run.  HIP events around repeated launches on the context's stream, two warm launches first
 (roam_engine_time_loop_describe, roam_time_loop_db_query):
 

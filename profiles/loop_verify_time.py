@@ -1,4 +1,4 @@
-"""Times of the loop database's resident peak clouds and of the verification that runs from them (csrc/loopclosure.hip, csrc/icp.hip) on
+"""Times of the loop database's resident peak clouds and of the verification that runs from them (csrc/loop_cloud.hip, csrc/loop_verify.hip, csrc/icp.hip) on
 the GPU, each workload in a process of its own under its own `timeout`; the first that fails ends the run.  The world is the eleven-scan
 revisit world of tests/scan_context_cases.py (eight places, three revisits, Oxford records) in an engine's pool, described into a
 LoopDetector(keepClouds=True) by Engine.loop_db_add; 60 x 20 descriptors, every peak kept (about 4 500 per scan), default ICP options.

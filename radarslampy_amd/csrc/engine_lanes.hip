@@ -1,6 +1,7 @@
 // Lane set-up and read-back of the engine (engine.hip): a lane's first pyramid, pose and features (given, or detected on the device),
 // what a lane holds now, and the pass-through entry points that run another unit's work on the scans resident in the pool.
 #include "engine.h"
+#include "loop.h"
 
 // features -> keyframe locals: undistort(velocity, (pts - center) * m/px) (Mapping.py:59-66)
 __global__ void lane_kf_reset_kernel(const float *__restrict__ feat, int K, const double *__restrict__ vel,
@@ -216,15 +217,20 @@ int32_t roam_engine_fmt_register(roam_ctx *ctx, int32_t n, const int32_t *prev_p
     return roam_fmt_register_run(ctx, in, n, e->cfg.rows, clip, R, Rc, out6, nullptr);
 }
 
+// the pool as the loop database's record entries read it.  As roam_engine_fmt_rotation: they run behind every step enqueued so far and
+// the uploads of the pool, the engine's bookkeeping untouched
+static LoopPool loop_pool(const roam_ctx *ctx, const Engine *e)
+{
+    return {e->pool, (int64_t)e->rec_bytes, e->cfg.stride, e->cfg.payload_off, e->cfg.rows, e->cfg.clip, e->uploads_pending ? ctx->ev_up : nullptr};
+}
+
 int32_t roam_engine_loop_db_add(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
                                 int32_t *first_index_out)
 {
     ENGINE();
     ARG_CHECK(ctx, db && n >= 1 && pool_idx);
     for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
-    // as roam_engine_fmt_rotation: behind every step enqueued so far and the uploads of the pool, the engine's bookkeeping untouched
-    return roam_loop_db_add_records(ctx, db, e->pool, (int64_t)e->rec_bytes, e->cfg.stride, e->cfg.payload_off, e->cfg.rows, e->cfg.clip, n,
-                                    pool_idx, clip_px, floor_code, first_index_out, e->uploads_pending ? ctx->ev_up : nullptr, 0, nullptr);
+    return loop_records_append(ctx, db, loop_pool(ctx, e), n, pool_idx, clip_px, floor_code, first_index_out);
 }
 
 int32_t roam_engine_time_loop_describe(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
@@ -233,8 +239,7 @@ int32_t roam_engine_time_loop_describe(roam_ctx *ctx, roam_loop_db *db, int32_t 
     ENGINE();
     ARG_CHECK(ctx, db && n >= 1 && pool_idx && ms_per_rep);
     for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
-    return roam_loop_db_add_records(ctx, db, e->pool, (int64_t)e->rec_bytes, e->cfg.stride, e->cfg.payload_off, e->cfg.rows, e->cfg.clip, n,
-                                    pool_idx, clip_px, floor_code, nullptr, e->uploads_pending ? ctx->ev_up : nullptr, reps, ms_per_rep);
+    return loop_records_time_describe(ctx, db, loop_pool(ctx, e), n, pool_idx, clip_px, floor_code, reps, ms_per_rep);
 }
 
 int32_t roam_engine_time_loop_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t reps, float *rows_ms,
@@ -244,8 +249,7 @@ int32_t roam_engine_time_loop_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t n, 
     ARG_CHECK(ctx, db && n >= 1 && pool_idx && rows_ms && gather_ms);
     for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
     float ms[2] = {0, 0};
-    const int32_t rc = roam_loop_db_add_records(ctx, db, e->pool, (int64_t)e->rec_bytes, e->cfg.stride, e->cfg.payload_off, e->cfg.rows, e->cfg.clip,
-                                                n, pool_idx, 0, 0, nullptr, e->uploads_pending ? ctx->ev_up : nullptr, reps, nullptr, ms);
+    const int32_t rc = loop_records_time_cloud(ctx, db, loop_pool(ctx, e), n, pool_idx, reps, ms);
     *rows_ms = ms[0];
     *gather_ms = ms[1];
     return rc;

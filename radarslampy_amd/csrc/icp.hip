@@ -28,9 +28,8 @@
 //
 // Budget: 32 KiB of LDS for the tile plus 320 bytes for the sums; ICP_IC = 4 points (8 float32 + 4 best + 4 index) per lane keep
 // the search in registers.
-#include "roam_internal.h"
+#include "loop.h"
 #include <math.h>
-#include <stdlib.h>
 #include <limits>
 
 #define ICP_THREADS 512
@@ -247,16 +246,6 @@ __global__ __launch_bounds__(ICP_THREADS) void icp2d_store_kernel(IcpStoreArgs A
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static int64_t icp_chunk_limit()
-{
-    int64_t limit = ICP_CHUNK_BYTES;
-    if (const char *ce = getenv("ROAM_ICP_CHUNK_BYTES")) {
-        const long long c = atoll(ce);
-        if (c >= 1 && c < limit) limit = c;
-    }
-    return limit;
-}
-
 static const roam_icp_opts ICP_DEFAULTS = {3.0, 0.5, 0.8, 40, 1e-4, 1e-5, 3};
 
 // the options' limits, shared with the loop database's verification
@@ -381,7 +370,7 @@ extern "C" int32_t roam_icp2d_batch(roam_ctx *ctx, int32_t n_pairs, const int32_
     if (rc != ROAM_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    const int64_t limit = icp_chunk_limit();
+    const int64_t limit = roam_chunk_limit("ROAM_ICP_CHUNK_BYTES", ICP_CHUNK_BYTES);
     for (int p0 = 0; p0 < n_pairs;) {
         int p1 = p0 + 1;                          // a pair is at most 8192 + 8192 points: it always fits
         while (p1 < n_pairs && icp_pairs_bytes(src_off, dst_off, p0, p1 + 1) <= limit) ++p1;
@@ -416,18 +405,5 @@ extern "C" int32_t roam_time_icp2d_batch(roam_ctx *ctx, int32_t n_pairs, const i
     IcpArgs A;
     const int32_t rs = icp_stage(ctx, 0, n_pairs, src_off, src, dst_off, dst, init, o, &A);
     if (rs != ROAM_OK) return rs;
-    hipEvent_t e0, e1;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    HIP_TRY(ctx, hipEventCreate(&e1));
-    for (int i = 0; i < 2; ++i) HIP_TRY(ctx, icp_launch(st, A, n_pairs));
-    HIP_TRY(ctx, hipEventRecord(e0, st));
-    for (int i = 0; i < reps; ++i) HIP_TRY(ctx, icp_launch(st, A, n_pairs));
-    HIP_TRY(ctx, hipEventRecord(e1, st));
-    HIP_TRY(ctx, hipEventSynchronize(e1));
-    float ms = 0;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_rep = ms / reps;
-    HIP_TRY(ctx, hipEventDestroy(e0));
-    HIP_TRY(ctx, hipEventDestroy(e1));
-    return ROAM_OK;
+    return roam_time_launches(ctx, st, reps, ms_per_rep, [&] { return icp_launch(st, A, n_pairs); });
 }

@@ -1,0 +1,145 @@
+// loop.h - what the units of the place-recognition family share: the loop database, its scan-context descriptors, its resident peak
+// clouds and the verification that runs from them; internal.  Which unit owns what:
+//   loop_describe.hip  scan_context_kernel, scan_context_norm_kernel; the geometry and float32 argument checks;
+//                      roam_scan_context_plan, roam_scan_context_f32; host float32 images in chunks (sc_describe_host_f32)
+//   loop_db.hip        the database's lifetime (create, destroy, count, get) and its three adds: add_f32, add_desc and the engine's
+//                      resident records (loop_records_prepare / _append / _time_describe / _time_cloud)
+//   loop_query.hip     loop_distance_kernel, loop_select_kernel; the query pass (LoopQueryBufs and the loop_query_* steps);
+//                      roam_loop_db_query, roam_time_loop_db_query
+//   loop_cloud.hip     cloud_gather_kernel, the row staging and the cloud build; roam_polar_cloud_table, roam_loop_db_keep_clouds,
+//                      set_cloud, get_cloud, cloud_counts
+//   loop_verify.hip    loop_pairs_kernel, the pair scratch and staging; roam_loop_db_verify, roam_time_loop_db_verify,
+//                      roam_loop_db_query_verify
+//   icp.hip            the ICP of a pair of stored clouds (icp2d_store_kernel), which loop_verify.hip launches
+// engine_lanes.hip describes the engine's pool (LoopPool) and calls the record entries.  The reference has no place recognition (a
+// commented-out "import m2dp" at Mapping.py:7 and an unused Keyframe.pointCloud at :61-62), so parity is unpinned: the contracts are
+// tests/scan_context_model.py and tests/loop_cloud_model.py.
+#pragma once
+#include "roam_internal.h"
+
+#define LOOP_UNIT __attribute__((visibility("hidden")))      // host functions that cross a unit, kept out of the library's symbol table
+#define LOOP_TRY(call) do { const int32_t rc_ = (call); if (rc_ != ROAM_OK) return rc_; } while (0)
+
+#define SC_THREADS 256
+#define SC_QW 4                                  // queries per wave
+#define SC_QB (SC_QW * (SC_THREADS / 64))        // queries per workgroup
+#define SC_LDS_BYTES 32768                       // the doubled candidate of one phase
+#define SC_DB_BYTES ((int64_t)2000 << 20)        // a database, and the scratch of one launch, as in the other batched stages
+#define SC_CHUNK_ENV "ROAM_LOOP_CHUNK_BYTES"     // the tests' smaller launch scratch (roam_chunk_limit): where a batch is cut, nothing else
+#define SC_MAX_ROWS 65536
+
+struct roam_loop_db {
+    int S = 0, R = 0, Rp = 0, capacity = 0, count = 0;
+    float *desc = nullptr;       // capacity x S x R
+    double *nrm = nullptr;       // capacity x S x Rp: normalised columns, zero for an invalid sector and in the padding
+    int32_t *valid = nullptr;    // capacity x S
+    // the peak clouds (roam_loop_db_keep_clouds): cloud_rows = 0 when the database keeps none
+    int cloud_rows = 0, max_points = 0, point_stride = 0;
+    double res = 0.0;            // metres per range bin
+    double *cloud = nullptr;     // capacity x max_points x 2, metres
+    int32_t *cloud_n = nullptr, *cloud_peaks = nullptr;      // capacity each: the points stored, the scan's full peak count
+    double *trig = nullptr;      // cos(phi_t), t < cloud_rows, then sin(phi_t)
+    std::vector<int32_t> h_n, h_peaks;                       // host mirror of the two counts, kept by the blocking entries
+};
+
+// image z of a launch: base + (index ? index[z] : z) * image_stride (+ payload_off for u8 records); strides in elements
+struct ScSrc {
+    const void *base;
+    int64_t image_stride, row_stride;
+    int32_t payload_off;
+    const int32_t *index;
+};
+
+#define SC_FAIL(err, cap, ...)                              \
+    do {                                                    \
+        if (err) snprintf(err, cap, __VA_ARGS__);           \
+        return ROAM_E_ARG;                                  \
+    } while (0)
+
+// ---- loop_describe.hip
+// the checks of the geometry, shared by every describing entry -> the clip
+LOOP_UNIT int32_t sc_check_geometry(char *err, size_t cap, int32_t rows, int32_t cols, int32_t clip_px, int32_t sectors, int32_t rings, int *clip_out);
+LOOP_UNIT int32_t sc_check_f32_args(roam_ctx *ctx, const float *polar, int32_t n, int32_t rows, int32_t cols, int64_t row_stride,
+                                    int64_t image_stride, int32_t clip_px, int32_t sectors, int32_t rings, double floor, int *clip);
+// n images -> rows of desc / nrm / valid starting at entry `first` (nrm / valid may be null)
+LOOP_UNIT hipError_t sc_launch_describe(hipStream_t st, bool u8, const ScSrc &src, int n, int rows, int clip, int S, int R, double floor_v,
+                                        int floor_code, float *desc, double *nrm, int32_t *valid, int64_t first);
+// the n descriptors already in db->desc from entry `first` on -> their nrm / valid
+LOOP_UNIT hipError_t sc_launch_norm(hipStream_t st, const roam_loop_db *db, int64_t first, int n);
+// host float32 images in chunks under the scratch limit: upload the clipped columns tightly, describe into desc (+ nrm, valid) from
+// entry `first` on.  cloud_db (optional, a database that keeps clouds; cols = the images' full width): all the columns are uploaded,
+// and the images' peak clouds go to the entries from `first` on as well
+LOOP_UNIT int32_t sc_describe_host_f32(roam_ctx *ctx, const float *polar, int n, int rows, int64_t row_stride, int64_t image_stride, int clip,
+                                       int S, int R, double floor_v, float *desc, double *nrm, int32_t *valid, int64_t first,
+                                       const roam_loop_db *cloud_db = nullptr, int cols = 0);
+
+// ---- loop_cloud.hip
+// bytes of row staging one scan of `cols` range bins takes (row_stage + row_count)
+static inline int64_t sc_stage_bytes(int rows, int cols) { return (int64_t)rows * ((cols + 1) / 2) * sizeof(uint16_t) + (int64_t)rows * sizeof(int32_t); }
+// the staging of nb scans (taken from the scratch slots S_TMP0 / S_TMP1, which no enqueued engine step reads: a step owns its buffers)
+LOOP_UNIT int32_t sc_cloud_stage(roam_ctx *ctx, int rows, int cols, int nb, uint16_t **stage, int32_t **rcount);
+LOOP_UNIT hipError_t sc_launch_cloud_gather(hipStream_t st, const roam_loop_db *db, int nb, const uint16_t *stage, int stage_cap, const int32_t *rcount,
+                                            int64_t first);
+// the clouds of the nb scans of `ps` (cols range bins each) -> the entries from `first` on; enqueued, not awaited
+LOOP_UNIT int32_t sc_build_clouds(roam_ctx *ctx, const roam_loop_db *db, const PeakSrc &ps, int nb, int cols, int64_t first);
+// what an add to a cloud-keeping database refuses beyond the descriptor's checks
+LOOP_UNIT int32_t sc_check_cloud_add(roam_ctx *ctx, const roam_loop_db *db, int rows, int cols);
+// the end of a blocking add of n entries from `first` on: their counts to the host mirror; waits for the stream
+LOOP_UNIT int32_t sc_mirror_counts(roam_ctx *ctx, roam_loop_db *db, int64_t first, int n);
+
+// ---- loop_db.hip: resident u8 records, for engine_lanes.hip after its own checks (the engine, the pool indices)
+struct LoopPool {
+    const uint8_t *pool;         // pool_scans records of rec_bytes
+    int64_t rec_bytes, row_stride;
+    int32_t payload_off, rows, clip;         // clip: the range bins a record holds
+    hipEvent_t pending;          // the pool's pending uploads (null: none): the stream waits for it once the arguments have passed
+};
+// Each entry first checks (db, the geometry, floor_code, the clouds, the room for n entries; a timing entry then its reps) and only
+// then enqueues: the wait for the pool's uploads and the upload of pool_idx (host, n indices the caller has checked).
+// describe the records and append them to db, blocking; a database that keeps clouds gets the records' peak clouds too
+LOOP_UNIT int32_t loop_records_append(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
+                                      int32_t floor_code, int32_t *first_index_out);
+// nothing is appended: `reps` launches of the describing kernel into the free entries, timed (roam_time_launches)
+LOOP_UNIT int32_t loop_records_time_describe(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
+                                             int32_t floor_code, int32_t reps, float *ms_per_rep);
+// likewise the two kernels of the cloud build, each alone: ms[0] the peak row kernel, ms[1] the cloud gather
+LOOP_UNIT int32_t loop_records_time_cloud(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t reps,
+                                          float *ms);
+
+// ---- loop_query.hip: the query pass of one chunk of nq queries at k candidates each, shared with roam_loop_db_query_verify
+LOOP_UNIT int32_t sc_check_query(roam_ctx *ctx, const roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index,
+                                 int32_t k, double max_distance);
+struct LoopQueryBufs {
+    double *d_dist;              // nq x count  (S_TMP0)
+    int32_t *d_shift;            // nq x count  (S_TMP1)
+    int32_t *d_q, *d_qmax;       // nq each, one take of 2 nq: the queries' indices, their clamped max_index  (S_IN1)
+    int32_t *d_ci;               // nq x k: the candidates' indices, distances and shifts  (S_OUT0, S_OUT1, S_OUT2)
+    double *d_cd;
+    int32_t *d_cs;
+};
+// max_index clamped to [0, count]
+LOOP_UNIT std::vector<int32_t> loop_query_clamp(const roam_loop_db *db, int32_t n_query, const int32_t *max_index);
+// take the scratch of the chunk and upload its nq indices and clamped maxima (host pointers at the chunk's first query)
+LOOP_UNIT int32_t loop_query_stage(roam_ctx *ctx, const roam_loop_db *db, int nq, int k, const int32_t *query_index, const int32_t *qmax, LoopQueryBufs *b);
+// distance, then selection.  every_pair: the distance of every (query, entry), not only of the entries below the query's maximum - what
+// the dist_full / shift_full outputs want
+LOOP_UNIT int32_t loop_query_enqueue(roam_ctx *ctx, const roam_loop_db *db, const LoopQueryBufs &b, int nq, int k, double max_distance, bool every_pair);
+// the three candidate downloads
+LOOP_UNIT int32_t loop_query_download(roam_ctx *ctx, const LoopQueryBufs &b, int nq, int k, int32_t *cand_index, double *cand_dist, int32_t *cand_shift);
+
+// ---- icp.hip, for the verification (loop_verify.hip).  Pair p aligns the stored cloud of entry src_index[p] to that of entry
+// dst_index[p]: slot e = cloud + 2 e max_points, cloud_n[e] points; an index of -1 is an empty cloud.  partner: np x max_points
+struct IcpStoreArgs {
+    const double *cloud;
+    const int32_t *cloud_n;
+    int32_t max_points;
+    const int32_t *src_index, *dst_index;         // np each
+    const double *init;                           // np x 3
+    int32_t *partner;
+    double *pose;                                 // np x 3
+    roam_icp_stats *stats;
+    roam_icp_opts o;
+};
+LOOP_UNIT hipError_t launch_icp2d_store(hipStream_t st, const IcpStoreArgs &A, int np);
+// opts (NULL: the defaults) -> *o, checked as roam_icp2d_batch checks them
+LOOP_UNIT int32_t roam_icp_resolve_opts(roam_ctx *ctx, const roam_icp_opts *opts, roam_icp_opts *o);

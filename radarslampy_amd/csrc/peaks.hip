@@ -310,7 +310,7 @@ __global__ __launch_bounds__(PK_T) void peaks_gather_kernel(const uint16_t *__re
     }
 }
 
-// the row kernel alone: row_stage / row_count of B scans, for a caller with a gather of its own (loopclosure.hip's cloud store)
+// the row kernel alone: row_stage / row_count of B scans, for a caller with a gather of its own (loop_cloud.hip's cloud store)
 hipError_t launch_peaks_rows(hipStream_t st, PeakSrc src, int B, int rows, int cols, uint16_t *row_stage, int stage_cap, int32_t *row_count)
 {
     const int half = (cols + 1) / 2;

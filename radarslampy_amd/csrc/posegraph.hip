@@ -28,6 +28,7 @@
 #define PG_MAX_ITERATIONS 1000
 #define PG_MAX_TRIALS 1000
 #define PG_CHUNK_BYTES ((int64_t)2000 << 20)     // scratch of one launch, as in the other batched stages
+#define PG_CHUNK_ENV "ROAM_POSE_GRAPH_CHUNK_BYTES"      // the tests' smaller figure
 
 // One graph of a chunk.  i_*: offsets into the chunk's int32 slab, d_*: into its float64 slab; v0 / e0: first vertex / edge of the
 // graph in the chunk's pose and edge arrays
@@ -431,19 +432,9 @@ static int32_t pg_plan_all(char *err, size_t cap, int32_t n_graphs, const int32_
     return ROAM_OK;
 }
 
-// the scratch of one launch: PG_CHUNK_BYTES, or the tests' smaller figure from ROAM_POSE_GRAPH_CHUNK_BYTES (read per call).  It only
-// decides where a batch is cut; a single graph is refused against PG_CHUNK_BYTES alone and always fits a chunk of its own
-static int64_t pg_chunk_limit()
-{
-    int64_t limit = PG_CHUNK_BYTES;
-    if (const char *ce = getenv("ROAM_POSE_GRAPH_CHUNK_BYTES")) {
-        const long long c = atoll(ce);
-        if (c >= 1 && c < limit) limit = c;
-    }
-    return limit;
-}
-
-// consecutive graphs, as many as stay under the limit (at least one): [begin, end) of the chunk that starts at `begin`, and its bytes
+// consecutive graphs, as many as stay under the limit (at least one): [begin, end) of the chunk that starts at `begin`, and its bytes.
+// The limit is roam_chunk_limit(PG_CHUNK_ENV, PG_CHUNK_BYTES): it only decides where a batch is cut; a single graph is refused against
+// PG_CHUNK_BYTES alone and always fits a chunk of its own
 static int pg_chunk_end(const std::vector<PgGraphPlan> &plans, int begin, int64_t limit, int64_t *bytes)
 {
     int64_t sum = 0;
@@ -465,7 +456,7 @@ extern "C" int32_t roam_pose_graph_plan(int32_t n_graphs, const int32_t *vertex_
     const int32_t rc = pg_plan_all(nullptr, 0, n_graphs, vertex_off, fixed, edge_off, edge_ij, &plans);
     if (rc != ROAM_OK) return rc;
     int64_t worst = 0;
-    const int64_t limit = pg_chunk_limit();
+    const int64_t limit = roam_chunk_limit(PG_CHUNK_ENV, PG_CHUNK_BYTES);
     for (int begin = 0; begin < n_graphs;) {
         int64_t bytes;
         begin = pg_chunk_end(plans, begin, limit, &bytes);
@@ -520,7 +511,7 @@ extern "C" int32_t roam_pose_graph_optimize(roam_ctx *ctx, int32_t n_graphs, con
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    const int64_t limit = pg_chunk_limit();
+    const int64_t limit = roam_chunk_limit(PG_CHUNK_ENV, PG_CHUNK_BYTES);
     for (int begin = 0; begin < n_graphs;) {
         int64_t chunk_bytes;
         const int end = pg_chunk_end(plans, begin, limit, &chunk_bytes);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <vector>
 #include "../../include/roam_abi.h"
@@ -59,6 +60,40 @@ struct roam_ctx {
             return ROAM_E_ARG;                                                              \
         }                                                                                   \
     } while (0)
+
+// the scratch of one launch of a batched stage: cap, or the tests' smaller figure from the environment variable env_name (read per
+// call).  A value in [1, cap) lowers the limit, anything else is ignored.  It only decides where a batch is cut
+static inline int64_t roam_chunk_limit(const char *env_name, int64_t cap)
+{
+    if (const char *ce = getenv(env_name)) {
+        const long long c = atoll(ce);
+        if (c >= 1 && c < cap) return c;
+    }
+    return cap;
+}
+
+// two warm launches on st, then `reps` launches between two events -> milliseconds per launch.  launch() enqueues one and returns its
+// hipError_t.  Both events are destroyed on every path, and the first error is the one reported
+template <typename F>
+static int32_t roam_time_launches(roam_ctx *ctx, hipStream_t st, int reps, float *ms_per_rep, F launch)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    for (int rep = -2; rep < reps && e == hipSuccess; ++rep) {
+        if (rep == 0) e = hipEventRecord(e0, st);
+        if (e == hipSuccess) e = launch();
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e != hipSuccess) { ROAM_SET_ERR(ctx, "timed launches failed: %s", hipGetErrorString(e)); return ROAM_E_HIP; }
+    *ms_per_rep = ms / reps;
+    return ROAM_OK;
+}
 
 // grow-only scratch allocation; returns nullptr on failure (error text set).  A slot that must grow is freed and allocated anew: a
 // pointer taken from a slot is dead after a later, larger take of that slot
@@ -219,30 +254,3 @@ __host__ __device__ inline double roam_normalize_angle(double th)
     if (th < 0) th += 2.0 * M_PI;
     return th - M_PI;
 }
-
-// loopclosure.hip: roam_engine_loop_db_add (engine_lanes.hip) after its own checks (the engine, the pool indices): describe n resident u8
-// records of `cols` range bins (pool_idx: host) and append them to db, on ctx->stream, blocking; a database that keeps clouds gets the
-// records' peak clouds too.  after (optional): an event the stream waits for once the arguments have passed - the pool's pending
-// uploads.  time_ms (optional): nothing is appended; time_reps launches of the describing kernel into the free entries are timed with
-// events (roam_engine_time_loop_describe).  cloud_ms (optional, two floats): likewise the peak row kernel and the cloud gather kernel
-// (roam_engine_time_loop_cloud)
-int32_t roam_loop_db_add_records(roam_ctx *ctx, roam_loop_db *db, const uint8_t *pool, int64_t rec_bytes, int64_t row_stride, int32_t payload_off,
-                                 int32_t rows, int32_t cols, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
-                                 int32_t *first_index_out, hipEvent_t after, int32_t time_reps, float *time_ms, float *cloud_ms = nullptr);
-
-// icp.hip, for the loop database's verification (loopclosure.hip).  Pair p aligns the stored cloud of entry src_index[p] to that of
-// entry dst_index[p]: slot e = cloud + 2 e max_points, cloud_n[e] points; an index of -1 is an empty cloud.  partner: np x max_points
-struct IcpStoreArgs {
-    const double *cloud;
-    const int32_t *cloud_n;
-    int32_t max_points;
-    const int32_t *src_index, *dst_index;         // np each
-    const double *init;                           // np x 3
-    int32_t *partner;
-    double *pose;                                 // np x 3
-    roam_icp_stats *stats;
-    roam_icp_opts o;
-};
-hipError_t launch_icp2d_store(hipStream_t st, const IcpStoreArgs &A, int np);
-// opts (NULL: the defaults) -> *o, checked as roam_icp2d_batch checks them
-int32_t roam_icp_resolve_opts(roam_ctx *ctx, const roam_icp_opts *opts, roam_icp_opts *o);

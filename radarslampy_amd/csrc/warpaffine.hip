@@ -115,20 +115,10 @@ extern "C" int32_t roam_time_warp_affine(roam_ctx *ctx, int32_t n, int32_t rows,
     const double *d_M = nullptr;
     const int32_t rc = wa_upload_matrices(ctx, M, 1, 0, inv, &d_M);
     if (rc != ROAM_OK) return rc;
-    hipEvent_t e0, e1;
-    HIP_TRY(ctx, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); ROAM_SET_ERR(ctx, "hipEventCreate failed"); return ROAM_E_HIP; }
-    for (int rep = -2; rep < reps; rep++) {                 // two warm runs
-        if (rep == 0) (void)hipEventRecord(e0, st);
+    const int32_t rt = roam_time_launches(ctx, st, reps, ms_per_rep, [&] {
         wa_launch(st, d_in, n, rows, cols, d_M, 1, d_out, cols, rows);
-    }
-    (void)hipEventRecord(e1, st);
-    hipError_t e = hipEventSynchronize(e1);                 // (also keeps `inv` alive until its upload is done)
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e == hipSuccess) e = hipGetLastError();
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIP_TRY(ctx, e);
-    *ms_per_rep = ms / reps;
-    return ROAM_OK;
+        return hipGetLastError();
+    });
+    if (rt != ROAM_OK) (void)hipStreamSynchronize(st);      // `inv` lives until its upload is done (a timed run has waited already)
+    return rt;
 }

@@ -1,4 +1,4 @@
-"""NumPy model of the loop database's peak-cloud store (csrc/loopclosure.hip, include/roam_abi.h): which peaks of a scan an entry keeps,
+"""NumPy model of the loop database's peak-cloud store (csrc/loop_cloud.hip, include/roam_abi.h): which peaks of a scan an entry keeps,
 and how a kept peak becomes metres.  PARITY UNPINNED - the reference stores Keyframe.pointCloud and never reads it.
 
 Selection.  A scan has N peaks in azimuth-major order.  step = max(point_stride, ceil(N / max_points)); the entry keeps the peaks

@@ -1,4 +1,4 @@
-"""The contract of the loop-closure candidates (radarslampy_amd/csrc/loopclosure.hip, radarslampy_amd/LoopClosure.py): the radar scan
+"""The contract of the loop-closure candidates (radarslampy_amd/csrc/loop_describe.hip, loop_query.hip, radarslampy_amd/LoopClosure.py): the radar scan
 context of Kim et al. (the MulRan data set) in NumPy, float64.  Nothing in the reference computes this (Mapping.py:7 is a
 commented-out "import m2dp"), so parity is unpinned and this file is what the device is held to.
 
@@ -124,7 +124,7 @@ LDS_BYTES = 32768
 
 
 def phase_rings(S, R):
-    """rings of one LDS phase of the distance kernel (csrc/loopclosure.hip sc_phase_rings): R padded to a multiple of four, or the
+    """rings of one LDS phase of the distance kernel (csrc/loop_query.hip sc_phase_rings): R padded to a multiple of four, or the
     largest multiple of four whose doubled candidate (2S + 1 float64 per ring) fits 32 KiB"""
     Rp = (R + 3) & ~3
     return min(Rp, (LDS_BYTES // (8 * (2 * S + 1))) & ~3)

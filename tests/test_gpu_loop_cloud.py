@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the loop database's resident peak clouds and the verification that runs from them (csrc/loopclosure.hip, csrc/icp.hip,
+"""GPU (-m gpu): the loop database's resident peak clouds and the verification that runs from them (csrc/loop_cloud.hip, csrc/loop_verify.hip, csrc/icp.hip,
 radarslampy_amd/LoopClosure.py) against tests/loop_cloud_model.py, the oracle's peak extraction and the existing ICP entry.  Parity is
 unpinned: nothing in the reference computes this.
 
@@ -23,7 +23,7 @@ RES = 0.0432
 LAYOUTS = {(497, 399, 504, 5): (60, 20, 400), (1000, 64, 1000, 0): (16, 8, 0)}      # layout -> (S, R, clip_px) of the descriptor
 SETTINGS = [(8192, 1), (512, 1), (2048, 4)]
 ORDER = [2, 0, 3, 3, 1]
-PAIR_BYTES = 4 * 8192 + 8 + 48 + 24          # device scratch of one stored pair at max_points = 8192 (loopclosure.hip sc_pair_bytes)
+PAIR_BYTES = 4 * 8192 + 8 + 48 + 24          # device scratch of one stored pair at max_points = 8192 (loop_verify.hip sc_pair_bytes)
 
 
 @pytest.fixture(scope="module")
@@ -138,7 +138,7 @@ def test_stored_clouds_from_float32_images(ctx, max_points, stride, monkeypatch)
         assert batch.add_f32(imgs, clip_px) == 0 and plain.add_f32(imgs, clip_px) == 0
         for i in range(n):
             assert single.add_f32(imgs[i], clip_px) == i
-        per = 4 * rows * cols + rows * ((cols + 1) // 2) * 2 + rows * 4       # an image's upload and row staging (loopclosure.hip)
+        per = 4 * rows * cols + rows * ((cols + 1) // 2) * 2 + rows * 4       # an image's upload and row staging (loop_describe.hip)
         monkeypatch.setenv("ROAM_LOOP_CHUNK_BYTES", str(max(1, n // 2) * per + 1))
         assert cut.add_f32(imgs, clip_px) == 0
         monkeypatch.delenv("ROAM_LOOP_CHUNK_BYTES")
@@ -265,8 +265,9 @@ def _cloud_cycle():
     return out
 
 
-def _query_verify_case(ctx, D, queries):
-    """queries: [(tag, query indices, max_index, k, max_distance)]"""
+def _query_verify_case(ctx, D, queries, monkeypatch=None, chunk_bytes=None):
+    """queries: [(tag, query indices, max_index, k, max_distance)].  chunk_bytes: the launch scratch of query_verify alone (the query and
+    the verification it is compared with run uncut)"""
     from radarslampy_amd import _ffi
     from radarslampy_amd.LoopClosure import _yaw
     S = D.shape[1]
@@ -277,7 +278,11 @@ def _query_verify_case(ctx, D, queries):
     for e in range(len(D)):
         db.set_cloud(e, clouds[e % len(clouds)])
     for tag, q, max_index, k, max_distance in queries:
+        if chunk_bytes is not None:
+            monkeypatch.setenv("ROAM_LOOP_CHUNK_BYTES", str(chunk_bytes))
         ci, cd, cs, poses, stats = db.query_verify(q, max_index, k, max_distance)
+        if chunk_bytes is not None:
+            monkeypatch.delenv("ROAM_LOOP_CHUNK_BYTES")
         wi, wd, ws = db.query(q, max_index, k, max_distance)
         assert ci.tobytes() == wi.tobytes() and cd.tobytes() == wd.tobytes() and cs.tobytes() == ws.tobytes(), tag
         used = ci >= 0
@@ -293,10 +298,13 @@ def _query_verify_case(ctx, D, queries):
     db.close()
 
 
-def test_query_verify_is_query_then_verify(ctx):
+def test_query_verify_is_query_then_verify(ctx, monkeypatch):
     E = sc.small_db_case()
     idx = np.arange(5, dtype=np.int32)
     _query_verify_case(ctx, E, [("small k32", idx, np.full(5, 99, np.int32), 32, np.inf), ("small k2 min_gap", idx, idx, 2, np.inf)])
+    # the same under a cut: a query takes 12 bytes per entry and k pairs' scratch, so two queries fit a launch and the five go in three
+    per = 12 * len(E) + 2 * PAIR_BYTES
+    _query_verify_case(ctx, E, [("small k2 min_gap, cut", idx, idx, 2, np.inf)], monkeypatch, 2 * per + 1)
     D, q, _, _ = sc.topk_case()
     _query_verify_case(ctx, D, [(f"topk {tag}", q, mi, k, md) for tag, mi, k, md in sc.topk_queries()])
 

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): loop-closure candidates by scan context (csrc/loopclosure.hip, radarslampy_amd/LoopClosure.py) against the model
+"""GPU (-m gpu): loop-closure candidates by scan context (csrc/loop_describe.hip, csrc/loop_query.hip, radarslampy_amd/LoopClosure.py) against the model
 tests/scan_context_model.py on the inputs of tests/scan_context_cases.py.  Parity is unpinned: nothing in the reference computes this.
 
 Descriptors: the u8 record form (engine pool, the Oxford layout and the 399 x 504 layout) bit for bit the integer model; the float32
