@@ -504,6 +504,58 @@ int32_t roam_engine_time_loop_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t n, 
 int32_t roam_time_loop_db_verify(roam_ctx *ctx, roam_loop_db *db, int32_t n_pairs, const int32_t *src_index, const int32_t *dst_index,
                                  const double *init, const roam_icp_opts *opts, int32_t reps, float *ms_per_rep);
 
+/* ---- origin-shifted scan contexts: revisits metres off the stored place (csrc/loop_offset.hip; the augmentation of Scan Context++,
+ * Kim, Choi, Kim, T-RO 2021).  PARITY UNPINNED as the sections above; the contract is tests/scan_context_offset_model.py.
+ * A scan is described again as seen from n_offsets virtual origins o (metres, the sensor frame x = r cos phi, y = r sin phi; in range
+ * bins o / range_resolution_m, one float64 division).  Every sample (a, c), a < rows, c < clip, sits at its centre: rho = c + 0.5,
+ * (C_a, S_a) = (cos, sin)((2.0 * M_PI * (a + 0.5)) / rows) by the host's libm; x = rho C_a - ox, y = rho S_a - oy, q = x x + y y, each
+ * operation rounded once in float64.  Ring r: E_r^2 <= q < E_{r+1}^2 with roam_scan_context_plan's column edges; q >= clip^2 is dropped.
+ * Sector: b_s = (cos, sin)((2.0 * M_PI * row_edges[s]) / rows) by the host's libm, k_s = b_s.x y - b_s.y x, the lowest s with k_s >= 0
+ * and k_{(s + 1) mod S} < 0; none: dropped.  A bin holds the mean of max(value - floor, 0) over the samples that landed in it (u8: the
+ * exact integer sum / (255.0 count); float32: summed in float64 in one order per (rows, clip, S, R), within 1 float32 ulp of any other and
+ * the same bits whatever the batch and the chunk), 0 when none did.  roam_scan_context_offset_table (host only, no context) returns
+ * the four tables; ROAM_E_ARG outside roam_scan_context_plan's limits or for a null pointer.
+ * Variant 0 of an entry is its plain descriptor, variant a >= 1 the one of offsets_m[a - 1].  roam_loop_db_keep_offsets: once, on an
+ * empty database; every later roam_loop_db_add_f32 / roam_engine_loop_db_add also stores the n_offsets variants of each new entry
+ * (descriptor, normalised columns, validity - as an entry's own), roam_loop_db_add_desc stores them all zero (invalid: distance 1).
+ * ROAM_E_ARG before any device call, the text naming the argument: n_offsets outside [1, ROAM_LOOP_MAX_OFFSETS], an offset that is not
+ * finite, beyond ROAM_ICP_MAX_COORD or (0, 0), range_resolution_m not finite or <= 0, a database that is not empty or keeps offsets
+ * already, capacity x n_offsets variants beyond 2000 MiB.  roam_loop_db_set_variants / _get_variants move the n_offsets descriptors
+ * (n_offsets, S, R) of one stored entry from and to the host (valid_out optional: (n_offsets, S)); ROAM_E_STATE: no offsets kept.
+ * roam_scan_context_offsets_f32: stateless, roam_scan_context_f32's arguments and checks -> desc_out (n, 1 + n_offsets, S, R).
+ * Queries.  D(i, j) = min over the variants a of query i of d(variant a of i, entry j), d as defined above; ties take the lowest a,
+ * the shift is that variant's; candidates by the rule above on D.  roam_loop_db_query_offsets: roam_loop_db_query's arguments and
+ * checks plus cand_offset (n k) and offset_full (optional, (n_query, count)): the winning variant a, 0 for an unused slot.  On a
+ * database without offsets it is roam_loop_db_query with all variants 0, and roam_loop_db_query is unchanged on every database.
+ * Verification.  On a database that keeps offsets roam_loop_db_query_verify runs the query over the variants and seeds slot (i, s)
+ * with (yaw, -R(yaw) o) for the winning offset o (metres; (yaw, 0, 0) for variant 0), still without a host round trip;
+ * roam_loop_db_query_verify_offsets also returns the winning variants.
+ * Measurement, as above: roam_engine_time_loop_offsets - the variants of n resident records into the free entries of db (the clear
+ * of the sums, the binning kernel and the finishing kernel as one launch); roam_time_loop_db_query_offsets - the plain distance
+ * kernel, the variants' distance kernel with the fold, and the selection kernel. */
+#define ROAM_LOOP_MAX_OFFSETS 48
+int32_t roam_scan_context_offset_table(int32_t rows, int32_t sectors, double *cos_row /* rows */, double *sin_row /* rows */,
+                                       double *cos_edge /* S */, double *sin_edge /* S */);
+int32_t roam_loop_db_keep_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n_offsets, const double *offsets_m /* n x 2 */,
+                                  double range_resolution_m);
+int32_t roam_loop_db_set_variants(roam_ctx *ctx, roam_loop_db *db, int32_t index, const float *desc /* n_offsets x S x R */);
+int32_t roam_loop_db_get_variants(roam_ctx *ctx, roam_loop_db *db, int32_t index, float *desc_out, int32_t *valid_out);
+int32_t roam_scan_context_offsets_f32(roam_ctx *ctx, const float *polar, int32_t n, int32_t rows, int32_t cols, int64_t row_stride,
+                                      int64_t image_stride, int32_t clip_px, int32_t sectors, int32_t rings, double floor,
+                                      int32_t n_offsets, const double *offsets_m, double range_resolution_m, float *desc_out);
+int32_t roam_loop_db_query_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index,
+                                   int32_t k, double max_distance, int32_t *cand_index, double *cand_dist, int32_t *cand_shift,
+                                   int32_t *cand_offset, double *dist_full, int32_t *shift_full, int32_t *offset_full);
+int32_t roam_loop_db_query_verify_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index,
+                                          const int32_t *max_index, int32_t k, double max_distance, const roam_icp_opts *opts,
+                                          int32_t *cand_index, double *cand_dist, int32_t *cand_shift, int32_t *cand_offset,
+                                          double *pose_out, roam_icp_stats *stats);
+int32_t roam_engine_time_loop_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px,
+                                      int32_t floor_code, int32_t reps, float *ms_per_rep);
+int32_t roam_time_loop_db_query_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index,
+                                        const int32_t *max_index, int32_t k, double max_distance, int32_t reps, float *plain_ms,
+                                        float *variants_ms, float *select_ms);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous

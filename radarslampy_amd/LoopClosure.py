@@ -7,9 +7,18 @@ of their sector columns, minimised over all circular sector shifts; the best shi
 the candidate ~ 2 pi shift / sectors).  The device compares a query with every stored keyframe at every shift exactly: no ring-key
 tree, no coarse sector-key alignment.
 
-What comes out of LoopDetector are CANDIDATES and a yaw.  The method's reach is short: on the synthetic worlds a revisit 2.5 m off the
-stored place still ranks first but at 0.79 of the next place's distance, and at 5 m it is not recognised (the point reflectors move to
-other rings).
+What comes out of LoopDetector are CANDIDATES and a yaw.  The plain descriptor's reach is short: on the synthetic worlds a revisit
+2.5 m off the stored place still ranks first but at 0.79 of the next place's distance, and at 5 m it is not recognised (the point
+reflectors move to other rings).
+
+Origin offsets (the augmentation of Scan Context++).  LoopDetector(originOffsetsM=offsetGrid(5.0, 2.5)) describes every added scan
+again as seen from 24 virtual origins a lane width apart (csrc/loop_offset.hip; contract tests/scan_context_offset_model.py), keeps
+these variants beside the entry and uses them on the QUERY side: the distance of a pair is the minimum over the query's variants
+against the candidate's plain descriptor, and the winning origin o becomes the translation prior -R(yaw) o of the verification.
+On the synthetic world four revisits 5 m off their place (the next lane), of which the plain descriptor ranks two first by under
+4 %, all rank first (0.018-0.022 against 0.027-0.030 for the best wrong place), the winning origin is within 0.4-1.7 m of the true
+displacement, and the ICP from that seed is accepted within 0.07 m where the plain seed is rejected (docs/PARITY.md).  At 7.5 m and
+at 10 m the 5 m grid puts only two of four first: that is where it still fails.  The candidate side is not augmented.
 
 Verification.  A candidate is verified metrically by a trimmed point-to-point ICP of the two keyframes' polar peak clouds
 (Keyframe.pointCloud, which the reference stores and never reads), seeded with the candidate's yaw: csrc/icp.hip, every pair of a
@@ -39,14 +48,40 @@ def _yaw(shift, sectors):
     return np.where(a > np.pi, a - 2.0 * np.pi, a)
 
 
-def scanContext(polarImg, sectors=60, rings=20, clip_px=None, floor=0.0):
+def offsetGrid(reachM, stepM):
+    """The virtual origins of LoopDetector(originOffsetsM=...): the grid of multiples of stepM within +-reachM on both axes, x-major,
+    without its centre -> (n, 2) float64 metres.  offsetGrid(5.0, 2.5) is the 24 points of a 5 x 5 grid."""
+    for name, v in (("reachM", reachM), ("stepM", stepM)):
+        if not isinstance(v, numbers.Real) or isinstance(v, bool) or not np.isfinite(v) or not v > 0:
+            raise ValueError(f"offsetGrid: {name} finite and > 0, not {v!r}")
+    k = int(np.floor(reachM / stepM + 1e-9))
+    if k < 1 or (2 * k + 1) ** 2 - 1 > _ffi.LOOP_MAX_OFFSETS:
+        raise ValueError(f"offsetGrid: between 1 and {_ffi.LOOP_MAX_OFFSETS} points, not the {(2 * k + 1) ** 2 - 1} of reach {reachM} at step {stepM}")
+    return np.array([(i * float(stepM), j * float(stepM)) for i in range(-k, k + 1) for j in range(-k, k + 1) if (i, j) != (0, 0)], np.float64)
+
+
+def _seed(yaw, offsetM):
+    """the ICP seed of a candidate with the yaw psi and the winning origin offset o (metres): (psi, -R(psi) o)"""
+    yaw, o = np.asarray(yaw, np.float64), np.asarray(offsetM, np.float64)
+    c, s = np.cos(yaw), np.sin(yaw)
+    return np.stack([yaw, -(c * o[..., 0] - s * o[..., 1]), -(s * o[..., 0] + c * o[..., 1])], axis=-1)
+
+
+def scanContext(polarImg, sectors=60, rings=20, clip_px=None, floor=0.0, originOffsetsM=None, rangeResolutionM=RANGE_RESOLUTION_M):
     """The scan-context descriptor of a float32 polar image (azimuth rows x range columns) -> (sectors, rings) float32, or of a 3-D
     batch -> (n, sectors, rings): the mean of max(value - floor, 0) over each bin, sector s = the rows [floor(s rows / sectors),
     floor((s + 1) rows / sectors)), ring r = the columns [floor(r clip / rings), floor((r + 1) clip / rings)), clip = clip_px if
-    0 < clip_px < cols else cols.  floor = 0 is the plain area mean.  ValueError before the device is touched for a bad argument."""
+    0 < clip_px < cols else cols.  floor = 0 is the plain area mean.  ValueError before the device is touched for a bad argument.
+    originOffsetsM (n, 2) metres: -> (1 + n, sectors, rings), or (batch, 1 + n, sectors, rings): the plain descriptor first, then the
+    scan as seen from each of these origins (x = r cos phi, y = r sin phi; tests/scan_context_offset_model.py), rangeResolutionM metres
+    per range bin."""
     a = np.asarray(polarImg)
     _ffi.scan_context_images(a, clip_px, sectors, rings)          # the argument checks come before a device is asked for
     _ffi.scan_context_floor(floor)
+    if originOffsetsM is not None:
+        _ffi.loop_offsets_args(originOffsetsM, rangeResolutionM)
+        out = _ffi.default_context().scan_context_offsets(a, originOffsetsM, rangeResolutionM, sectors, rings, clip_px, floor)
+        return out[0] if a.ndim == 2 else out
     out = _ffi.default_context().scan_context(a, sectors, rings, clip_px, floor)
     return out[0] if a.ndim == 2 else out
 
@@ -73,9 +108,12 @@ class LoopDetector:
     yaw differences."""
 
     def __init__(self, capacity, sectors=60, rings=20, clip_px=None, floor=0.0, min_gap=50, max_distance=0.2, k=8, ctx=None, keepClouds=False,
-                 rows=None, maxPoints=8192, pointStride=1, rangeResolutionM=RANGE_RESOLUTION_M):
+                 rows=None, maxPoints=8192, pointStride=1, rangeResolutionM=RANGE_RESOLUTION_M, originOffsetsM=None):
         """keepClouds: every added scan also stores its polar peak cloud in metres (rows: the azimuths of every scan to come; at most
-        maxPoints points per entry, every step-th peak with step = max(pointStride, ceil(peaks / maxPoints)))"""
+        maxPoints points per entry, every step-th peak with step = max(pointStride, ceil(peaks / maxPoints))).
+        originOffsetsM ((n, 2) metres, n <= 48, e.g. offsetGrid(5.0, 2.5); None: today's behaviour exactly): every added scan is also
+        described as seen from these origins, a query takes the minimum distance over these variants, and the winning origin seeds the
+        verification with a translation"""
         if not isinstance(min_gap, numbers.Integral) or isinstance(min_gap, bool) or min_gap < 1:
             raise ValueError(f"LoopDetector: min_gap an integer >= 1, not {min_gap!r}")
         if clip_px is not None and (not isinstance(clip_px, numbers.Integral) or isinstance(clip_px, bool) or clip_px < 0):
@@ -90,10 +128,16 @@ class LoopDetector:
             if not isinstance(capacity, numbers.Integral) or isinstance(capacity, bool) or capacity < 1:
                 raise ValueError(f"LoopDetector: capacity an integer >= 1, not {capacity!r}")
             _ffi.loop_cloud_args(capacity, rows, maxPoints, pointStride, rangeResolutionM)
+        self.keepOffsets = originOffsetsM is not None
+        if self.keepOffsets:
+            ints = all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in (capacity, sectors, rings))
+            _ffi.loop_offsets_args(originOffsetsM, rangeResolutionM, *((capacity, sectors, rings) if ints else ()))
         self.db = _ffi.LoopDb(ctx, capacity, sectors, rings)
         self.sectors, self.rings = self.db.sectors, self.db.rings
         if self.keepClouds:
             self.db.keep_clouds(rows, maxPoints, pointStride, rangeResolutionM)
+        if self.keepOffsets:
+            self.db.keep_offsets(originOffsetsM, rangeResolutionM)
 
     def close(self):
         self.db.close()
@@ -125,33 +169,48 @@ class LoopDetector:
         """-> (xy (n, 2) float64 metres: the stored cloud of entry i, the scan's full peak count)"""
         return self.db.get_cloud(i)
 
-    def verify(self, queryIndex, candIndex, candYaw, **verify):
-        """verifyCandidates from the stored clouds: the arguments, keywords and results are verifyCandidates' without `clouds`"""
+    def verify(self, queryIndex, candIndex, candYaw, candOffset=None, **verify):
+        """verifyCandidates from the stored clouds: the arguments, keywords and results are verifyCandidates' without `clouds`.
+        candOffset (Q, k, 2) metres, what query(withOffsets=True) returned: candidate (a, slot) is seeded with (yaw, -R(yaw) offset)
+        instead of (yaw, 0, 0), and the table carries ox, oy (VERIFY_TABLE_OFFSETS)"""
         q, ci, yaw, o, accept = _verify_args(queryIndex, candIndex, candYaw, verify)
+        off = None
+        if candOffset is not None:
+            off = np.asarray(candOffset, np.float64)
+            if off.shape != ci.shape + (2,) or not np.all(np.abs(off) <= _ffi.ICP_MAX_COORD):
+                raise ValueError(f"LoopDetector.verify: candOffset {ci.shape + (2,)} finite metres, not {off.shape}")
         rows, pos = _verify_rows(q, ci, len(self.db), "entries")
         if not rows:
-            return [], np.zeros(0, VERIFY_TABLE)
-        seeds = np.array([[yaw[a, slot], 0.0, 0.0] for a, (_, _, slot) in zip(pos, rows)])
+            return [], np.zeros(0, VERIFY_TABLE if off is None else VERIFY_TABLE_OFFSETS)
+        slots = [slot for _, _, slot in rows]
+        offs = None if off is None else off[pos, slots]
+        seeds = _seed(yaw[pos, slots], np.zeros((len(rows), 2)) if offs is None else offs)
         poses, stats = self.db.verify([r[0] for r in rows], [r[1] for r in rows], seeds, o)
         n, _ = self.db.cloud_counts()
         sizes = np.array([min(n[qi], n[cj]) for qi, cj, _ in rows])
-        return _accept(len(q), rows, pos, seeds, poses, stats, sizes, *accept)
+        return _accept(len(q), rows, pos, seeds, poses, stats, sizes, *accept, offsets=offs)
 
     def queryAndVerify(self, indices=None, **verify):
         """query the entries `indices` (None: the newest) and verify every candidate from the stored clouds in the same device pass
-        (roam_loop_db_query_verify) -> (edges, table) as verifyCandidates returns them"""
+        (roam_loop_db_query_verify) -> (edges, table) as verifyCandidates returns them.  A detector that keeps origin offsets queries
+        over the variants and seeds every candidate with its winning offset, (yaw, -R(yaw) offset); its table carries ox, oy
+        (VERIFY_TABLE_OFFSETS)"""
         idx = np.array([len(self.db) - 1], np.int32) if indices is None else np.ascontiguousarray(indices, np.int32).ravel()
         o, accept = _verify_opts(verify)
-        ci, _, cs, poses, stats = self.db.query_verify(idx, idx - self.min_gap + 1, self.k, self.max_distance, o)
+        if self.keepOffsets:
+            ci, _, cs, cv, poses, stats = self.db.query_verify_offsets(idx, idx - self.min_gap + 1, self.k, self.max_distance, o)
+        else:
+            ci, _, cs, poses, stats = self.db.query_verify(idx, idx - self.min_gap + 1, self.k, self.max_distance, o)
         rows, pos = _verify_rows(idx, ci, len(self.db), "entries")
         if not rows:
-            return [], np.zeros(0, VERIFY_TABLE)
+            return [], np.zeros(0, VERIFY_TABLE_OFFSETS if self.keepOffsets else VERIFY_TABLE)
         flat = np.array([a * self.k + slot for a, (_, _, slot) in zip(pos, rows)])
         yaw = _yaw(cs, self.sectors).reshape(-1)[flat]
-        seeds = np.stack([yaw, np.zeros(len(rows)), np.zeros(len(rows))], axis=1)
+        offs = self.db.variant_offsets(cv.reshape(-1)[flat]) if self.keepOffsets else None
+        seeds = _seed(yaw, np.zeros((len(rows), 2)) if offs is None else offs)
         n, _ = self.db.cloud_counts()
         sizes = np.array([min(n[qi], n[cj]) for qi, cj, _ in rows])
-        return _accept(len(idx), rows, pos, seeds, poses.reshape(-1, 3)[flat], stats.reshape(-1)[flat], sizes, *accept)
+        return _accept(len(idx), rows, pos, seeds, poses.reshape(-1, 3)[flat], stats.reshape(-1)[flat], sizes, *accept, offsets=offs)
 
     def floorCode(self):
         """the integer floor of the u8 record form that equals this detector's floor (Engine.loop_db_add): floor * 255, which must be
@@ -161,10 +220,15 @@ class LoopDetector:
             raise ValueError(f"LoopDetector: floor {self.floor} is no u8 code / 255 in [0, 254 / 255]")
         return code
 
-    def query(self, indices=None):
+    def query(self, indices=None, withOffsets=False):
         """candidates of the entries `indices` (None: the newest) among the entries j <= i - min_gap -> (index (m, k) int32, distance
-        (m, k) float64, yaw (m, k) float64); unused slots hold -1, +inf, 0"""
+        (m, k) float64, yaw (m, k) float64); unused slots hold -1, +inf, 0.  withOffsets: the distance of a pair is the minimum over
+        the query's origin-shifted variants (a detector with originOffsetsM; otherwise the plain query), and a fourth array
+        (m, k, 2) float64 holds the winning origin offsets in metres, (0, 0) where the plain descriptor won"""
         idx = np.array([len(self.db) - 1], np.int32) if indices is None else np.ascontiguousarray(indices, np.int32).ravel()
+        if withOffsets:
+            ci, cd, cs, cv = self.db.query_offsets(idx, idx - self.min_gap + 1, self.k, self.max_distance)
+            return ci, cd, _yaw(cs, self.sectors), self.db.variant_offsets(cv)
         ci, cd, cs = self.db.query(idx, idx - self.min_gap + 1, self.k, self.max_distance)
         return ci, cd, _yaw(cs, self.sectors)
 
@@ -226,6 +290,10 @@ VERIFY_TABLE = np.dtype([("query", np.int32), ("candidate", np.int32), ("slot", 
                          ("n_inliers", np.int32), ("fraction", np.float64), ("rms", np.float64), ("accepted", np.bool_)])
 
 
+# the table of a detector that keeps origin offsets: VERIFY_TABLE plus the winning offset of every tried candidate, metres
+VERIFY_TABLE_OFFSETS = np.dtype(VERIFY_TABLE.descr + [("ox", np.float64), ("oy", np.float64)])
+
+
 def verifyCandidates(clouds, queryIndex, candIndex, candYaw, *, minInlierFraction=MIN_INLIER_FRACTION, maxRmsM=None, maxTranslationM=5.0,
                      allPerQuery=False, **opts):
     """Verify loop-closure candidates by ICP and measure their edges.  clouds: one (K, 2) metre cloud per keyframe
@@ -284,10 +352,12 @@ def _verify_rows(q, ci, count, what):
     return rows, pos
 
 
-def _accept(n_query, rows, pos, seeds, poses, stats, sizes, minInlierFraction, max_rms, maxTranslationM, allPerQuery):
+def _accept(n_query, rows, pos, seeds, poses, stats, sizes, minInlierFraction, max_rms, maxTranslationM, allPerQuery, offsets=None):
     """The acceptance, written once for verifyCandidates, LoopDetector.verify and LoopDetector.queryAndVerify: the tried candidates
     (rows, pos: _verify_rows), their seeds, ICP poses and statistics, sizes = min(n, m) of each pair's clouds -> (edges, table)"""
-    table = np.zeros(len(rows), VERIFY_TABLE)
+    table = np.zeros(len(rows), VERIFY_TABLE if offsets is None else VERIFY_TABLE_OFFSETS)
+    if offsets is not None:
+        table["ox"], table["oy"] = offsets[:, 0], offsets[:, 1]
     table["query"], table["candidate"], table["slot"] = [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
     table["yaw"], table["theta"], table["tx"], table["ty"] = seeds[:, 0], poses[:, 0], poses[:, 1], poses[:, 2]
     for name in ("status", "iterations", "n_pairs_last", "n_inliers", "rms"):

@@ -84,6 +84,7 @@ ICP_DEFAULTS = dict(gate_start=3.0, gate_end=0.5, gate_decay=0.8, max_iterations
 SCAN_CONTEXT_MAX_SECTORS, SCAN_CONTEXT_MAX_RINGS = 256, 128     # roam_abi.h ROAM_SCAN_CONTEXT_MAX_*
 SCAN_CONTEXT_MAX_ROWS, SCAN_CONTEXT_MAX_CLIP = 65536, 4096
 LOOP_MAX_K = 32                         # roam_abi.h ROAM_LOOP_MAX_K
+LOOP_MAX_OFFSETS = 48                   # roam_abi.h ROAM_LOOP_MAX_OFFSETS
 LOOP_DB_BYTES = 2000 << 20              # a database, and the device scratch of one launch
 
 
@@ -166,6 +167,18 @@ _SIGS = {
     "roam_loop_db_query_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, _P(IcpOpts), _vp, _vp, _vp, _vp, _vp]),
     "roam_engine_time_loop_cloud": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, _P(C.c_float), _P(C.c_float)]),
     "roam_time_loop_db_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _P(IcpOpts), C.c_int32, _P(C.c_float)]),
+    "roam_scan_context_offset_table": (C.c_int32, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "roam_loop_db_keep_offsets": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_double]),
+    "roam_loop_db_set_variants": (C.c_int32, [_vp, _vp, C.c_int32, _vp]),
+    "roam_loop_db_get_variants": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp]),
+    "roam_scan_context_offsets_f32": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_double, C.c_int32, _vp, C.c_double, _vp]),
+    "roam_loop_db_query_offsets": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "roam_loop_db_query_verify_offsets": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, _P(IcpOpts), _vp, _vp, _vp, _vp, _vp,
+                                                      _vp]),
+    "roam_engine_time_loop_offsets": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
+    "roam_time_loop_db_query_offsets": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _P(C.c_float), _P(C.c_float),
+                                                    _P(C.c_float)]),
     "roam_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), _vp, _vp]),
     "roam_time_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), C.c_int32, _P(C.c_float)]),
     "roam_engine_create": (C.c_int32, [_vp, _P(EngineCfg)]),
@@ -615,6 +628,47 @@ def loop_query_args(count, indices, max_index, k, max_distance):
     if not isinstance(max_distance, numbers.Real) or np.isnan(max_distance):
         raise ValueError(f"loop query: max_distance is a number, not {max_distance!r}")
     return q, m
+
+
+def loop_offsets_args(offsets_m, range_resolution_m, capacity=None, sectors=None, rings=None):
+    """the checks of LoopDb.keep_offsets and Context.scan_context_offsets before any library call -> (offsets (n, 2) float64, C order,
+    range_resolution_m).  ValueError: not (n, 2) numbers with 1 <= n <= 48, an offset that is not finite, beyond 1e6 m or (0, 0), a
+    resolution that is not finite or <= 0, a variant store (capacity x n x sectors x (4 rings + 8 padded rings + 4) bytes) beyond 2000 MiB"""
+    a = np.asarray(offsets_m)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"scan context offsets: offsets of numbers, not {a.dtype}")
+    if a.ndim == 1 and a.size == 2:
+        a = a.reshape(1, 2)
+    if a.ndim != 2 or a.shape[1] != 2 or not 1 <= len(a) <= LOOP_MAX_OFFSETS:
+        raise ValueError(f"scan context offsets: (n, 2) offsets in metres with 1 <= n <= {LOOP_MAX_OFFSETS}, not shape {a.shape}")
+    a = np.ascontiguousarray(a, np.float64)
+    if not np.all(np.abs(a) <= ICP_MAX_COORD):
+        raise ValueError(f"scan context offsets: an offset that is not finite or beyond {ICP_MAX_COORD:g} m")
+    if np.any(np.all(a == 0.0, axis=1)):
+        raise ValueError("scan context offsets: the offset (0, 0) - variant 0 is the plain descriptor already")
+    res = range_resolution_m
+    if not isinstance(res, numbers.Real) or isinstance(res, bool) or not np.isfinite(res) or not res > 0:
+        raise ValueError(f"scan context offsets: range_resolution_m finite and > 0, not {res!r}")
+    if capacity is not None:
+        per = len(a) * sectors * (4 * rings + 8 * ((rings + 3) & ~3) + 4)
+        if capacity * per > LOOP_DB_BYTES:
+            raise ValueError(f"loop db: capacity {capacity} x {len(a)} offsets x {per // len(a)} bytes is beyond the {LOOP_DB_BYTES} bytes of a variant store")
+    return a, float(res)
+
+
+def scan_context_offset_table(rows, sectors):
+    """roam_scan_context_offset_table, host code only (no device, no context): the tables of the origin-shifted descriptor by the
+    host's libm -> (cos, sin of the row centres (rows,), cos, sin of the sector boundaries (sectors,)) float64.  ValueError outside
+    scan_context_plan's limits"""
+    for name, v in (("rows", rows), ("sectors", sectors)):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool):
+            raise ValueError(f"scan context: {name} is an integer, not {v!r}")
+    if not 2 <= sectors <= SCAN_CONTEXT_MAX_SECTORS or not sectors <= rows <= SCAN_CONTEXT_MAX_ROWS:
+        raise ValueError(f"scan context: sectors in [2, {SCAN_CONTEXT_MAX_SECTORS}] and rows in [sectors, {SCAN_CONTEXT_MAX_ROWS}], not {sectors} and {rows}")
+    out = [np.empty(rows), np.empty(rows), np.empty(sectors), np.empty(sectors)]
+    if load_library().roam_scan_context_offset_table(int(rows), int(sectors), *[_ptr(a) for a in out]) != ROAM_OK:
+        raise ValueError(f"scan context: roam_scan_context_offset_table refused rows {rows}, sectors {sectors}")
+    return tuple(out)
 
 
 def polar_cloud_table(rows):
@@ -1120,6 +1174,20 @@ class Context:
                                                   C.byref(o), int(reps), C.byref(ms)))
         return ms.value
 
+    def scan_context_offsets(self, polar, offsets_m, range_resolution_m, sectors=60, rings=20, clip_px=None, floor=0.0):
+        """scan_context with the origin-shifted variants (roam_scan_context_offsets_f32) -> (n, 1 + n_offsets, sectors, rings) float32:
+        variant 0 the plain descriptor, variant a the scan as seen from offsets_m[a - 1] (metres, x = r cos phi, y = r sin phi).
+        ValueError before any library call"""
+        a3, n, rows, cols, row_stride, image_stride, _ = scan_context_images(polar, clip_px, sectors, rings)
+        floor = scan_context_floor(floor)
+        off, res = loop_offsets_args(offsets_m, range_resolution_m)
+        if n * len(off) * sectors * rings * 4 > LOOP_DB_BYTES:
+            raise ValueError(f"scan context offsets: {n} images x {len(off)} offsets are beyond {LOOP_DB_BYTES} bytes of descriptors")
+        out = np.empty((n, 1 + len(off), sectors, rings), np.float32)
+        self.check(self.lib.roam_scan_context_offsets_f32(self.h, _ptr(a3), n, rows, cols, row_stride, image_stride, int(clip_px or 0), int(sectors),
+                                                          int(rings), floor, len(off), _ptr(off), res, _ptr(out)))
+        return out
+
     def scan_context(self, polar, sectors=60, rings=20, clip_px=None, floor=0.0):
         """the scan-context descriptors of a 2-D float32 polar image or a 3-D batch (roam_scan_context_f32) -> (n, sectors, rings)
         float32: the area mean of max(v - floor, 0) over integer bins (scan_context_plan).  ValueError before any library call"""
@@ -1274,6 +1342,7 @@ class LoopDb:
         ctx.check(ctx.lib.roam_loop_db_create(ctx.h, self.capacity, self.sectors, self.rings, C.byref(h)))
         self.h = h
         self.cloud_rows = self.max_points = None             # set by keep_clouds
+        self.offsets_m = None                                # set by keep_offsets: (n_offsets, 2) float64 metres
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -1332,6 +1401,85 @@ class LoopDb:
         self.ctx.check(self.ctx.lib.roam_loop_db_query(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance), _ptr(ci),
                                                        _ptr(cd), _ptr(cs), _ptr(df), _ptr(sf)))
         return (ci, cd, cs, df, sf) if want_full else (ci, cd, cs)
+
+    # ---- origin-shifted variants
+    def keep_offsets(self, offsets_m, range_resolution_m=0.0432):
+        """roam_loop_db_keep_offsets: once, on an empty database - from here on every described scan also stores its descriptor as
+        seen from each of the offsets (metres), and query_offsets / query_verify take the minimum over these variants"""
+        off, res = loop_offsets_args(offsets_m, range_resolution_m, self.capacity, self.sectors, self.rings)
+        if self.offsets_m is not None:
+            raise ValueError("loop db: keeps offsets already")
+        if len(self):
+            raise ValueError(f"loop db: keep_offsets on an empty database, not one of {len(self)} entries")
+        self.ctx.check(self.ctx.lib.roam_loop_db_keep_offsets(self.ctx.h, self.h, len(off), _ptr(off), res))
+        self.offsets_m = off
+
+    def _needs_offsets(self):
+        if self.offsets_m is None:
+            raise ValueError("loop db: keeps no offsets (keep_offsets)")
+
+    def _entry(self, index):
+        if not isinstance(index, numbers.Integral) or isinstance(index, bool) or not 0 <= index < len(self):
+            raise ValueError(f"loop db: index in [0, {len(self)}), not {index!r}")
+        return int(index)
+
+    def set_variants(self, index, desc):
+        """replace the variants 1 .. n_offsets of the stored entry `index` by desc (n_offsets, S, R)"""
+        self._needs_offsets()
+        d = np.ascontiguousarray(desc, np.float32)
+        if d.shape != (len(self.offsets_m), self.sectors, self.rings):
+            raise ValueError(f"loop db: variants ({len(self.offsets_m)}, {self.sectors}, {self.rings}), not {d.shape}")
+        if not np.isfinite(d).all():
+            raise ValueError("loop db: a descriptor value that is not finite")
+        self.ctx.check(self.ctx.lib.roam_loop_db_set_variants(self.ctx.h, self.h, self._entry(index), _ptr(d)))
+
+    def get_variants(self, index):
+        """-> (desc (n_offsets, S, R) float32, valid (n_offsets, S) int32) of the stored entry `index`"""
+        self._needs_offsets()
+        d = np.empty((len(self.offsets_m), self.sectors, self.rings), np.float32)
+        v = np.empty((len(self.offsets_m), self.sectors), np.int32)
+        self.ctx.check(self.ctx.lib.roam_loop_db_get_variants(self.ctx.h, self.h, self._entry(index), _ptr(d), _ptr(v)))
+        return d, v
+
+    def query_offsets(self, indices, max_index, k=8, max_distance=np.inf, want_full=False):
+        """roam_loop_db_query_offsets: query over the variants of the query entries -> query's arrays plus the winning variant
+        (m, k) int32 (0: the plain descriptor, a: offsets_m[a - 1]); want_full: also (m, count) distance, shift and variant"""
+        q, m = loop_query_args(len(self), indices, max_index, k, max_distance)
+        ci, cd, cs = np.empty((len(q), k), np.int32), np.empty((len(q), k), np.float64), np.empty((len(q), k), np.int32)
+        cv = np.empty((len(q), k), np.int32)
+        df = np.empty((len(q), len(self)), np.float64) if want_full else None
+        sf = np.empty((len(q), len(self)), np.int32) if want_full else None
+        vf = np.empty((len(q), len(self)), np.int32) if want_full else None
+        self.ctx.check(self.ctx.lib.roam_loop_db_query_offsets(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance), _ptr(ci),
+                                                               _ptr(cd), _ptr(cs), _ptr(cv), _ptr(df), _ptr(sf), _ptr(vf)))
+        return (ci, cd, cs, cv, df, sf, vf) if want_full else (ci, cd, cs, cv)
+
+    def variant_offsets(self, variant):
+        """variant indices (...) -> their offsets in metres (..., 2); variant 0 (and a database without offsets) is (0, 0)"""
+        table = np.zeros((1, 2)) if self.offsets_m is None else np.concatenate([np.zeros((1, 2)), self.offsets_m])
+        return table[np.asarray(variant)]
+
+    def query_verify_offsets(self, indices, max_index, k=8, max_distance=np.inf, opts=None):
+        """roam_loop_db_query_verify_offsets: query_verify plus the winning variants (m, k) int32 before the poses"""
+        self._needs_clouds()
+        o = icp2d_opts(opts)
+        q, m = loop_query_args(len(self), indices, max_index, k, max_distance)
+        ci, cd, cs = np.empty((len(q), k), np.int32), np.empty((len(q), k), np.float64), np.empty((len(q), k), np.int32)
+        cv = np.empty((len(q), k), np.int32)
+        poses, stats = np.empty((len(q), k, 3), np.float64), np.zeros((len(q), k), ICP_STATS)
+        self.ctx.check(self.ctx.lib.roam_loop_db_query_verify_offsets(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance),
+                                                                      C.byref(o), _ptr(ci), _ptr(cd), _ptr(cs), _ptr(cv), _ptr(poses), _ptr(stats)))
+        return ci, cd, cs, cv, poses, stats
+
+    def time_query_offsets(self, indices, max_index, k=8, max_distance=np.inf, reps=20):
+        """(plain distance kernel ms, variants' distance kernel and fold ms, selection kernel ms) per launch
+        (roam_time_loop_db_query_offsets)"""
+        self._needs_offsets()
+        q, m = loop_query_args(len(self), indices, max_index, k, max_distance)
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        self.ctx.check(self.ctx.lib.roam_time_loop_db_query_offsets(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance),
+                                                                    int(reps), C.byref(a), C.byref(b), C.byref(c)))
+        return float(a.value), float(b.value), float(c.value)
 
     # ---- peak clouds
     def keep_clouds(self, rows, max_points=ICP_MAX_POINTS, point_stride=1, range_resolution_m=0.0432):

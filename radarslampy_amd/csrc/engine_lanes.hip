@@ -242,6 +242,15 @@ int32_t roam_engine_time_loop_describe(roam_ctx *ctx, roam_loop_db *db, int32_t 
     return loop_records_time_describe(ctx, db, loop_pool(ctx, e), n, pool_idx, clip_px, floor_code, reps, ms_per_rep);
 }
 
+int32_t roam_engine_time_loop_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
+                                      int32_t reps, float *ms_per_rep)
+{
+    ENGINE();
+    ARG_CHECK(ctx, db && n >= 1 && pool_idx && ms_per_rep);
+    for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
+    return loop_records_time_offsets(ctx, db, loop_pool(ctx, e), n, pool_idx, clip_px, floor_code, reps, ms_per_rep);
+}
+
 int32_t roam_engine_time_loop_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t reps, float *rows_ms,
                                     float *gather_ms)
 {

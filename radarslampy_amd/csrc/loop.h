@@ -3,19 +3,23 @@
 //   loop_describe.hip  scan_context_kernel, scan_context_norm_kernel; the geometry and float32 argument checks;
 //                      roam_scan_context_plan, roam_scan_context_f32; host float32 images in chunks (sc_describe_host_f32)
 //   loop_db.hip        the database's lifetime (create, destroy, count, get) and its three adds: add_f32, add_desc and the engine's
-//                      resident records (loop_records_prepare / _append / _time_describe / _time_cloud)
-//   loop_query.hip     loop_distance_kernel, loop_select_kernel; the query pass (LoopQueryBufs and the loop_query_* steps);
-//                      roam_loop_db_query, roam_time_loop_db_query
+//                      resident records (loop_records_prepare / _append / _time_describe / _time_offsets / _time_cloud)
+//   loop_query.hip     loop_distance_kernel, loop_variant_fold_kernel, loop_select_kernel, loop_variant_gather_kernel; the query pass
+//                      (LoopQueryBufs and the loop_query_* steps); roam_loop_db_query, roam_loop_db_query_offsets and their timing entries
 //   loop_cloud.hip     cloud_gather_kernel, the row staging and the cloud build; roam_polar_cloud_table, roam_loop_db_keep_clouds,
 //                      set_cloud, get_cloud, cloud_counts
 //   loop_verify.hip    loop_pairs_kernel, the pair scratch and staging; roam_loop_db_verify, roam_time_loop_db_verify,
 //                      roam_loop_db_query_verify
+//   loop_offset.hip    the origin-shifted variants of an entry (Scan Context++): scan_context_offset_kernel and its finishing kernel,
+//                      the variant store (roam_loop_db_keep_offsets, set_variants, get_variants), roam_scan_context_offset_table,
+//                      roam_scan_context_offsets_f32; loop_query.hip reads the store as its queries, loop_verify.hip seeds from it
 //   icp.hip            the ICP of a pair of stored clouds (icp2d_store_kernel), which loop_verify.hip launches
 // engine_lanes.hip describes the engine's pool (LoopPool) and calls the record entries.  The reference has no place recognition (a
 // commented-out "import m2dp" at Mapping.py:7 and an unused Keyframe.pointCloud at :61-62), so parity is unpinned: the contracts are
-// tests/scan_context_model.py and tests/loop_cloud_model.py.
+// tests/scan_context_model.py, tests/loop_cloud_model.py and tests/scan_context_offset_model.py.
 #pragma once
 #include "roam_internal.h"
+#include <vector>
 
 #define LOOP_UNIT __attribute__((visibility("hidden")))      // host functions that cross a unit, kept out of the library's symbol table
 #define LOOP_TRY(call) do { const int32_t rc_ = (call); if (rc_ != ROAM_OK) return rc_; } while (0)
@@ -40,7 +44,26 @@ struct roam_loop_db {
     int32_t *cloud_n = nullptr, *cloud_peaks = nullptr;      // capacity each: the points stored, the scan's full peak count
     double *trig = nullptr;      // cos(phi_t), t < cloud_rows, then sin(phi_t)
     std::vector<int32_t> h_n, h_peaks;                       // host mirror of the two counts, kept by the blocking entries
+    // the origin-shifted variants (roam_loop_db_keep_offsets): n_off = 0 when the database keeps none.  Variant a >= 1 of entry e is
+    // row e n_off + a - 1 of the store; variant 0 is the entry itself
+    int n_off = 0, off_rows = 0; // off_rows: the azimuths off_trig was made for (0: not yet)
+    float *vdesc = nullptr;      // capacity x n_off x S x R
+    double *vnrm = nullptr;      // capacity x n_off x S x Rp
+    int32_t *vvalid = nullptr;   // capacity x n_off x S
+    double *off_bins = nullptr, *off_m = nullptr;            // n_off x 2 each: the offsets in range bins and in metres
+    double *off_trig = nullptr;  // sc_offset_table's four tables for off_rows azimuths (room for SC_MAX_ROWS)
 };
+
+// the float64 norm of one sector column of a descriptor, rings ascending - the one function behind every stored nrm / valid, so that
+// an entry's (and a variant's) stored bits depend on its descriptor alone
+__device__ static inline double sc_sector_norm(const float *d, int R)
+{
+    double n2 = 0.0;
+    for (int r = 0; r < R; ++r) n2 += (double)d[r] * (double)d[r];
+    return sqrt(n2);
+}
+
+__device__ static inline double sc_normalised(float d, double norm) { return norm > 0.0 ? (double)d / norm : 0.0; }
 
 // image z of a launch: base + (index ? index[z] : z) * image_stride (+ payload_off for u8 records); strides in elements
 struct ScSrc {
@@ -56,6 +79,8 @@ struct ScSrc {
         return ROAM_E_ARG;                                  \
     } while (0)
 
+struct ScOffsets;                                // loop_offset.hip, below
+
 // ---- loop_describe.hip
 // the checks of the geometry, shared by every describing entry -> the clip
 LOOP_UNIT int32_t sc_check_geometry(char *err, size_t cap, int32_t rows, int32_t cols, int32_t clip_px, int32_t sectors, int32_t rings, int *clip_out);
@@ -66,12 +91,37 @@ LOOP_UNIT hipError_t sc_launch_describe(hipStream_t st, bool u8, const ScSrc &sr
                                         int floor_code, float *desc, double *nrm, int32_t *valid, int64_t first);
 // the n descriptors already in db->desc from entry `first` on -> their nrm / valid
 LOOP_UNIT hipError_t sc_launch_norm(hipStream_t st, const roam_loop_db *db, int64_t first, int n);
+// the same kernel on any n_rows sector columns of ready-made descriptors (the variant store's)
+LOOP_UNIT hipError_t sc_launch_norm_rows(hipStream_t st, const float *desc, int64_t n_rows, int R, int Rp, double *nrm, int32_t *valid);
 // host float32 images in chunks under the scratch limit: upload the clipped columns tightly, describe into desc (+ nrm, valid) from
 // entry `first` on.  cloud_db (optional, a database that keeps clouds; cols = the images' full width): all the columns are uploaded,
 // and the images' peak clouds go to the entries from `first` on as well
 LOOP_UNIT int32_t sc_describe_host_f32(roam_ctx *ctx, const float *polar, int n, int rows, int64_t row_stride, int64_t image_stride, int clip,
                                        int S, int R, double floor_v, float *desc, double *nrm, int32_t *valid, int64_t first,
-                                       const roam_loop_db *cloud_db = nullptr, int cols = 0);
+                                       const roam_loop_db *cloud_db = nullptr, int cols = 0, const ScOffsets *offs = nullptr);
+
+// ---- loop_offset.hip
+// where the variants of a describing call come from and go to: device pointers, the store's at its entry 0 (vnrm / vvalid may be null)
+struct ScOffsets {
+    int n_off;
+    const double *trig, *off_bins;
+    float *vdesc;
+    double *vnrm;
+    int32_t *vvalid;
+};
+// tables of the host's libm for `rows` azimuths and the S sector boundaries: out = cos(phi_a) (rows), sin(phi_a) (rows), cos(beta_s) (S),
+// sin(beta_s) (S), phi_a = (2.0 * M_PI * (a + 0.5)) / rows, beta_s = (2.0 * M_PI * floor(s rows / S)) / rows
+LOOP_UNIT void sc_offset_table(int rows, int S, double *out);
+// device bytes of partial sums one image of a launch takes (the float32 form: one slab per block of rows; u8: one slab)
+LOOP_UNIT int64_t sc_offset_part_bytes(bool u8, int rows, int S, int R, int n_off);
+// the n_off variants of n images -> the store's entries from `first` on; enqueued, not awaited (scratch S_TMP5 / S_TMP6)
+LOOP_UNIT int32_t sc_launch_offsets(roam_ctx *ctx, bool u8, const ScSrc &src, int n, int rows, int clip, int S, int R, double floor_v,
+                                    int floor_code, const ScOffsets &offs, int64_t first);
+// a database that keeps offsets: its tables for scans of `rows` azimuths (uploaded when rows changes) -> what sc_launch_offsets takes
+LOOP_UNIT int32_t sc_offsets_of_db(roam_ctx *ctx, roam_loop_db *db, int rows, ScOffsets *out);
+// the n ready-made entries from `first` on: all their variants zero (invalid: distance 1)
+LOOP_UNIT int32_t sc_offsets_clear(roam_ctx *ctx, const roam_loop_db *db, int64_t first, int n);
+LOOP_UNIT void sc_offsets_free(roam_loop_db *db);
 
 // ---- loop_cloud.hip
 // bytes of row staging one scan of `cols` range bins takes (row_stage + row_count)
@@ -102,6 +152,9 @@ LOOP_UNIT int32_t loop_records_append(roam_ctx *ctx, roam_loop_db *db, const Loo
 // nothing is appended: `reps` launches of the describing kernel into the free entries, timed (roam_time_launches)
 LOOP_UNIT int32_t loop_records_time_describe(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
                                              int32_t floor_code, int32_t reps, float *ms_per_rep);
+// likewise the variants of the records (the clear, the binning kernel and the finishing kernel as one launch) into the free entries
+LOOP_UNIT int32_t loop_records_time_offsets(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
+                                            int32_t floor_code, int32_t reps, float *ms_per_rep);
 // likewise the two kernels of the cloud build, each alone: ms[0] the peak row kernel, ms[1] the cloud gather
 LOOP_UNIT int32_t loop_records_time_cloud(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t reps,
                                           float *ms);
@@ -116,11 +169,23 @@ struct LoopQueryBufs {
     int32_t *d_ci;               // nq x k: the candidates' indices, distances and shifts  (S_OUT0, S_OUT1, S_OUT2)
     double *d_cd;
     int32_t *d_cs;
+    // a query over the variants (n_off > 0; all null otherwise)
+    int n_off;
+    double *d_vdist;             // nq n_off x count: row q n_off + o = variant o + 1 of query q  (S_TMP2)
+    int32_t *d_vshift;           // likewise  (S_TMP5)
+    int32_t *d_var;              // nq x count: the winning variant of every pair  (S_TMP6)
+    int32_t *d_vq, *d_vqmax;     // nq n_off each: the variants' rows in the store, their queries' maxima  (S_TMP7)
+    int32_t *d_cv;               // nq x k: the candidates' winning variants  (S_IN0)
+    std::vector<int32_t> h_rows; // the host side of d_vq / d_vqmax while their upload is in flight
 };
 // max_index clamped to [0, count]
 LOOP_UNIT std::vector<int32_t> loop_query_clamp(const roam_loop_db *db, int32_t n_query, const int32_t *max_index);
 // take the scratch of the chunk and upload its nq indices and clamped maxima (host pointers at the chunk's first query)
-LOOP_UNIT int32_t loop_query_stage(roam_ctx *ctx, const roam_loop_db *db, int nq, int k, const int32_t *query_index, const int32_t *qmax, LoopQueryBufs *b);
+// with_variants: also the scratch and the row lists of a query over the variants of a database that keeps offsets
+LOOP_UNIT int32_t loop_query_stage(roam_ctx *ctx, const roam_loop_db *db, int nq, int k, const int32_t *query_index, const int32_t *qmax, LoopQueryBufs *b,
+                                   bool with_variants = false);
+// device bytes of distance scratch one query takes
+LOOP_UNIT int64_t loop_query_bytes(const roam_loop_db *db, bool with_variants);
 // distance, then selection.  every_pair: the distance of every (query, entry), not only of the entries below the query's maximum - what
 // the dist_full / shift_full outputs want
 LOOP_UNIT int32_t loop_query_enqueue(roam_ctx *ctx, const roam_loop_db *db, const LoopQueryBufs &b, int nq, int k, double max_distance, bool every_pair);

@@ -13,6 +13,7 @@ static void sc_db_free(roam_loop_db *db)
     if (db->cloud_n) (void)hipFree(db->cloud_n);
     if (db->cloud_peaks) (void)hipFree(db->cloud_peaks);
     if (db->trig) (void)hipFree(db->trig);
+    sc_offsets_free(db);
     delete db;
 }
 
@@ -98,8 +99,10 @@ extern "C" int32_t roam_loop_db_add_f32(roam_ctx *ctx, roam_loop_db *db, const f
     if (db->cloud_rows) LOOP_TRY(sc_check_cloud_add(ctx, db, rows, cols));
     LOOP_TRY(sc_check_room(ctx, db, n));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ScOffsets offs;
+    if (db->n_off) LOOP_TRY(sc_offsets_of_db(ctx, db, rows, &offs));
     LOOP_TRY(sc_describe_host_f32(ctx, polar, n, rows, row_stride, image_stride, clip, db->S, db->R, floor, db->desc, db->nrm, db->valid, db->count,
-                                  db->cloud_rows ? db : nullptr, cols));
+                                  db->cloud_rows ? db : nullptr, cols, db->n_off ? &offs : nullptr));
     if (db->cloud_rows) LOOP_TRY(sc_mirror_counts(ctx, db, db->count, n));
     if (first_index_out) *first_index_out = db->count;
     db->count += n;
@@ -121,6 +124,7 @@ extern "C" int32_t roam_loop_db_add_desc(roam_ctx *ctx, roam_loop_db *db, const 
     const hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(db->desc + db->count * per, desc, sizeof(float) * per * n, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, sc_launch_norm(st, db, db->count, n));
+    if (db->n_off) LOOP_TRY(sc_offsets_clear(ctx, db, db->count, n));      // no scan, no variants: all invalid (roam_loop_db_set_variants fills them)
     if (db->cloud_rows) {                                 // ready-made descriptors bring no scan: empty clouds (roam_loop_db_set_cloud fills them)
         HIP_TRY(ctx, hipMemsetAsync(db->cloud_n + db->count, 0, sizeof(int32_t) * (size_t)n, st));
         HIP_TRY(ctx, hipMemsetAsync(db->cloud_peaks + db->count, 0, sizeof(int32_t) * (size_t)n, st));
@@ -167,6 +171,22 @@ static int32_t sc_stage_records(roam_ctx *ctx, const LoopPool &pool, int32_t n, 
     return ROAM_OK;
 }
 
+// the variants of the n staged records -> the entries from db->count on, in chunks that bound the slabs; enqueued
+static int32_t sc_records_offsets(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, const ScSrc &src, int32_t n, int clip, int32_t floor_code,
+                                  const ScOffsets &offs)
+{
+    int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / sc_offset_part_bytes(true, pool.rows, db->S, db->R, db->n_off);
+    if (chunk < 1) chunk = 1;
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+        const int nb = (int)(n - i0 < chunk ? n - i0 : chunk);
+        ScSrc part = src;
+        part.index += i0;
+        LOOP_TRY(sc_launch_offsets(ctx, true, part, nb, pool.rows, clip, db->S, db->R, 0.0, floor_code, offs, db->count + i0));
+        if (i0 + nb < n) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the next chunk reuses the slabs
+    }
+    return ROAM_OK;
+}
+
 int32_t loop_records_append(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
                             int32_t floor_code, int32_t *first_index_out)
 {
@@ -177,6 +197,11 @@ int32_t loop_records_append(roam_ctx *ctx, roam_loop_db *db, const LoopPool &poo
     LOOP_TRY(sc_stage_records(ctx, pool, n, pool_idx, &src, &ps));
     const hipStream_t st = ctx->stream;
     HIP_TRY(ctx, sc_launch_describe(st, true, src, n, pool.rows, clip, db->S, db->R, 0.0, floor_code, db->desc, db->nrm, db->valid, db->count));
+    if (db->n_off) {
+        ScOffsets offs;
+        LOOP_TRY(sc_offsets_of_db(ctx, db, pool.rows, &offs));
+        LOOP_TRY(sc_records_offsets(ctx, db, pool, src, n, clip, floor_code, offs));
+    }
     if (db->cloud_rows) {                                 // in chunks that bound the staging; what is stored does not depend on the cut
         int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / sc_stage_bytes(pool.rows, pool.clip);
         if (chunk < 1) chunk = 1;
@@ -207,6 +232,30 @@ int32_t loop_records_time_describe(roam_ctx *ctx, roam_loop_db *db, const LoopPo
     return roam_time_launches(ctx, st, reps, ms_per_rep, [&] {
         return sc_launch_describe(st, true, src, n, pool.rows, clip, db->S, db->R, 0.0, floor_code, db->desc, db->nrm, db->valid, db->count);
     });
+}
+
+int32_t loop_records_time_offsets(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
+                                  int32_t floor_code, int32_t reps, float *ms_per_rep)
+{
+    int clip;
+    LOOP_TRY(sc_check_records(ctx, db, pool, n, clip_px, floor_code, false, &clip));
+    LOOP_TRY(sc_check_reps(ctx, reps));
+    if (!db->n_off) { ROAM_SET_ERR(ctx, "loop db timing: db keeps no offsets"); return ROAM_E_ARG; }
+    if (n * sc_offset_part_bytes(true, pool.rows, db->S, db->R, db->n_off) > SC_DB_BYTES) {
+        ROAM_SET_ERR(ctx, "loop db timing: %d records do not fit one launch", n);
+        return ROAM_E_ARG;
+    }
+    ScSrc src;
+    PeakSrc ps;
+    LOOP_TRY(sc_stage_records(ctx, pool, n, pool_idx, &src, &ps));
+    ScOffsets offs;
+    LOOP_TRY(sc_offsets_of_db(ctx, db, pool.rows, &offs));
+    int32_t rc = ROAM_OK;
+    const int32_t rt = roam_time_launches(ctx, ctx->stream, reps, ms_per_rep, [&] {
+        rc = sc_launch_offsets(ctx, true, src, n, pool.rows, clip, db->S, db->R, 0.0, floor_code, offs, db->count);
+        return rc == ROAM_OK ? hipSuccess : hipErrorUnknown;
+    });
+    return rc != ROAM_OK ? rc : rt;
 }
 
 int32_t loop_records_time_cloud(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t reps, float *ms)

@@ -13,16 +13,7 @@
 #include <type_traits>
 
 // ---------------------------------------------------------------------------------------------------------------- device
-// the float64 norm of one sector column of a descriptor, rings ascending
-__device__ static double sc_sector_norm(const float *d, int R)
-{
-    double n2 = 0.0;
-    for (int r = 0; r < R; ++r) n2 += (double)d[r] * (double)d[r];
-    return sqrt(n2);
-}
-
-__device__ static double sc_normalised(float d, double norm) { return norm > 0.0 ? (double)d / norm : 0.0; }
-
+// (sc_sector_norm and sc_normalised: loop.h - the offset unit stores its variants through them too)
 template <bool U8>
 __global__ __launch_bounds__(SC_THREADS) void scan_context_kernel(ScSrc src, int rows, int clip, int S, int R, int Rp, double floor_v,
                                                                   int floor_code, float *__restrict__ desc, double *__restrict__ nrm,
@@ -127,21 +118,27 @@ hipError_t sc_launch_describe(hipStream_t st, bool u8, const ScSrc &src, int n, 
     return hipGetLastError();
 }
 
+hipError_t sc_launch_norm_rows(hipStream_t st, const float *desc, int64_t n_rows, int R, int Rp, double *nrm, int32_t *valid)
+{
+    hipLaunchKernelGGL(scan_context_norm_kernel, dim3((unsigned)((n_rows + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, st, desc, n_rows, R,
+                       Rp, nrm, valid);
+    return hipGetLastError();
+}
+
 hipError_t sc_launch_norm(hipStream_t st, const roam_loop_db *db, int64_t first, int n)
 {
-    const int64_t n_rows = (int64_t)n * db->S;
-    hipLaunchKernelGGL(scan_context_norm_kernel, dim3((unsigned)((n_rows + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, st,
-                       db->desc + first * db->S * db->R, n_rows, db->R, db->Rp, db->nrm + first * db->S * db->Rp, db->valid + first * db->S);
-    return hipGetLastError();
+    return sc_launch_norm_rows(st, db->desc + first * db->S * db->R, (int64_t)n * db->S, db->R, db->Rp, db->nrm + first * db->S * db->Rp,
+                               db->valid + first * db->S);
 }
 
 int32_t sc_describe_host_f32(roam_ctx *ctx, const float *polar, int n, int rows, int64_t row_stride, int64_t image_stride, int clip, int S,
                              int R, double floor_v, float *desc, double *nrm, int32_t *valid, int64_t first, const roam_loop_db *cloud_db,
-                             int cols)
+                             int cols, const ScOffsets *offs)
 {
     const hipStream_t st = ctx->stream;
     const int width = cloud_db ? cols : clip;
-    const int64_t per = (int64_t)sizeof(float) * rows * width + (cloud_db ? sc_stage_bytes(rows, cols) : 0);
+    const int64_t per = (int64_t)sizeof(float) * rows * width + (cloud_db ? sc_stage_bytes(rows, cols) : 0) +
+                        (offs ? sc_offset_part_bytes(false, rows, S, R, offs->n_off) : 0);
     int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / per;
     if (chunk < 1) chunk = 1;
     for (int64_t i0 = 0; i0 < n; i0 += chunk) {
@@ -151,6 +148,7 @@ int32_t sc_describe_host_f32(roam_ctx *ctx, const float *polar, int n, int rows,
         HIP_TRY(ctx, roam_upload_packed_f32(st, d_in, polar + i0 * image_stride, nb, width, rows, row_stride, image_stride));
         const ScSrc src = {d_in, (int64_t)rows * width, width, 0, nullptr};
         HIP_TRY(ctx, sc_launch_describe(st, false, src, nb, rows, clip, S, R, floor_v, 0, desc, nrm, valid, first + i0));
+        if (offs) LOOP_TRY(sc_launch_offsets(ctx, false, src, nb, rows, clip, S, R, floor_v, 0, *offs, first + i0));
         if (cloud_db) {
             const PeakSrc ps = {d_in, (int64_t)rows * width, width, 0, 0, nullptr};
             LOOP_TRY(sc_build_clouds(ctx, cloud_db, ps, nb, cols, first + i0));

@@ -13,11 +13,18 @@
 // on (d, k)).  Nothing in a pair's arithmetic depends on where the candidate sits, on the other queries or on the chunk, so its
 // (distance, shift) are the same bits in any call.
 //
+// Variants.  The kernel reads its queries as rows of (qnrm, qvalid): the database's own entries, or the variant store of a database
+// that keeps offsets, where row q n_off + o is variant o + 1 of entry q.  A query over the variants runs the kernel twice - the plain
+// entries, then the store - and loop_variant_fold_kernel takes per pair the minimum over the variants in ascending order with a
+// strict <, so a tie keeps the lower variant and a result equal to the plain one reports variant 0.
+//
 // Selection (loop_select_kernel): one workgroup per query, k <= 32 passes, each the lexicographic minimum of (distance, index)
 // above the previous pick, among the indices below max_index with distance <= max_distance.
 #include "loop.h"
 #include <cmath>
+#include <cstring>
 #include <limits>
+#include <vector>
 
 // ---------------------------------------------------------------------------------------------------------------- device
 // rings of one LDS phase: all of them (padded to a multiple of four) when the doubled candidate fits, else the largest multiple of four
@@ -27,9 +34,11 @@ __host__ __device__ static int sc_phase_rings(int S, int Rp)
     return Rp < fit ? Rp : fit;
 }
 
-// dist / shift: nq x count, row q = query qidx[q].  qmax (optional): candidate j is computed for query q only when j < qmax[q]
+// dist / shift: nq x count, row q = query row qidx[q] of (qnrm, qvalid).  qmax (optional): candidate j is computed for query q only
+// when j < qmax[q]
 template <int TK>
 __global__ __launch_bounds__(SC_THREADS) void loop_distance_kernel(const double *__restrict__ nrm, const int32_t *__restrict__ valid,
+                                                                   const double *__restrict__ qnrm, const int32_t *__restrict__ qvalid,
                                                                    const int32_t *__restrict__ qidx, const int32_t *__restrict__ qmax, int nq,
                                                                    int count, int S, int Rp, int RL, double *__restrict__ dist,
                                                                    int32_t *__restrict__ shift)
@@ -75,7 +84,7 @@ __global__ __launch_bounds__(SC_THREADS) void loop_distance_kernel(const double 
             for (int r = 0; r < rl; r += 4) {
                 double qv[SC_QW][4];
                 for (int i = 0; i < SC_QW; ++i) {
-                    const double *qp = nrm + ((int64_t)qi[i] * S + s) * Rp + r0 + r;      // wave-uniform: scalar loads
+                    const double *qp = qnrm + ((int64_t)qi[i] * S + s) * Rp + r0 + r;      // wave-uniform: scalar loads
                     for (int m = 0; m < 4; ++m) qv[i][m] = qp[m];
                 }
                 for (int m = 0; m < 4; ++m)
@@ -95,7 +104,7 @@ __global__ __launch_bounds__(SC_THREADS) void loop_distance_kernel(const double 
         for (int i = 0; i < SC_QW; ++i) cnt[u][i] = 0;
     for (int s = 0; s < S; ++s) {
         int vq[SC_QW];
-        for (int i = 0; i < SC_QW; ++i) vq[i] = valid[(int64_t)qi[i] * S + s];
+        for (int i = 0; i < SC_QW; ++i) vq[i] = qvalid[(int64_t)qi[i] * S + s];
         for (int u = 0; u < TK; ++u) {
             const int v = vc[s + kk[u]];
             for (int i = 0; i < SC_QW; ++i) cnt[u][i] += vq[i] * v;
@@ -120,6 +129,37 @@ __global__ __launch_bounds__(SC_THREADS) void loop_distance_kernel(const double 
             shift[(int64_t)(q0 + i) * count + j] = bk;
         }
     }
+}
+
+// the minimum over the variants of every pair (q, j) that was computed: dist / shift hold variant 0 on entry and the minimum on exit
+__global__ __launch_bounds__(SC_THREADS) void loop_variant_fold_kernel(double *__restrict__ dist, int32_t *__restrict__ shift,
+                                                                       int32_t *__restrict__ var, const double *__restrict__ vdist,
+                                                                       const int32_t *__restrict__ vshift, const int32_t *__restrict__ qmax,
+                                                                       int nq, int count, int n_off)
+{
+    const int64_t p = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+    if (p >= (int64_t)nq * count) return;
+    const int64_t q = p / count;
+    const int j = (int)(p - q * count);
+    if (qmax && j >= qmax[q]) return;
+    double bd = dist[p];
+    int bs = shift[p], ba = 0;
+    for (int o = 0; o < n_off; ++o) {
+        const int64_t v = (q * n_off + o) * count + j;
+        if (vdist[v] < bd) { bd = vdist[v]; bs = vshift[v]; ba = o + 1; }
+    }
+    dist[p] = bd;
+    shift[p] = bs;
+    var[p] = ba;
+}
+
+// the winning variant of every candidate slot (0 for an unused one)
+__global__ __launch_bounds__(SC_THREADS) void loop_variant_gather_kernel(const int32_t *__restrict__ ci, const int32_t *__restrict__ var, int n_slots,
+                                                                         int k, int count, int32_t *__restrict__ cv)
+{
+    const int p = blockIdx.x * SC_THREADS + threadIdx.x;
+    if (p >= n_slots) return;
+    cv[p] = ci[p] >= 0 ? var[(int64_t)(p / k) * count + ci[p]] : 0;
 }
 
 // per query the k smallest by (distance, index) among j < qmax[q] with distance <= max_distance; unused slots -1, +inf, 0
@@ -169,18 +209,21 @@ __global__ __launch_bounds__(SC_THREADS) void loop_select_kernel(const double *_
 
 // ---------------------------------------------------------------------------------------------------------------- host
 // the distance kernel for nq queries (d_q: their indices, d_mask: optional max_index) against every entry, and the selection
+// variants: the queries are rows of the variant store, not entries
 static hipError_t sc_launch_distance(hipStream_t st, const roam_loop_db *db, const int32_t *d_q, const int32_t *d_mask, int nq, double *d_dist,
-                                     int32_t *d_shift)
+                                     int32_t *d_shift, bool variants = false)
 {
+    const double *qn = variants ? db->vnrm : db->nrm;
+    const int32_t *qv = variants ? db->vvalid : db->valid;
     const int count = db->count, S = db->S, Rp = db->Rp;
     const int RL = sc_phase_rings(S, Rp);
     const size_t lds = sizeof(double) * (size_t)RL * (2 * S + 1) + sizeof(int32_t) * 2 * S;
     const dim3 grid(count, (nq + SC_QB - 1) / SC_QB);
     switch ((S + 63) / 64) {
-    case 1: hipLaunchKernelGGL(loop_distance_kernel<1>, grid, dim3(SC_THREADS), lds, st, db->nrm, db->valid, d_q, d_mask, nq, count, S, Rp, RL, d_dist, d_shift); break;
-    case 2: hipLaunchKernelGGL(loop_distance_kernel<2>, grid, dim3(SC_THREADS), lds, st, db->nrm, db->valid, d_q, d_mask, nq, count, S, Rp, RL, d_dist, d_shift); break;
-    case 3: hipLaunchKernelGGL(loop_distance_kernel<3>, grid, dim3(SC_THREADS), lds, st, db->nrm, db->valid, d_q, d_mask, nq, count, S, Rp, RL, d_dist, d_shift); break;
-    default: hipLaunchKernelGGL(loop_distance_kernel<4>, grid, dim3(SC_THREADS), lds, st, db->nrm, db->valid, d_q, d_mask, nq, count, S, Rp, RL, d_dist, d_shift); break;
+    case 1: hipLaunchKernelGGL(loop_distance_kernel<1>, grid, dim3(SC_THREADS), lds, st, db->nrm, db->valid, qn, qv, d_q, d_mask, nq, count, S, Rp, RL, d_dist, d_shift); break;
+    case 2: hipLaunchKernelGGL(loop_distance_kernel<2>, grid, dim3(SC_THREADS), lds, st, db->nrm, db->valid, qn, qv, d_q, d_mask, nq, count, S, Rp, RL, d_dist, d_shift); break;
+    case 3: hipLaunchKernelGGL(loop_distance_kernel<3>, grid, dim3(SC_THREADS), lds, st, db->nrm, db->valid, qn, qv, d_q, d_mask, nq, count, S, Rp, RL, d_dist, d_shift); break;
+    default: hipLaunchKernelGGL(loop_distance_kernel<4>, grid, dim3(SC_THREADS), lds, st, db->nrm, db->valid, qn, qv, d_q, d_mask, nq, count, S, Rp, RL, d_dist, d_shift); break;
     }
     return hipGetLastError();
 }
@@ -189,6 +232,17 @@ static hipError_t sc_launch_select(hipStream_t st, const roam_loop_db *db, const
                                    const double *d_dist, const int32_t *d_shift, int32_t *d_ci, double *d_cd, int32_t *d_cs)
 {
     hipLaunchKernelGGL(loop_select_kernel, dim3(nq), dim3(SC_THREADS), 0, st, d_dist, d_shift, d_qmax, db->count, k, max_distance, d_ci, d_cd, d_cs);
+    return hipGetLastError();
+}
+
+// a query over the variants, after the plain distance: the store's rows against every entry, then the fold into dist / shift / var
+static hipError_t sc_launch_variants(hipStream_t st, const roam_loop_db *db, const LoopQueryBufs &b, int nq, bool every_pair)
+{
+    hipError_t e = sc_launch_distance(st, db, b.d_vq, every_pair ? nullptr : b.d_vqmax, nq * b.n_off, b.d_vdist, b.d_vshift, true);
+    if (e != hipSuccess) return e;
+    const int64_t pairs = (int64_t)nq * db->count;
+    hipLaunchKernelGGL(loop_variant_fold_kernel, dim3((unsigned)((pairs + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, st, b.d_dist, b.d_shift,
+                       b.d_var, b.d_vdist, b.d_vshift, every_pair ? nullptr : b.d_qmax, nq, db->count, b.n_off);
     return hipGetLastError();
 }
 
@@ -219,8 +273,42 @@ std::vector<int32_t> loop_query_clamp(const roam_loop_db *db, int32_t n_query, c
     return qm;
 }
 
-int32_t loop_query_stage(roam_ctx *ctx, const roam_loop_db *db, int nq, int k, const int32_t *query_index, const int32_t *qmax, LoopQueryBufs *b)
+int64_t loop_query_bytes(const roam_loop_db *db, bool with_variants)
 {
+    const int64_t pair = (int64_t)(sizeof(double) + sizeof(int32_t)) * db->count;
+    return with_variants ? pair * (1 + db->n_off) + (int64_t)sizeof(int32_t) * db->count : pair;
+}
+
+// the variants' side of the stage: scratch, and the rows q n_off + o with their queries' maxima
+static int32_t loop_query_stage_variants(roam_ctx *ctx, const roam_loop_db *db, int nq, int k, const int32_t *query_index, const int32_t *qmax,
+                                         LoopQueryBufs *b)
+{
+    const int n_off = db->n_off;
+    const size_t vrows = (size_t)nq * n_off, vpairs = vrows * db->count;
+    b->n_off = n_off;
+    b->d_vdist = (double *)roam_scratch(ctx, S_TMP2, sizeof(double) * vpairs);
+    b->d_vshift = (int32_t *)roam_scratch(ctx, S_TMP5, sizeof(int32_t) * vpairs);
+    b->d_var = (int32_t *)roam_scratch(ctx, S_TMP6, sizeof(int32_t) * (size_t)nq * db->count);
+    b->d_vq = (int32_t *)roam_scratch(ctx, S_TMP7, sizeof(int32_t) * 2 * vrows);
+    b->d_vqmax = b->d_vq ? b->d_vq + vrows : nullptr;
+    b->d_cv = (int32_t *)roam_scratch(ctx, S_IN0, sizeof(int32_t) * (size_t)nq * k);
+    if (!b->d_vdist || !b->d_vshift || !b->d_var || !b->d_vq || !b->d_cv) return ROAM_E_HIP;
+    std::vector<int32_t> &rows = b->h_rows;                       // the caller's: alive until the chunk's wait
+    rows.resize(2 * vrows);
+    for (int q = 0; q < nq; ++q)
+        for (int o = 0; o < n_off; ++o) {
+            rows[(size_t)q * n_off + o] = query_index[q] * n_off + o;
+            rows[vrows + (size_t)q * n_off + o] = qmax[q];
+        }
+    HIP_TRY(ctx, hipMemcpyAsync(b->d_vq, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, ctx->stream));
+    return ROAM_OK;
+}
+
+int32_t loop_query_stage(roam_ctx *ctx, const roam_loop_db *db, int nq, int k, const int32_t *query_index, const int32_t *qmax, LoopQueryBufs *b,
+                         bool with_variants)
+{
+    b->n_off = 0;
+    b->d_vdist = nullptr; b->d_vshift = b->d_var = b->d_vq = b->d_vqmax = b->d_cv = nullptr;
     const size_t pairs = (size_t)nq * db->count, cands = (size_t)nq * k;
     b->d_dist = (double *)roam_scratch(ctx, S_TMP0, sizeof(double) * pairs);
     b->d_shift = (int32_t *)roam_scratch(ctx, S_TMP1, sizeof(int32_t) * pairs);
@@ -232,13 +320,21 @@ int32_t loop_query_stage(roam_ctx *ctx, const roam_loop_db *db, int nq, int k, c
     if (!b->d_dist || !b->d_shift || !b->d_q || !b->d_ci || !b->d_cd || !b->d_cs) return ROAM_E_HIP;
     HIP_TRY(ctx, hipMemcpyAsync(b->d_q, query_index, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(b->d_qmax, qmax, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+    if (with_variants && db->n_off) LOOP_TRY(loop_query_stage_variants(ctx, db, nq, k, query_index, qmax, b));
     return ROAM_OK;
 }
 
 int32_t loop_query_enqueue(roam_ctx *ctx, const roam_loop_db *db, const LoopQueryBufs &b, int nq, int k, double max_distance, bool every_pair)
 {
-    HIP_TRY(ctx, sc_launch_distance(ctx->stream, db, b.d_q, every_pair ? nullptr : b.d_qmax, nq, b.d_dist, b.d_shift));
-    HIP_TRY(ctx, sc_launch_select(ctx->stream, db, b.d_qmax, nq, k, max_distance, b.d_dist, b.d_shift, b.d_ci, b.d_cd, b.d_cs));
+    const hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, sc_launch_distance(st, db, b.d_q, every_pair ? nullptr : b.d_qmax, nq, b.d_dist, b.d_shift));
+    if (b.n_off) HIP_TRY(ctx, sc_launch_variants(st, db, b, nq, every_pair));
+    HIP_TRY(ctx, sc_launch_select(st, db, b.d_qmax, nq, k, max_distance, b.d_dist, b.d_shift, b.d_ci, b.d_cd, b.d_cs));
+    if (b.n_off) {
+        hipLaunchKernelGGL(loop_variant_gather_kernel, dim3((nq * k + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st, b.d_ci, b.d_var, nq * k, k,
+                           db->count, b.d_cv);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     return ROAM_OK;
 }
 
@@ -248,6 +344,42 @@ int32_t loop_query_download(roam_ctx *ctx, const LoopQueryBufs &b, int nq, int k
     HIP_TRY(ctx, hipMemcpyAsync(cand_index, b.d_ci, sizeof(int32_t) * cands, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(cand_dist, b.d_cd, sizeof(double) * cands, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(cand_shift, b.d_cs, sizeof(int32_t) * cands, hipMemcpyDeviceToHost, ctx->stream));
+    return ROAM_OK;
+}
+
+// roam_loop_db_query and roam_loop_db_query_offsets: variants = the queries are the entries' variants as well (a database that keeps
+// offsets); cand_var / var_full: the winning variants, zero without variants
+static int32_t sc_query_run(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index, int32_t k,
+                            double max_distance, bool variants, int32_t *cand_index, double *cand_dist, int32_t *cand_shift, int32_t *cand_var,
+                            double *dist_full, int32_t *shift_full, int32_t *var_full)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const int count = db->count;
+    int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / loop_query_bytes(db, variants);
+    if (chunk < 1) chunk = 1;
+    const int64_t rows_per_query = variants ? db->n_off : 1;
+    if (chunk > 65535 * SC_QB / rows_per_query) chunk = 65535 * SC_QB / rows_per_query;     // the grid's y extent
+    const std::vector<int32_t> qm = loop_query_clamp(db, n_query, max_index);
+    const bool full = dist_full || shift_full || var_full;
+    for (int64_t q0 = 0; q0 < n_query; q0 += chunk) {
+        const int nq = (int)(n_query - q0 < chunk ? n_query - q0 : chunk);
+        const size_t pairs = (size_t)nq * count;
+        LoopQueryBufs b;
+        LOOP_TRY(loop_query_stage(ctx, db, nq, k, query_index + q0, qm.data() + q0, &b, variants));
+        LOOP_TRY(loop_query_enqueue(ctx, db, b, nq, k, max_distance, full));
+        LOOP_TRY(loop_query_download(ctx, b, nq, k, cand_index + q0 * k, cand_dist + q0 * k, cand_shift + q0 * k));
+        if (dist_full) HIP_TRY(ctx, hipMemcpyAsync(dist_full + q0 * count, b.d_dist, sizeof(double) * pairs, hipMemcpyDeviceToHost, st));
+        if (shift_full) HIP_TRY(ctx, hipMemcpyAsync(shift_full + q0 * count, b.d_shift, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, st));
+        if (variants) {
+            if (cand_var) HIP_TRY(ctx, hipMemcpyAsync(cand_var + q0 * k, b.d_cv, sizeof(int32_t) * (size_t)nq * k, hipMemcpyDeviceToHost, st));
+            if (var_full) HIP_TRY(ctx, hipMemcpyAsync(var_full + q0 * count, b.d_var, sizeof(int32_t) * pairs, hipMemcpyDeviceToHost, st));
+        } else {
+            if (cand_var) memset(cand_var + q0 * k, 0, sizeof(int32_t) * (size_t)nq * k);
+            if (var_full) memset(var_full + q0 * count, 0, sizeof(int32_t) * pairs);
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
     return ROAM_OK;
 }
 
@@ -261,24 +393,22 @@ extern "C" int32_t roam_loop_db_query(roam_ctx *ctx, roam_loop_db *db, int32_t n
         ROAM_SET_ERR(ctx, "loop db query: %s is null", !cand_index ? "cand_index" : !cand_dist ? "cand_dist" : "cand_shift");
         return ROAM_E_ARG;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = ctx->stream;
-    const int count = db->count;
-    int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / ((int64_t)(sizeof(double) + sizeof(int32_t)) * count);
-    if (chunk < 1) chunk = 1;
-    if (chunk > 65535 * SC_QB) chunk = 65535 * SC_QB;     // the grid's y extent
-    const std::vector<int32_t> qm = loop_query_clamp(db, n_query, max_index);
-    for (int64_t q0 = 0; q0 < n_query; q0 += chunk) {
-        const int nq = (int)(n_query - q0 < chunk ? n_query - q0 : chunk);
-        LoopQueryBufs b;
-        LOOP_TRY(loop_query_stage(ctx, db, nq, k, query_index + q0, qm.data() + q0, &b));
-        LOOP_TRY(loop_query_enqueue(ctx, db, b, nq, k, max_distance, dist_full || shift_full));
-        LOOP_TRY(loop_query_download(ctx, b, nq, k, cand_index + q0 * k, cand_dist + q0 * k, cand_shift + q0 * k));
-        if (dist_full) HIP_TRY(ctx, hipMemcpyAsync(dist_full + q0 * count, b.d_dist, sizeof(double) * (size_t)nq * count, hipMemcpyDeviceToHost, st));
-        if (shift_full) HIP_TRY(ctx, hipMemcpyAsync(shift_full + q0 * count, b.d_shift, sizeof(int32_t) * (size_t)nq * count, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
+    return sc_query_run(ctx, db, n_query, query_index, max_index, k, max_distance, false, cand_index, cand_dist, cand_shift, nullptr, dist_full,
+                        shift_full, nullptr);
+}
+
+extern "C" int32_t roam_loop_db_query_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index,
+                                              int32_t k, double max_distance, int32_t *cand_index, double *cand_dist, int32_t *cand_shift,
+                                              int32_t *cand_offset, double *dist_full, int32_t *shift_full, int32_t *offset_full)
+{
+    if (!ctx) return ROAM_E_ARG;
+    LOOP_TRY(sc_check_query(ctx, db, n_query, query_index, max_index, k, max_distance));
+    if (!cand_index || !cand_dist || !cand_shift || !cand_offset) {
+        ROAM_SET_ERR(ctx, "loop db query: %s is null", !cand_index ? "cand_index" : !cand_dist ? "cand_dist" : !cand_shift ? "cand_shift" : "cand_offset");
+        return ROAM_E_ARG;
     }
-    return ROAM_OK;
+    return sc_query_run(ctx, db, n_query, query_index, max_index, k, max_distance, db->n_off > 0, cand_index, cand_dist, cand_shift, cand_offset,
+                        dist_full, shift_full, offset_full);
 }
 
 extern "C" int32_t roam_time_loop_db_query(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index,
@@ -298,6 +428,29 @@ extern "C" int32_t roam_time_loop_db_query(roam_ctx *ctx, roam_loop_db *db, int3
     LoopQueryBufs b;
     LOOP_TRY(loop_query_stage(ctx, db, n_query, k, query_index, qm.data(), &b));
     LOOP_TRY(roam_time_launches(ctx, st, reps, distance_ms, [&] { return sc_launch_distance(st, db, b.d_q, b.d_qmax, n_query, b.d_dist, b.d_shift); }));
+    return roam_time_launches(ctx, st, reps, select_ms,
+                              [&] { return sc_launch_select(st, db, b.d_qmax, n_query, k, max_distance, b.d_dist, b.d_shift, b.d_ci, b.d_cd, b.d_cs); });
+}
+
+extern "C" int32_t roam_time_loop_db_query_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index,
+                                                   const int32_t *max_index, int32_t k, double max_distance, int32_t reps, float *plain_ms,
+                                                   float *variants_ms, float *select_ms)
+{
+    if (!ctx) return ROAM_E_ARG;
+    LOOP_TRY(sc_check_query(ctx, db, n_query, query_index, max_index, k, max_distance));
+    ARG_CHECK(ctx, reps >= 1 && plain_ms && variants_ms && select_ms);
+    if (!db->n_off) { ROAM_SET_ERR(ctx, "loop db timing: db keeps no offsets"); return ROAM_E_ARG; }
+    if (n_query * loop_query_bytes(db, true) > SC_DB_BYTES || (int64_t)n_query * db->n_off > 65535 * SC_QB) {
+        ROAM_SET_ERR(ctx, "loop db timing: %d queries against %d entries do not fit one launch", n_query, db->count);
+        return ROAM_E_ARG;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const std::vector<int32_t> qm = loop_query_clamp(db, n_query, max_index);
+    LoopQueryBufs b;
+    LOOP_TRY(loop_query_stage(ctx, db, n_query, k, query_index, qm.data(), &b, true));
+    LOOP_TRY(roam_time_launches(ctx, st, reps, plain_ms, [&] { return sc_launch_distance(st, db, b.d_q, b.d_qmax, n_query, b.d_dist, b.d_shift); }));
+    LOOP_TRY(roam_time_launches(ctx, st, reps, variants_ms, [&] { return sc_launch_variants(st, db, b, n_query, false); }));
     return roam_time_launches(ctx, st, reps, select_ms,
                               [&] { return sc_launch_select(st, db, b.d_qmax, n_query, k, max_distance, b.d_dist, b.d_shift, b.d_ci, b.d_cd, b.d_cs); });
 }

@@ -4,12 +4,15 @@
 // query form enqueues distance, selection, loop_pairs_kernel (candidates -> pairs and their yaw seeds) and the ICP on one stream.
 #include "loop.h"
 #include <cmath>
+#include <cstring>
 
 // ---------------------------------------------------------------------------------------------------------------- device
 // query_verify: slot (q, s) of the selection -> pair q k + s: the query's cloud onto the candidate's (-1: an empty pair) from
-// (yaw, 0, 0), yaw = 2 pi shift / S in (-pi, pi] by LoopClosure._yaw's operations
+// (yaw, 0, 0), yaw = 2 pi shift / S in (-pi, pi] by LoopClosure._yaw's operations.  cv (optional, a database that keeps offsets): the
+// slot's winning variant; variant a >= 1 with the offset o = off_m[a - 1] seeds (yaw, -R(yaw) o), variant 0 as before
 __global__ __launch_bounds__(SC_THREADS) void loop_pairs_kernel(const int32_t *__restrict__ qidx, const int32_t *__restrict__ ci,
-                                                                const int32_t *__restrict__ cs, int n_pairs, int k, int S,
+                                                                const int32_t *__restrict__ cs, const int32_t *__restrict__ cv,
+                                                                const double *__restrict__ off_m, int n_pairs, int k, int S,
                                                                 int32_t *__restrict__ src_index, int32_t *__restrict__ dst_index,
                                                                 double *__restrict__ init)
 {
@@ -18,9 +21,16 @@ __global__ __launch_bounds__(SC_THREADS) void loop_pairs_kernel(const int32_t *_
     src_index[p] = qidx[p / k];
     dst_index[p] = ci[p];
     const double a = (6.283185307179586 * (double)cs[p]) / (double)S;
-    init[3 * (int64_t)p] = a > 3.141592653589793 ? a - 6.283185307179586 : a;
-    init[3 * (int64_t)p + 1] = 0.0;
-    init[3 * (int64_t)p + 2] = 0.0;
+    const double yaw = a > 3.141592653589793 ? a - 6.283185307179586 : a;
+    double tx = 0.0, ty = 0.0;
+    if (cv && cv[p] > 0) {
+        const double ox = off_m[2 * (cv[p] - 1)], oy = off_m[2 * (cv[p] - 1) + 1], c = cos(yaw), s = sin(yaw);
+        tx = -(c * ox - s * oy);
+        ty = -(s * ox + c * oy);
+    }
+    init[3 * (int64_t)p] = yaw;
+    init[3 * (int64_t)p + 1] = tx;
+    init[3 * (int64_t)p + 2] = ty;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
@@ -136,9 +146,10 @@ extern "C" int32_t roam_time_loop_db_verify(roam_ctx *ctx, roam_loop_db *db, int
     return roam_time_launches(ctx, st, reps, ms_per_rep, [&] { return launch_icp2d_store(st, A, n_pairs); });
 }
 
-extern "C" int32_t roam_loop_db_query_verify(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index,
-                                             int32_t k, double max_distance, const roam_icp_opts *opts, int32_t *cand_index, double *cand_dist,
-                                             int32_t *cand_shift, double *pose_out, roam_icp_stats *stats)
+// roam_loop_db_query_verify and its _offsets form: cand_offset (optional) = the winning variants, zero for a database without offsets
+static int32_t sc_query_verify(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index, int32_t k,
+                               double max_distance, const roam_icp_opts *opts, int32_t *cand_index, double *cand_dist, int32_t *cand_shift,
+                               int32_t *cand_offset, double *pose_out, roam_icp_stats *stats)
 {
     if (!ctx) return ROAM_E_ARG;
     LOOP_TRY(sc_check_query(ctx, db, n_query, query_index, max_index, k, max_distance));
@@ -153,9 +164,10 @@ extern "C" int32_t roam_loop_db_query_verify(roam_ctx *ctx, roam_loop_db *db, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
     // queries per launch: the distance scratch, the pairs' scratch and the grids' extents
-    int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) /
-                    ((int64_t)(sizeof(double) + sizeof(int32_t)) * db->count + (int64_t)k * sc_pair_bytes(db));
+    const bool variants = db->n_off > 0;
+    int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / (loop_query_bytes(db, variants) + (int64_t)k * sc_pair_bytes(db));
     if (chunk > ROAM_ICP_MAX_PAIRS / k) chunk = ROAM_ICP_MAX_PAIRS / k;
+    if (variants && chunk > 65535 * SC_QB / db->n_off) chunk = 65535 * SC_QB / db->n_off;
     if (chunk < 1) chunk = 1;
     const std::vector<int32_t> qm = loop_query_clamp(db, n_query, max_index);
     for (int64_t q0 = 0; q0 < n_query; q0 += chunk) {
@@ -164,15 +176,35 @@ extern "C" int32_t roam_loop_db_query_verify(roam_ctx *ctx, roam_loop_db *db, in
         IcpStoreArgs A;
         LoopQueryBufs b;
         LOOP_TRY(sc_verify_scratch(ctx, db, np, o, &A));  // every take of the chunk comes before its first copy: a slot that grows waits for the stream
-        LOOP_TRY(loop_query_stage(ctx, db, nq, k, query_index + q0, qm.data() + q0, &b));
+        LOOP_TRY(loop_query_stage(ctx, db, nq, k, query_index + q0, qm.data() + q0, &b, variants));
         LOOP_TRY(loop_query_enqueue(ctx, db, b, nq, k, max_distance, false));
-        hipLaunchKernelGGL(loop_pairs_kernel, dim3((np + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st, b.d_q, b.d_ci, b.d_cs, np, k, db->S,
+        hipLaunchKernelGGL(loop_pairs_kernel, dim3((np + SC_THREADS - 1) / SC_THREADS), dim3(SC_THREADS), 0, st, b.d_q, b.d_ci, b.d_cs, b.d_cv, db->off_m,
+                           np, k, db->S,
                            (int32_t *)A.src_index, (int32_t *)A.dst_index, (double *)A.init);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, launch_icp2d_store(st, A, np));
         LOOP_TRY(loop_query_download(ctx, b, nq, k, cand_index + q0 * k, cand_dist + q0 * k, cand_shift + q0 * k));
         LOOP_TRY(sc_download_pairs(ctx, A, q0 * k, np, pose_out, stats));
+        if (cand_offset && variants) HIP_TRY(ctx, hipMemcpyAsync(cand_offset + q0 * k, b.d_cv, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
+        if (cand_offset && !variants) memset(cand_offset + q0 * k, 0, sizeof(int32_t) * (size_t)np);
         HIP_TRY(ctx, hipStreamSynchronize(st));           // the one wait of the chunk
     }
     return ROAM_OK;
+}
+
+extern "C" int32_t roam_loop_db_query_verify(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index,
+                                             int32_t k, double max_distance, const roam_icp_opts *opts, int32_t *cand_index, double *cand_dist,
+                                             int32_t *cand_shift, double *pose_out, roam_icp_stats *stats)
+{
+    return sc_query_verify(ctx, db, n_query, query_index, max_index, k, max_distance, opts, cand_index, cand_dist, cand_shift, nullptr, pose_out, stats);
+}
+
+extern "C" int32_t roam_loop_db_query_verify_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n_query, const int32_t *query_index,
+                                                     const int32_t *max_index, int32_t k, double max_distance, const roam_icp_opts *opts,
+                                                     int32_t *cand_index, double *cand_dist, int32_t *cand_shift, int32_t *cand_offset,
+                                                     double *pose_out, roam_icp_stats *stats)
+{
+    if (ctx && !cand_offset) { ROAM_SET_ERR(ctx, "loop db query: cand_offset is null"); return ROAM_E_ARG; }
+    return sc_query_verify(ctx, db, n_query, query_index, max_index, k, max_distance, opts, cand_index, cand_dist, cand_shift, cand_offset, pose_out,
+                           stats);
 }
