@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import oracle
+from det_candidate_cases import blob_payload as _blob_payload
 from test_oracle_reference_dump import FIX, W
 
 pytestmark = pytest.mark.gpu
@@ -266,25 +267,10 @@ def test_step_results_ring_does_not_drain_the_pipeline():
     ctx.close()
 
 
-def _blob_payload(clip, seed, rows=400):
-    """speckle + Gaussian blobs in (azimuth, range), a third of them at the far end of the range axis = along the borders of the
-    Cartesian image, where the box corners of the determinant are clipped"""
-    rng = np.random.default_rng(seed)
-    img = rng.exponential(6.0, size=(rows, clip))
-    for i in range(max(18, clip // 5)):
-        a, A = rng.uniform(0, rows), rng.uniform(80, 200)
-        r = rng.uniform(clip - 24, clip - 2) if i % 3 == 0 else rng.uniform(4, clip - 2)
-        sa, sr = max(1.5, 240.0 / max(r, 4.0)), rng.uniform(2.0, 7.0)
-        aa = np.arange(int(a - 4 * sa), int(a + 4 * sa) + 1)
-        rr = np.arange(max(0, int(r - 4 * sr)), min(clip, int(r + 4 * sr) + 1))
-        img[np.ix_(aa % rows, rr)] += A * np.exp(-0.5 * ((aa - a) / sa) ** 2)[:, None] * np.exp(-0.5 * ((rr - r) / sr) ** 2)[None, :]
-    return np.clip(np.floor(img), 0, 255).astype(np.uint8)
-
-
 @pytest.mark.parametrize("clip", [132, 300, 508, 1020])
 def test_detection_on_image_sizes_that_do_not_fill_the_strips(clip):
-    """the determinant kernel marches 126-column strips in steps of 32 rows: images of 132 ... 1020 pixels end inside a strip and
-    inside a step (last strip 6 ... 12 columns wide), most of their positions clip box corners at the border, and blobs sit on
+    """the determinant kernel marches 62-column strips in steps of 16 rows: images of 132 ... 1020 pixels end inside a strip and
+    inside a step (last strip 8 ... 52 columns wide), most of their positions clip box corners at the border, and blobs sit on
     the border itself - detections must equal the oracle's getFeatures"""
     from radarslampy_amd import _ffi
     from radarslampy_amd.engine import Engine
