@@ -556,6 +556,55 @@ int32_t roam_time_loop_db_query_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t
                                         const int32_t *max_index, int32_t k, double max_distance, int32_t reps, float *plain_ms,
                                         float *variants_ms, float *select_ms);
 
+/* ---- global map: the resident peak clouds binned at given poses (csrc/loop_map.hip).  The reference's Map.mapPoints is an empty list
+ * with a TODO beside it (Mapping.py: "a big array of map points in global coordinates") and Map.plot scatters global feature points;
+ * nothing there computes a map, so PARITY UNPINNED as the sections above; the contract is tests/global_map_model.py.
+ * In: a database that keeps clouds, `count` entries; poses (count, 3) rows x, y, theta - finite, |x| and |y| <= ROAM_ICP_MAX_COORD;
+ * use (count) int8, 0 leaves the entry out, NULL = every entry; the cell size res in metres; the extent: origin (ox, oy), W x H cells.
+ * Every operation below is one float64 operation rounded once.
+ * Pose table.  roam_map_pose_table (host only, no context): cs_out (n, 2) = (cos theta, sin theta) by the host's libm, as
+ * roam_polar_cloud_table; the device only multiplies with these values.  ROAM_E_ARG: n < 0, a null pointer, a theta that is not finite.
+ * World point of the stored point (px, py) of entry e: wx = ((c px) - (s py)) + x, wy = ((s px) + (c py)) + y.
+ * Cell.  dx = (wx - ox) / res, dy = (wy - oy) / res; the point is inside when 0 <= dx < W and 0 <= dy < H, compared in float64 before
+ * any conversion; then u = floor(dx), v = floor(dy), otherwise the point counts in n_outside.  dx - u is exact, and the sub-cell
+ * position is qx = floor((dx - u) * 65536.0) in [0, 65535]; qy likewise.
+ * Per cell, integers all, so that the result does not depend on the order of arrival: hits (uint32) the points that landed in it,
+ * views (uint32) the distinct entries that put at least one point there, sx, sy (uint64) the sums of qx and qy.
+ * Map points.  A cell qualifies when hits >= min_hits and views >= min_views (both >= 1); the qualifying cells in row-major order, v
+ * major, each as (cx, cy, hits, views): m = (2 sx + hits) / (131072.0 hits) (the numerator an exact integer below 2^53),
+ * cx = ox + res * (u + m), cy likewise.  More of them than cap: ROAM_E_CAPACITY, no point is written and *n_points_out is the count
+ * required.
+ * Automatic extent.  roam_loop_db_map_bounds: bounds_out = {min wx, max wx, min wy, max wy} over the used entries' points, exactly (a
+ * zero bound is +0), and *n_points_out their number; with no point the bounds are {+inf, -inf, +inf, -inf}.  roam_map_plan (host only,
+ * no context): ox = (floor(minx / res) - 1) * res, W = floor((maxx - ox) / res) + 2, the y side likewise - one cell of margin on each
+ * side, so that the rounding of ox cannot push a bounding point outside: with a planned extent n_outside is 0.  ROAM_E_ARG: a null
+ * pointer, bounds that are not finite, min > max, res not finite or <= 0, |floor(min / res)| > ROAM_MAP_MAX_INDEX (a cell so fine
+ * against the coordinates that the margin's two operations are no longer nearly exact).  ROAM_E_CAPACITY: W H > ROAM_MAP_MAX_CELLS
+ * (at 24 bytes per cell the grid stays under the 2000 MiB every other stage keeps to).
+ * roam_loop_db_map_render: the grid's clear, the splat (one workgroup per entry: the entry's cell keys sorted in LDS, a run of equal
+ * keys adds its length and its sums once and one view; integer atomics only), the compaction (a count per chunk of the row-major
+ * grid, an exclusive scan, the write) - enqueued on the context's stream with no host synchronisation between them - and the
+ * read-back: the two counters with hits_out / views_out ((H, W) each, either may be NULL), then the *n_points_out records the counters
+ * announce.  The grid is scratch of the call: the database keeps no map, and a database never asked for one is untouched.
+ * ROAM_E_STATE: the database keeps no clouds.  ROAM_E_ARG before any device call, the text naming the argument: null pointers
+ * (points_out, point_hits_out, point_views_out may be NULL when cap is 0), a pose that is not finite or beyond the limit, res not
+ * finite or <= 0, an origin that is not finite, W or H < 1, W H > ROAM_MAP_MAX_CELLS, a threshold < 1, cap < 0.  An empty database, or
+ * one with nothing used, gives an all-zero grid and no points.
+ * roam_time_loop_db_map: measurement as above (HIP events, two warm launches, `reps` timed) -> ms[3]: the clear, the splat and the
+ * compaction apart. */
+#define ROAM_MAP_MAX_CELLS (1 << 26)
+#define ROAM_MAP_MAX_INDEX 1125899906842624.0 /* 2^50 */
+int32_t roam_map_pose_table(int32_t n, const double *poses /* n x 3 */, double *cs_out /* n x 2 */);
+int32_t roam_map_plan(double minx, double maxx, double miny, double maxy, double res, double *ox, double *oy, int32_t *W, int32_t *H);
+int32_t roam_loop_db_map_bounds(roam_ctx *ctx, roam_loop_db *db, const double *poses /* count x 3 */, const int8_t *use /* count or NULL */,
+                                double *bounds_out /* 4 */, int64_t *n_points_out);
+int32_t roam_loop_db_map_render(roam_ctx *ctx, roam_loop_db *db, const double *poses, const int8_t *use, double res, double ox, double oy,
+                                int32_t W, int32_t H, int32_t min_hits, int32_t min_views, uint32_t *hits_out /* H x W */,
+                                uint32_t *views_out /* H x W */, double *points_out /* cap x 2 */, uint32_t *point_hits_out /* cap */,
+                                uint32_t *point_views_out /* cap */, int32_t cap, int32_t *n_points_out, int64_t *n_outside_out);
+int32_t roam_time_loop_db_map(roam_ctx *ctx, roam_loop_db *db, const double *poses, const int8_t *use, double res, double ox, double oy,
+                              int32_t W, int32_t H, int32_t min_hits, int32_t min_views, int32_t reps, float *ms /* 3 */);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous

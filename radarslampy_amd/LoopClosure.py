@@ -30,7 +30,12 @@ Resident clouds.  LoopDetector(keepClouds=True, rows=...) makes the database the
 (add, Engine.loop_db_add) leaves its polar peaks in metres beside its descriptor, built on the device at that moment - an engine's
 pool has forgotten the scan long before a revisit is recognised.  verify and queryAndVerify run the same ICP from that store, the
 second with no host round trip between the query and the verification; closeLoops uses it when the detector keeps clouds.  The
-rule of the stored points (every step-th peak, tables from the host's libm) is tests/loop_cloud_model.py."""
+rule of the stored points (every step-th peak, tables from the host's libm) is tests/loop_cloud_model.py.
+
+Global map.  The stored clouds are also what a map is made of: LoopDetector.renderMap takes one pose per entry and bins every entry's
+points in the world frame on the device (csrc/loop_map.hip) -> Mapping.GlobalMap, an occupancy grid (points and distinct keyframes per
+cell) and a thinned list of map points; mapFromGraph(detector, graph) is the step after closeLoops.  A closure moves every pose, so
+the map is rendered again after each; nothing of it is kept in the detector.  The definition is tests/global_map_model.py."""
 import numbers
 
 import numpy as np
@@ -168,6 +173,23 @@ class LoopDetector:
     def cloud(self, i):
         """-> (xy (n, 2) float64 metres: the stored cloud of entry i, the scan's full peak count)"""
         return self.db.get_cloud(i)
+
+    def renderMap(self, poses, cellM=0.5, extent=None, minHits=1, minViews=1, use=None, grids=True):
+        """The global map of the stored clouds (keepClouds) at poses (len(self), 3) rows x, y, theta -> Mapping.GlobalMap: every
+        entry's points in the world frame, binned into cells of cellM metres on the device (csrc/loop_map.hip; the definition is
+        tests/global_map_model.py).  extent (ox, oy, W, H): the corner of cell (0, 0) in metres and the grid's size in cells; None:
+        the points' bounding box with one cell of margin (bounds, plan, then the render; an empty map is 1 x 1 at the origin).  A
+        map point is the mean position of a cell with at least minHits points from at least minViews entries.  use (len(self),): zero
+        leaves an entry out.  grids=False: the two (H, W) grids are not read back"""
+        from .Mapping import GlobalMap
+        if not self.keepClouds:
+            raise ValueError("LoopDetector.renderMap: the detector keeps no clouds (keepClouds=True)")
+        p, u, res, extent, minHits, minViews = _ffi.loop_map_args(len(self.db), poses, use, cellM, extent, minHits, minViews)
+        if extent is None:
+            b, n = self.db.map_bounds(p, u)
+            extent = _ffi.map_plan(b, res) if n else (0.0, 0.0, 1, 1)
+        r = self.db.map_render(p, res, extent, minHits, minViews, u, grids)
+        return GlobalMap(extent[:2], res, (extent[3], extent[2]), r["hits"], r["views"], r["points"], r["point_hits"], r["point_views"], r["outside"])
 
     def verify(self, queryIndex, candIndex, candYaw, candOffset=None, **verify):
         """verifyCandidates from the stored clouds: the arguments, keywords and results are verifyCandidates' without `clouds`.
@@ -402,6 +424,14 @@ def closeLoops(keyframes, detector, clouds=None, *, rows=None, rangeResolutionM=
     ci, _, yaw = detector.query(idx)
     edges, table = verifyCandidates(clouds, idx, ci, yaw, **verify)
     return _optimise(keyframes, edges, table, loopInformation, huber, odomInformation, max_iterations, ctx)
+
+
+def mapFromGraph(detector, graph, **renderMap):
+    """The step after closeLoops: the global map of the detector's stored clouds at the graph's poses, graph.get_pose(k) for entry
+    k < len(detector) -> Mapping.GlobalMap.  renderMap: LoopDetector.renderMap's keywords (cellM, extent, minHits, minViews, use, grids)"""
+    n = len(detector)
+    poses = np.array([graph.get_pose(k) for k in range(n)], np.float64).reshape(n, 3)
+    return detector.renderMap(poses, **renderMap)
 
 
 def _optimise(keyframes, edges, table, loopInformation, huber, odomInformation, max_iterations, ctx):

@@ -57,6 +57,33 @@ class Map():
         self.keyframes.append(keyframe)
 
 
+class GlobalMap():
+    """What the reference's Map.mapPoints was meant to become ("a big array of map points in global coordinates", an empty list there):
+    the keyframes' polar peaks in one world frame, binned on a grid.  A plain result object, made by LoopDetector.renderMap /
+    LoopClosure.mapFromGraph (csrc/loop_map.hip; the definition is include/roam_abi.h's "global map" and tests/global_map_model.py).
+    hits, views (H, W) uint32: the points in a cell and the distinct keyframes that put one there (None when rendered with
+    grids=False); origin (ox, oy) metres: the corner of cell (0, 0); cellM: the cell size; shape = (H, W); points (M, 2) float64: the
+    mean position of the points of every qualifying cell, row-major (v major), with pointHits, pointViews (M,) uint32; outside: the
+    points that fell outside the extent."""
+
+    def __init__(self, origin, cellM, shape, hits, views, points, pointHits, pointViews, outside) -> None:
+        self.origin, self.cellM, self.shape = (float(origin[0]), float(origin[1])), float(cellM), (int(shape[0]), int(shape[1]))
+        self.hits, self.views = hits, views
+        self.points, self.pointHits, self.pointViews = points, pointHits, pointViews
+        self.outside = int(outside)
+
+    @property
+    def nPoints(self) -> int:
+        return len(self.points)
+
+    def cellOf(self, xy) -> np.ndarray:
+        """world points (n, 2) metres -> (n, 2) int64 rows (u, v) = floor((x - ox) / cellM), floor((y - oy) / cellM), each operation in
+        float64: the column and the row of hits / views that a point lands in.  A point outside the extent gives a u outside [0, W) or
+        a v outside [0, H) - floor, not truncation, so just below the origin is -1"""
+        a = np.asarray(xy, np.float64).reshape(-1, 2)
+        return np.floor((a - np.array(self.origin)) / self.cellM).astype(np.int64)
+
+
 class DeviceMap():
     """the keyframes of one engine lane, resident in HBM (roam_engine_map_*).  Read-only view with the
     reference's attribute names; `keyframes[-1]` is the live keyframe the tracker is pruning."""

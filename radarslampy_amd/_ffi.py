@@ -86,6 +86,7 @@ SCAN_CONTEXT_MAX_ROWS, SCAN_CONTEXT_MAX_CLIP = 65536, 4096
 LOOP_MAX_K = 32                         # roam_abi.h ROAM_LOOP_MAX_K
 LOOP_MAX_OFFSETS = 48                   # roam_abi.h ROAM_LOOP_MAX_OFFSETS
 LOOP_DB_BYTES = 2000 << 20              # a database, and the device scratch of one launch
+MAP_MAX_CELLS = 1 << 26                 # roam_abi.h ROAM_MAP_MAX_CELLS: the cells of a global map's grid
 
 
 PRIOR_RECORD = np.dtype([("out6", np.float64, (6,)), ("affine", np.float32, (2, 3)), ("source", np.uint8)])     # Engine.step_prior's rows
@@ -179,6 +180,14 @@ _SIGS = {
     "roam_engine_time_loop_offsets": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _P(C.c_float)]),
     "roam_time_loop_db_query_offsets": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _P(C.c_float), _P(C.c_float),
                                                     _P(C.c_float)]),
+    "roam_map_pose_table": (C.c_int32, [C.c_int32, _vp, _vp]),
+    "roam_map_plan": (C.c_int32, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P(C.c_double), _P(C.c_double), _P(C.c_int32),
+                                  _P(C.c_int32)]),
+    "roam_loop_db_map_bounds": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, _P(C.c_int64)]),
+    "roam_loop_db_map_render": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                            _vp, _vp, _vp, _vp, C.c_int32, _P(C.c_int32), _P(C.c_int64)]),
+    "roam_time_loop_db_map": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, _vp]),
     "roam_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), _vp, _vp]),
     "roam_time_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), C.c_int32, _P(C.c_float)]),
     "roam_engine_create": (C.c_int32, [_vp, _P(EngineCfg)]),
@@ -732,6 +741,73 @@ def loop_verify_args(count, src_index, dst_index, init):
     if not (np.all(np.isfinite(x0)) and np.all(np.abs(x0[:, 1:]) <= ICP_MAX_COORD)):
         raise ValueError(f"loop verify: an initial pose that is not finite or beyond {ICP_MAX_COORD:g} m")
     return si, di, np.ascontiguousarray(x0)
+
+
+def map_pose_table(poses):
+    """roam_map_pose_table, host code only (no device, no context): poses (n, 3) rows x, y, theta -> (n, 2) float64 rows (cos theta,
+    sin theta) by the host's libm - the values a global map's kernels multiply with.  ValueError: not (n, 3), a theta that is not finite"""
+    p = np.ascontiguousarray(poses, np.float64)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"global map: poses (n, 3) rows x, y, theta, not {p.shape}")
+    cs = np.empty((len(p), 2), np.float64)
+    if load_library().roam_map_pose_table(len(p), _ptr(p), _ptr(cs)) != ROAM_OK:
+        raise ValueError("global map: poses with a theta that is not finite")
+    return cs
+
+
+def map_plan(bounds, res):
+    """roam_map_plan, host code only: bounds (min x, max x, min y, max y) metres and the cell size -> (ox, oy, W, H), the extent with one
+    cell of margin on each side.  ValueError: bounds that are not finite or min > max, res not finite or <= 0, a cell too fine for the
+    coordinates, more than MAP_MAX_CELLS cells"""
+    b = np.asarray(bounds, np.float64).ravel()
+    if b.shape != (4,):
+        raise ValueError(f"global map: bounds (min x, max x, min y, max y), not shape {np.shape(bounds)}")
+    if not isinstance(res, numbers.Real) or isinstance(res, bool):
+        raise ValueError(f"global map: res finite and > 0, not {res!r}")
+    ox, oy, W, H = C.c_double(0), C.c_double(0), C.c_int32(0), C.c_int32(0)
+    rc = load_library().roam_map_plan(b[0], b[1], b[2], b[3], float(res), C.byref(ox), C.byref(oy), C.byref(W), C.byref(H))
+    if rc == ROAM_E_CAPACITY:
+        raise ValueError(f"global map: bounds {b.tolist()} at res {res} take more than W H = {MAP_MAX_CELLS} cells")
+    if rc != ROAM_OK:
+        raise ValueError(f"global map: finite bounds with min <= max and a res finite, > 0 and not below 2^-50 of them, not {b.tolist()} and {res!r}")
+    return ox.value, oy.value, W.value, H.value
+
+
+def loop_map_args(count, poses, use=None, res=0.5, extent=None, min_hits=1, min_views=1):
+    """the checks of LoopDb.map_bounds / map_render before any library call -> (poses (count, 3) float64, use (count,) int8 or None,
+    res, extent (ox, oy, W, H) or None, min_hits, min_views)"""
+    p = np.asarray(poses)
+    if p.dtype.kind not in "fiu":
+        raise ValueError(f"global map: poses of numbers, not {p.dtype}")
+    if p.size == 0 and count == 0:
+        p = p.reshape(0, 3)
+    if p.shape != (count, 3):
+        raise ValueError(f"global map: poses ({count}, 3) rows x, y, theta - one per entry - not {p.shape}")
+    p = np.ascontiguousarray(p, np.float64)
+    if not (np.all(np.isfinite(p)) and np.all(np.abs(p[:, :2]) <= ICP_MAX_COORD)):
+        raise ValueError(f"global map: poses with an entry that is not finite or beyond {ICP_MAX_COORD:g} m")
+    if use is not None:
+        u = np.asarray(use)
+        if u.dtype.kind not in "biu" or u.shape != (count,):
+            raise ValueError(f"global map: use ({count},) flags - one per entry - not {u.dtype} {u.shape}")
+        use = np.ascontiguousarray(u != 0, np.int8)
+    if not isinstance(res, numbers.Real) or isinstance(res, bool) or not np.isfinite(res) or not res > 0:
+        raise ValueError(f"global map: res finite and > 0, not {res!r}")
+    if extent is not None:
+        if len(extent) != 4:
+            raise ValueError(f"global map: extent (ox, oy, W, H), not {extent!r}")
+        ox, oy, W, H = extent
+        if not all(isinstance(v, numbers.Real) and not isinstance(v, bool) and np.isfinite(v) for v in (ox, oy)):
+            raise ValueError(f"global map: extent origin ox, oy finite, not {ox!r}, {oy!r}")
+        if not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and v >= 1 for v in (W, H)):
+            raise ValueError(f"global map: extent W and H integers >= 1, not {W!r} and {H!r}")
+        if W * H > MAP_MAX_CELLS:
+            raise ValueError(f"global map: extent W H = {W * H} cells, more than {MAP_MAX_CELLS}")
+        extent = (float(ox), float(oy), int(W), int(H))
+    for name, v in (("min_hits", min_hits), ("min_views", min_views)):
+        if not isinstance(v, numbers.Integral) or isinstance(v, bool) or not 1 <= v < 2 ** 31:
+            raise ValueError(f"global map: {name} an integer >= 1, not {v!r}")
+    return p, use, float(res), extent, int(min_hits), int(min_views)
 
 
 def icp2d_opts(opts=None):
@@ -1552,6 +1628,53 @@ class LoopDb:
         self.ctx.check(self.ctx.lib.roam_loop_db_query_verify(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance), C.byref(o),
                                                               _ptr(ci), _ptr(cd), _ptr(cs), _ptr(poses), _ptr(stats)))
         return ci, cd, cs, poses, stats
+
+    # ---- the global map
+    def map_bounds(self, poses, use=None):
+        """roam_loop_db_map_bounds: (bounds (4,) float64 = min x, max x, min y, max y of the used entries' points at these poses, their
+        number); no point: (+inf, -inf, +inf, -inf), 0"""
+        self._needs_clouds()
+        p, u, _, _, _, _ = loop_map_args(len(self), poses, use)
+        b, n = np.empty(4, np.float64), C.c_int64(0)
+        self.ctx.check(self.ctx.lib.roam_loop_db_map_bounds(self.ctx.h, self.h, _ptr(p), _ptr(u), _ptr(b), C.byref(n)))
+        return b, n.value
+
+    def map_render(self, poses, res, extent, min_hits=1, min_views=1, use=None, grids=True, cap=None):
+        """roam_loop_db_map_render on the extent (ox, oy, W, H) -> dict: hits, views (H, W) uint32 (None without grids), points (M, 2)
+        float64, point_hits, point_views (M,) uint32, outside.  cap (None: as many as there can be - the cells, or the used entries'
+        points if those are fewer): more map points than that raise RoamError ROAM_E_CAPACITY, its .required the count"""
+        self._needs_clouds()
+        p, u, res, extent, min_hits, min_views = loop_map_args(len(self), poses, use, res, extent, min_hits, min_views)
+        if extent is None:
+            raise ValueError("global map: extent (ox, oy, W, H), not None")
+        ox, oy, W, H = extent
+        if cap is None:
+            n = self.cloud_counts()[0].astype(np.int64)
+            cap = int(min(W * H, n.sum() if u is None else n[u != 0].sum()))
+        if not isinstance(cap, numbers.Integral) or isinstance(cap, bool) or not 0 <= cap < 2 ** 31:
+            raise ValueError(f"global map: cap an integer >= 0, not {cap!r}")
+        hits, views = (np.empty((H, W), np.uint32), np.empty((H, W), np.uint32)) if grids else (None, None)
+        pts, ph, pv = np.empty((cap, 2), np.float64), np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+        m, outside = C.c_int32(0), C.c_int64(0)
+        rc = self.ctx.lib.roam_loop_db_map_render(self.ctx.h, self.h, _ptr(p), _ptr(u), res, ox, oy, W, H, min_hits, min_views, _ptr(hits),
+                                                  _ptr(views), _ptr(pts), _ptr(ph), _ptr(pv), int(cap), C.byref(m), C.byref(outside))
+        if rc == ROAM_E_CAPACITY:
+            err = RoamError(rc, self.ctx.lib.roam_last_error(self.ctx.h).decode(errors="replace"))
+            err.required = m.value
+            raise err
+        self.ctx.check(rc)
+        return dict(hits=hits, views=views, points=pts[:m.value].copy(), point_hits=ph[:m.value].copy(), point_views=pv[:m.value].copy(),
+                    outside=outside.value)
+
+    def time_map(self, poses, res, extent, min_hits=1, min_views=1, use=None, reps=5):
+        """(clear ms, splat ms, compaction ms) per launch of this render's three parts (roam_time_loop_db_map)"""
+        self._needs_clouds()
+        p, u, res, extent, min_hits, min_views = loop_map_args(len(self), poses, use, res, extent, min_hits, min_views)
+        if extent is None:
+            raise ValueError("global map: extent (ox, oy, W, H), not None")
+        ms = (C.c_float * 3)()
+        self.ctx.check(self.ctx.lib.roam_time_loop_db_map(self.ctx.h, self.h, _ptr(p), _ptr(u), res, *extent, min_hits, min_views, int(reps), ms))
+        return tuple(float(v) for v in ms)
 
     def time_query(self, indices, max_index, k=8, max_distance=np.inf, reps=20):
         """(distance kernel ms, selection kernel ms) per launch of this query, HIP events around reps launches (roam_time_loop_db_query)"""

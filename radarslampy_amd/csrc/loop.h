@@ -13,10 +13,14 @@
 //   loop_offset.hip    the origin-shifted variants of an entry (Scan Context++): scan_context_offset_kernel and its finishing kernel,
 //                      the variant store (roam_loop_db_keep_offsets, set_variants, get_variants), roam_scan_context_offset_table,
 //                      roam_scan_context_offsets_f32; loop_query.hip reads the store as its queries, loop_verify.hip seeds from it
+//   loop_map.hip       the global map from the resident clouds at given poses: map_bounds_kernel, map_splat_kernel, the compaction
+//                      (map_count_kernel, map_scan_kernel, map_write_kernel); roam_map_pose_table, roam_map_plan,
+//                      roam_loop_db_map_bounds, roam_loop_db_map_render, roam_time_loop_db_map.  It reads the database and writes
+//                      scratch of the context only; no other unit calls into it
 //   icp.hip            the ICP of a pair of stored clouds (icp2d_store_kernel), which loop_verify.hip launches
 // engine_lanes.hip describes the engine's pool (LoopPool) and calls the record entries.  The reference has no place recognition (a
 // commented-out "import m2dp" at Mapping.py:7 and an unused Keyframe.pointCloud at :61-62), so parity is unpinned: the contracts are
-// tests/scan_context_model.py, tests/loop_cloud_model.py and tests/scan_context_offset_model.py.
+// tests/scan_context_model.py, tests/loop_cloud_model.py, tests/scan_context_offset_model.py and tests/global_map_model.py.
 #pragma once
 #include "roam_internal.h"
 #include <vector>
