@@ -173,9 +173,13 @@ int32_t roam_pyr_down_u8(roam_ctx *ctx, const uint8_t *src, int32_t w, int32_t h
  * |d_prev - d_next| <= thr_px consistency graph; when several maximum cliques exist, the one
  * the reference returns: the first strictly-largest clique in networkx.find_cliques order
  * (outlierRejection.py:63-75; CPython set order restated on the device, csrc/clique.hip).
- * node_limit bounds the branch-and-bound (0 = default); *flags_out bit0 = search completed
- * (result proven maximum and equal to the reference's; otherwise the best clique found). adj_out (optional) receives
- * the K x ((K+63)/64) uint64 adjacency bit rows. */
+ * node_limit bounds the search nodes counted over the whole call (0 = default, 300 000): first the search for the
+ * clique number and one maximum clique (the witness), then the existence queries that single out the reference's
+ * clique.  *flags_out bit0 = search completed: the mask is proven maximum and equal to the reference's.  Bit0 clear,
+ * the budget ran out: inside the first search the mask is the largest clique completed so far - EMPTY (n_inliers 0)
+ * when no descent had reached a leaf yet; after it the mask is the witness, a maximum clique that need not be the
+ * reference's.  The mask is a clique of the graph and *n_inliers its count in every case
+ * (tests/clique_budget_model.py).  adj_out (optional) receives the K x ((K+63)/64) uint64 adjacency bit rows. */
 int32_t roam_reject_outliers(roam_ctx *ctx, const float *prev, const float *next, int32_t K,
                              double thr_px, int64_t node_limit, uint8_t *mask_out,
                              int32_t *n_inliers, int32_t *flags_out, uint64_t *adj_out);
@@ -620,7 +624,8 @@ typedef struct roam_engine_cfg {
     int32_t peaks_cap;        /* per-lane capacity of the peak list                       */
     int32_t reject_outliers;  /* paramFlags["rejectOutliers"] (Tracker.py:93)             */
     int32_t motion_distortion;/* 1: LM pose (RawROAMSystem.py:208-237); 0: Kabsch dead reckoning (:236,301-317) */
-    int64_t clique_node_limit;
+    int64_t clique_node_limit;/* roam_reject_outliers' node_limit for every lane (0 = default): a lane short of nodes takes
+                                 the unproven mask - possibly empty - as its inliers, bit0 of its flags clear */
     double sigma5[5];
     int32_t retrack_on_device;/* 1: lanes that run out of features (<= 60 inliers, RawROAMSystem.py:250-271) re-detect
                                  (appendNewFeatures: DoH blobs + ANMS, getFeatures.py:74-118) inside roam_engine_step */
