@@ -4,7 +4,8 @@ start of the search, cv2.calcOpticalFlowPyrLK's OPTFLOW_USE_INITIAL_FLOW.  OpenC
 level only, nextPt = init_pts * 2^-maxLevel in place of prevPt; everything else is the unseeded tracker.
 
 Unseeded it is tied to the oracle bit for bit by tests/test_klt_flow_cpu.py; apply_affine is the float32 order in which the kernel
-turns a lane's affine prior into guesses."""
+turns a lane's affine prior into guesses.  An optional trace says which branch each (point, level) took and how large its window sums
+were (tests/klt_branch_cases.py); the tile bookkeeping in it restates klt_kernel's rule and takes no part in any result."""
 import numpy as np
 
 F = np.float32
@@ -106,8 +107,54 @@ def _ifloor(v):
     return int(np.floor(v))
 
 
-def track_on_pyramids(pp, npyr, pts, init_pts=None):
-    """-> (nextPts (K, 2) f32, status (K, 1) u8, err (K, 1) f32); init_pts (K, 2) or None"""
+def _wsum(p, what):
+    """an exact window sum (Python int) of the normal matrix (what = "A") or the mismatch vector ("b"): the one place a test swaps for
+    narrower arithmetic, to see that its cases would notice"""
+    return int(p.sum())
+
+
+GROUP_ROWS = ((0, 4), (4, 8), (8, 12), (12, 15))      # window rows summed in 32 bits by one 16-lane DPP row of klt_kernel
+SUM_NAMES = ("IxIx", "IxIy", "IyIy", "dIx", "dIy")
+TILE = 32                                              # klt_kernel's cached neighbourhood of the next image
+TILE_KEEP = 15                                         # the tile is kept while 0 <= inx - tx0 <= TILE_KEEP, likewise in y
+
+
+def _note_sums(e, names, prods):
+    """largest |sum| per 4-window-row group and over the whole window, kept in the trace entry e"""
+    for name, p in zip(names, prods):
+        g = max(abs(int(p[a:b].sum())) for a, b in GROUP_ROWS)
+        e["group"][name] = max(e["group"][name], g)
+        e["whole"][name] = max(e["whole"][name], abs(int(p.sum())))
+
+
+def _tile_sides(tx0, ty0, w, h):
+    """the sides on which a TILE x TILE tile at (tx0, ty0) leaves a w x h image: empty = load_j_tile's interior path"""
+    return frozenset(n for n, out in (("left", tx0 < 0), ("right", tx0 + TILE > w), ("top", ty0 < 0), ("bottom", ty0 + TILE > h)) if out)
+
+
+def _tile_step(e, tile, ix, iy, w, h):
+    """klt_kernel's tile rule restated (trace only): reload with origin (ix - 8, iy - 8) unless the window origin is 0 ... 15 from the
+    cached one; -> (tile origin, the directions in which the window left the old tile: None = kept, () = the level's first load)"""
+    if tile is not None and 0 <= ix - tile[0] <= TILE_KEEP and 0 <= iy - tile[1] <= TILE_KEEP:
+        return tile, None
+    dirs = ()
+    if tile is not None:
+        dirs = tuple(n for n, out in (("+x", ix - tile[0] > TILE_KEEP), ("-x", ix < tile[0]), ("+y", iy - tile[1] > TILE_KEEP),
+                                      ("-y", iy < tile[1])) if out)
+    tile = (ix - 8, iy - 8)
+    e["tiles"].append(_tile_sides(tile[0], tile[1], w, h))
+    return tile, dirs
+
+
+def track_on_pyramids(pp, npyr, pts, init_pts=None, trace=None):
+    """-> (nextPts (K, 2) f32, status (K, 1) u8, err (K, 1) f32); init_pts (K, 2) or None.
+    trace: None, or a list that receives one dict per (point, level), levels from the top down, which changes no result:
+      k, level; exit: "prev_outside", "mineig", "d_only" (minEig passes, D < FLT_EPSILON), "eps0" (|d|^2 <= eps^2 at j == 0), "eps"
+      (at j >= 1), "backoff", "maxiter" or "left" (the window left the image in mid-iteration); iters: mismatch vectors formed;
+      reloads: per reload after the level's first load, the directions in which the window left the tile; tiles: per loaded tile, the
+      sides on which it leaves the image (empty: interior path), the error patch's load included; err_reload: the error patch needed a
+      load; err_outside: the final position was outside the image after iterations inside it; group / whole: largest |sum| of SUM_NAMES
+      per group of GROUP_ROWS and over the window"""
     pts = np.ascontiguousarray(pts, F).reshape(-1, 2)
     K = len(pts)
     guess = pts if init_pts is None else np.ascontiguousarray(init_pts, F).reshape(-1, 2)
@@ -132,6 +179,11 @@ def track_on_pyramids(pp, npyr, pts, init_pts=None):
             else:
                 nx, ny = nxt[k, 0] * two, nxt[k, 1] * two
             nxt[k] = (nx, ny)
+            e = None
+            if trace is not None:
+                e = dict(k=k, level=level, exit="prev_outside", iters=0, reloads=[], tiles=[], err_reload=False, err_outside=False,
+                         group=dict.fromkeys(SUM_NAMES, 0), whole=dict.fromkeys(SUM_NAMES, 0))
+                trace.append(e)
             px, py = px - half, py - half
             ipx, ipy = _ifloor(px), _ifloor(py)
             if ipx < -WIN or ipx >= w or ipy < -WIN or ipy >= h:
@@ -143,12 +195,15 @@ def track_on_pyramids(pp, npyr, pts, init_pts=None):
             Iv = _bilin(_patch(I, ipx, ipy, WIN + 1), iw, W_BITS - 5)
             Ix = _bilin(_patch_zero(Dx, ipx, ipy, WIN + 1), iw, W_BITS)
             Iy = _bilin(_patch_zero(Dy, ipx, ipy, WIN + 1), iw, W_BITS)
-            A11 = F(int((Ix * Ix).sum())) * FLT_SCALE
-            A12 = F(int((Ix * Iy).sum())) * FLT_SCALE
-            A22 = F(int((Iy * Iy).sum())) * FLT_SCALE
+            A11 = F(_wsum(Ix * Ix, "A")) * FLT_SCALE
+            A12 = F(_wsum(Ix * Iy, "A")) * FLT_SCALE
+            A22 = F(_wsum(Iy * Iy, "A")) * FLT_SCALE
             D = A11 * A22 - A12 * A12
             dA = A11 - A22
             minEig = (A22 + A11 - np.sqrt(dA * dA + four * A12 * A12)) / F(2 * WIN * WIN)
+            if e is not None:
+                _note_sums(e, SUM_NAMES[:3], (Ix * Ix, Ix * Iy, Iy * Iy))
+                e["exit"] = "mineig" if minEig < MIN_EIG else "d_only" if D < F(1.1920929e-07) else "maxiter"
             if minEig < MIN_EIG or D < F(1.1920929e-07):
                 if level == 0:
                     status[k] = 0
@@ -156,25 +211,39 @@ def track_on_pyramids(pp, npyr, pts, init_pts=None):
             D = F(1.0) / D
             nx, ny = nx - half, ny - half
             pdx = pdy = F(0.0)
+            tile = None
             for j in range(MAX_ITER):
                 inx, iny = _ifloor(nx), _ifloor(ny)
                 if inx < -WIN or inx >= w or iny < -WIN or iny >= h:
                     if level == 0:
                         status[k] = 0
+                    if e is not None:
+                        e["exit"] = "left"
                     break
+                if e is not None:
+                    tile, dirs = _tile_step(e, tile, inx, iny, w, h)
+                    if dirs:
+                        e["reloads"].append(dirs)
                 jw = _weights(nx - F(inx), ny - F(iny))
                 diff = _bilin(_patch(J, inx, iny, WIN + 1), jw, W_BITS - 5) - Iv
-                b1 = F(int((diff * Ix).sum())) * FLT_SCALE
-                b2 = F(int((diff * Iy).sum())) * FLT_SCALE
+                if e is not None:
+                    e["iters"] = j + 1
+                    _note_sums(e, SUM_NAMES[3:], (diff * Ix, diff * Iy))
+                b1 = F(_wsum(diff * Ix, "b")) * FLT_SCALE
+                b2 = F(_wsum(diff * Iy, "b")) * FLT_SCALE
                 dx = (A12 * b2 - A22 * b1) * D
                 dy = (A12 * b1 - A11 * b2) * D
                 nx, ny = nx + dx, ny + dy
                 nxt[k] = (nx + half, ny + half)
                 if dx * dx + dy * dy <= eps2:
+                    if e is not None:
+                        e["exit"] = "eps0" if j == 0 else "eps"
                     break
                 if j > 0 and abs(dx + pdx) < F(0.01) and abs(dy + pdy) < F(0.01):
                     nxt[k, 0] -= dx * half_f
                     nxt[k, 1] -= dy * half_f
+                    if e is not None:
+                        e["exit"] = "backoff"
                     break
                 pdx, pdy = dx, dy
             if status[k] and level == 0:
@@ -182,7 +251,12 @@ def track_on_pyramids(pp, npyr, pts, init_pts=None):
                 iex, iey = _ifloor(ex), _ifloor(ey)
                 if iex < -WIN or iex >= w or iey < -WIN or iey >= h:
                     status[k] = 0
+                    if e is not None:
+                        e["err_outside"] = True
                     continue
+                if e is not None:
+                    assert tile is not None                 # status 1 at level 0: an iteration ran and loaded a tile
+                    e["err_reload"] = _tile_step(e, tile, iex, iey, w, h)[1] is not None
                 ew = _weights(ex - F(iex), ey - F(iey))
                 diff = _bilin(_patch(J, iex, iey, WIN + 1), ew, W_BITS - 5) - Iv
                 err[k] = F(int(np.abs(diff).sum())) * (F(1.0) / F(32 * WIN * WIN))
