@@ -39,8 +39,10 @@ __device__ __forceinline__ void rt_push_maxima(const RtArgs &a, int ls, int r, i
 //     offsets in registers, so the strips along the left / right image border run the same code as interior ones; rows need clipping
 //     in the first and the last steps only (a variant with computed row offsets).  The dxy boxes (where dxx * dyy can pass the
 //     threshold: ~4 % of the wave-rows) compute their addresses on the fly.
-//   * the 16 boxes of a thread and step are ONE stream of 8 pairs, the reads of pair i + 1 issued before the arithmetic of pair i
-//     (sd_tile_fast); max(0, box) is the clamp modifier of the box's last subtraction (the ring holds the image scaled by 2^-10).
+//   * the boxes of a thread and step are ONE stream of pairs, the reads of pair i + 1 issued before the arithmetic of pair i, and the
+//     xx-side pair of a layer is read only by the waves in which a bound from dyy and the xx-mid box cannot rule dxx * dyy > threshold
+//     out (sd_tile_fast: three waves in four skip it on the benchmark's scene); max(0, box) is the clamp modifier of the box's last subtraction (the ring
+//     holds the image scaled by 2^-10).
 //   * workgroup -> strip mapping is XCD-aware: the strips of a detection are consecutive workgroups of ONE XCD, started together
 //     and marching in step, so that the cache lines neighbouring strips share come from that XCD's L2 (hit rate 25 %).
 //   * a step whose window lies beyond the maximum range - the corners of the image - skips its boxes, and the blocks only such steps
@@ -85,17 +87,42 @@ __device__ __forceinline__ double sd_ldr(const uint32_t (&ca)[12], const uint32_
 }
 
 // dxx * dyy (hessian_det_pruned's first product) of a thread's two positions in a step whose box rows need no clipping; PH = step & 3.
-// The 16 boxes are ONE stream of 8 pairs (the same box of both positions): the eight corner reads of pair i + 1 are issued before the
+// The boxes are ONE stream of pairs (the same box of both positions): the eight corner reads of pair i + 1 are issued before the
 // arithmetic of pair i (the compiler's own order waited for every box's reads before it issued the next four), and the two
 // positions' dependent float64 chains alternate instruction by instruction, so that a wave that is alone on its SIMD - the tail of
 // every step: the hardware favours the oldest wave, the youngest finish last - still issues back to back.
+//
+// The xx-side box is read only where a bound cannot rule the product out.  A product at or below the threshold is used for one fact only,
+// that it is at or below the threshold (rt_det_strip_kernel: no dxy term, no candidate, nothing a passing neighbour could not exceed), and
+// most of that fact is known before the last box is read: the side box lies inside its mid box and every box sum is clamped at 0, so
+// mid - 3 side lies in [-2 mid, mid] and dxx = -(mid - 3 side) w_i in [-mid w_i, 2 mid w_i].  With dyy exact (the bound from an exact dyy
+// rules out more than the one from an exact dxx: profiles/det_screen_rate.py) and the product positive, dxx dyy > thr needs
+//     |dyy| k mid_xx w_i > thr,    k = 2 where dyy > 0 (dxx > 0: side > mid / 3), k = 1 where dyy < 0 (dxx < 0: side < mid / 3).
+// The stream is therefore, per layer, yy-mid, yy-side, xx-mid - six pairs, read ahead as before - and then the xx-side pair of a layer
+// only if some lane of the wave, for either of its positions, is not ruled out (one ballot per layer; layer 15's is taken while layer
+// 30's reads are in flight).  A layer the wave skips holds 0.0, as a dark step's positions do.
+// The margin - a position is ruled out only if  fl(fl(|dyy| mid_xx) c_k) <= fl(thr - SD_SKIP_ABS),  c_k = fl(k w_i (1 + SD_SKIP_REL)):
+//   * rounding: the bound rounds four times (c_k, its two products, thr - SD_SKIP_ABS), the kernel's dxx dyy four times (3 side,
+//     mid - 3 side, the factor w_i, the product; dyy is the same number on both sides), every one monotone: together below 8 x 2^-53
+//     relative, against SD_SKIP_REL = 2^-20.  A product that underflows is below 1e-300, and SD_SKIP_ABS covers that.
+//   * a COMPUTED side sum can exceed its computed mid sum by the rounding of the integral image, delta (in image units).  The ~1e-9
+//     quoted above rt_darktab_kernel is what one sees; the worst case of 8 corners x (H + W) roundings of half an ulp of H W is 1.5e-5
+//     at the engine's 2024 x 2024 and 1.2e-4 at the 4094 x 4094 the launcher accepts.  Only k = 2 is touched (side >= 0 holds exactly,
+//     so mid - 3 side <= mid does too): |mid - 3 side| <= 2 mid + 3 delta, and the product grows by at most |dyy| 3 delta / size^2
+//     <= 6 delta / 225 (|dyy| <= 2: a box holds at most size^2 pixels of at most 1.0).  SD_SKIP_ABS = 2^-18 covers delta <= 1.4e-4.
+//   * the 2^-10 that the ring's box sums carry is undone by w_i = 2^10 / size^2 (sd_wi), which the bound multiplies by as the kernel
+//     does: both scalings are exact, and delta enters as delta 2^-10 w_i = delta / size^2, as used above.
+// So: ruled out => the product as the kernel rounds it is at or below thr.  Never the reverse - a position that is not ruled out may
+// still come out below - and a threshold below SD_SKIP_ABS rules nothing out, since a bound is never negative.  Against a threshold
+// of 5e-4 the two margins cost no measurable skip rate.
+#define SD_SKIP_REL 9.5367431640625e-07
+#define SD_SKIP_ABS 3.814697265625e-06
 template <int PH>
-__device__ __forceinline__ void sd_tile_fast(const uint32_t (&ca)[12], const uint32_t (&cb)[12], double (&d0)[SD_T / 8], double (&d1)[SD_T / 8])
+__device__ __forceinline__ void sd_tile_fast(const uint32_t (&ca)[12], const uint32_t (&cb)[12], double thr_s, double (&d0)[SD_T / 8], double (&d1)[SD_T / 8])
 {
     static_assert(SD_T == 16, "two positions per thread and step");
     double v[2][2][4];                                                     // [pair slot][position][corner]
-    auto issue = [&](int i, double(&o)[2][4]) {
-        const int L = (i >> 2) & 1, q = i & 3;                             // q: xx-mid, xx-side, yy-mid, yy-side (hessian_box 4..7)
+    auto issue = [&](int L, int q, double(&o)[2][4]) {                     // q: xx-mid, xx-side, yy-mid, yy-side (hessian_box 4..7)
         const int SIZE = L ? 30 : 15, s2 = (SIZE - 1) / 2, s3 = SIZE / 3;
         const int ra = q < 2 ? -s3 + 1 : (q == 2 ? -s2 : -(s3 / 2)), rb = ra + (q < 2 ? 2 * s3 - 1 : (q == 2 ? SIZE : s3));
         const int ja = 6 * L + (q == 0 ? 0 : (q == 1 ? 2 : 4)), jb = ja + 1;
@@ -106,29 +133,48 @@ __device__ __forceinline__ void sd_tile_fast(const uint32_t (&ca)[12], const uin
             o[k][2] = sd_ldr(ca, cb, R0 + ra, jb); o[k][3] = sd_ldr(ca, cb, R0 + rb, ja);
         }
     };
-    issue(0, v[0]);
-    double mid[2] = {0.0, 0.0}, dxx[2] = {0.0, 0.0};
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        if (i + 1 < 8) issue(i + 1, v[(i + 1) & 1]);
-        const int L = (i >> 2) & 1, q = i & 3;
-        const double(&x)[2][4] = v[i & 1];
+    // the two positions' box sums of a pair, then -(mid - 3 side) w_i: the chains of the two positions alternate
+    auto boxes = [&](const double(&x)[2][4], double(&b)[2]) {
         double t0 = __dadd_rn(x[0][0], x[0][1]), t1 = __dadd_rn(x[1][0], x[1][1]);
         t0 = __dsub_rn(t0, x[0][2]); t1 = __dsub_rn(t1, x[1][2]);
-        double b0, b1;
-        asm("v_add_f64 %0, %1, -%2 clamp" : "=v"(b0) : "v"(t0), "v"(x[0][3]));
-        asm("v_add_f64 %0, %1, -%2 clamp" : "=v"(b1) : "v"(t1), "v"(x[1][3]));
-        if (q == 0 || q == 2) { mid[0] = b0; mid[1] = b1; }
-        else {
-            const double w_i = L ? sd_wi<30>() : sd_wi<15>();
-            double m0 = __dmul_rn(3.0, b0), m1 = __dmul_rn(3.0, b1);
-            double e0 = __dsub_rn(mid[0], m0), e1 = __dsub_rn(mid[1], m1);
-            e0 = __dmul_rn(-e0, w_i); e1 = __dmul_rn(-e1, w_i);
-            if (q == 1) { dxx[0] = e0; dxx[1] = e1; }
-            else if (L) { d1[0] = __dmul_rn(dxx[0], e0); d1[1] = __dmul_rn(dxx[1], e1); }
-            else { d0[0] = __dmul_rn(dxx[0], e0); d0[1] = __dmul_rn(dxx[1], e1); }
+        asm("v_add_f64 %0, %1, -%2 clamp" : "=v"(b[0]) : "v"(t0), "v"(x[0][3]));
+        asm("v_add_f64 %0, %1, -%2 clamp" : "=v"(b[1]) : "v"(t1), "v"(x[1][3]));
+    };
+    auto deriv = [&](int L, const double(&mid)[2], const double(&side)[2], double(&e)[2]) {
+        const double w_i = L ? sd_wi<30>() : sd_wi<15>();
+        const double m0 = __dmul_rn(3.0, side[0]), m1 = __dmul_rn(3.0, side[1]);
+        const double e0 = __dsub_rn(mid[0], m0), e1 = __dsub_rn(mid[1], m1);
+        e[0] = __dmul_rn(-e0, w_i); e[1] = __dmul_rn(-e1, w_i);
+    };
+    issue(0, 2, v[0]);
+    double mid[2], b[2], dyy[2][2], xm[2][2];                              // dyy, xx-mid: [layer][position]
+    bool need[2];                                                          // (wave-uniform) the layer's xx-side pair has to be read
+#pragma unroll
+    for (int i = 0; i < 6; i++) {                                          // per layer: yy-mid, yy-side, xx-mid
+        const int L = i / 3, j = i % 3;
+        if (i + 1 < 6) issue((i + 1) / 3, (i + 1) % 3 == 0 ? 2 : ((i + 1) % 3 == 1 ? 3 : 0), v[(i + 1) & 1]);
+        boxes(v[i & 1], j == 0 ? mid : (j == 1 ? b : xm[L]));
+        if (j == 1) deriv(L, mid, b, dyy[L]);
+        if (j == 2) {
+            const double w1 = __dmul_rn(L ? sd_wi<30>() : sd_wi<15>(), 1.0 + SD_SKIP_REL), w2 = __dmul_rn(2.0, w1);
+            const double u0 = __dmul_rn(__dmul_rn(fabs(dyy[L][0]), xm[L][0]), dyy[L][0] > 0.0 ? w2 : w1);
+            const double u1 = __dmul_rn(__dmul_rn(fabs(dyy[L][1]), xm[L][1]), dyy[L][1] > 0.0 ? w2 : w1);
+            need[L] = __builtin_amdgcn_ballot_w64(u0 > thr_s || u1 > thr_s) != 0;
         }
         __builtin_amdgcn_sched_barrier(0);
+    }
+    if (need[0]) issue(0, 1, v[0]);
+    if (need[1]) issue(1, 1, v[1]);
+    d0[0] = 0.0; d0[1] = 0.0; d1[0] = 0.0; d1[1] = 0.0;
+    if (need[0]) {
+        double e[2];
+        boxes(v[0], b); deriv(0, xm[0], b, e);
+        d0[0] = __dmul_rn(e[0], dyy[0][0]); d0[1] = __dmul_rn(e[1], dyy[0][1]);
+    }
+    if (need[1]) {
+        double e[2];
+        boxes(v[1], b); deriv(1, xm[1], b, e);
+        d1[0] = __dmul_rn(e[0], dyy[1][0]); d1[1] = __dmul_rn(e[1], dyy[1][1]);
     }
 }
 
@@ -224,7 +270,7 @@ __global__ __launch_bounds__(SD_THREADS) void rt_det_strip_kernel(RtArgs a, int 
     if (jq >= per || work >= total) return;
     const int ls = work / nstrips, strip = work - ls * nstrips;
     const int W = a.W, H = a.W, SP = a.SP;
-    const double thr = a.threshold;
+    const double thr = a.threshold, thr_s = __dsub_rn(thr, SD_SKIP_ABS);   // thr_s: what sd_tile_fast's bound is held against
     typedef const uint32_t __attribute__((address_space(4))) *SdConstPtr;     // constant address space + uniform address = scalar load
     const SdConstPtr dtab = (SdConstPtr)(uintptr_t)(a.darktab + strip * SD_DT_WORDS);
     uint32_t dk_w = 0, skf_w = 0;                                           // the words of the current 32 steps: dark / skip the load
@@ -358,7 +404,7 @@ __global__ __launch_bounds__(SD_THREADS) void rt_det_strip_kernel(RtArgs a, int 
 #pragma unroll
             for (int k = 0; k < SD_T / 8; k++) { d0[k] = 0.0; d1[k] = 0.0; }
         } else if (fast) {
-            sd_tile_fast<PH>(ca, cb, d0, d1);
+            sd_tile_fast<PH>(ca, cb, thr_s, d0, d1);
         } else {
 #pragma unroll
             for (int k = 0; k < SD_T / 8; k++) {
