@@ -507,6 +507,37 @@ int32_t roam_engine_time_loop_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t n, 
                                     float *gather_ms);
 int32_t roam_time_loop_db_verify(roam_ctx *ctx, roam_loop_db *db, int32_t n_pairs, const int32_t *src_index, const int32_t *dst_index,
                                  const double *init, const roam_icp_opts *opts, int32_t reps, float *ms_per_rep);
+/* motion compensation of the stored clouds (csrc/cloud_motion.h, cloud_gather_motion_kernel in csrc/loop_cloud.hip).  PARITY UNPINNED as
+ * the clouds; the contract is tests/loop_cloud_motion_model.py, which is the reference's MotionDistortionSolver.undistort with the time
+ * of a point taken from its azimuth row instead of atan2.
+ * A scan sweeps its `rows` azimuths over `period` seconds.  With the scan's velocity v = (vx, vy, vtheta) - m/s, m/s, rad/s in the
+ * sensor frame of the stored points, roam_keyframe_hdr.velocity - the peak of row t is stored where mid-scan would have seen it:
+ *   tau_t = period ((2 t - rows) / (2 rows))   (-period / 2 at row 0, 0 at mid-scan), a = vtheta tau_t, C = cos a, S = sin a by the
+ *   host's libm, DX = vx tau_t, DY = vy tau_t;   with (x0, y0) the plain stored point above:
+ *   x = ((C x0) - (S y0)) + DX, y = ((S x0) + (C y0)) + DY, every operation one float64 operation rounded once.
+ * The selection of the peaks is unchanged.  roam_cloud_motion_table: host only, no context; out (n, rows, 4) = C S DX DY of every row
+ * of n scans, velocities (n, 3); a scan whose vx is NaN has NO velocity - its rows are NaN, and an add stores its plain cloud, bit for
+ * bit.  ROAM_E_ARG: rows outside [1, 65536], n < 1, a null pointer, period not finite or <= 0, a component that is not finite (other
+ * than that marker).  The device only multiplies and adds with the table, which follows the chunks of an add (32 bytes per row beside
+ * the staging): what is stored depends on the scan and its velocity alone.
+ * roam_loop_db_add_f32_motion / roam_engine_loop_db_add_motion: roam_loop_db_add_f32 / roam_engine_loop_db_add with velocities
+ * (n, 3), one row per scan, or NULL - then they ARE those entries, which call them so, and period is not read.  ROAM_E_ARG before any
+ * device call, the text naming the argument, beyond what those entries refuse: velocities for a database that keeps no clouds; period
+ * not finite or <= 0; a velocity component that is not finite (other than the marker); a velocity for which hypot(vx, vy) period / 2
+ * plus the largest range cols range_resolution_m exceeds ROAM_ICP_MAX_COORD.  A failed add leaves the database as it was.
+ * roam_engine_time_loop_cloud_motion: roam_engine_time_loop_cloud with such velocities - the gather's motion form, its table
+ * uploaded once before the launches. */
+int32_t roam_cloud_motion_table(int32_t rows, double period, int32_t n, const double *velocities /* n x 3 */,
+                                double *out /* n x rows x 4: C S DX DY */);
+int32_t roam_loop_db_add_f32_motion(roam_ctx *ctx, roam_loop_db *db, const float *polar, int32_t n, int32_t rows, int32_t cols,
+                                    int64_t row_stride, int64_t image_stride, int32_t clip_px, double floor,
+                                    const double *velocities /* n x 3 or NULL */, double period, int32_t *first_index_out);
+int32_t roam_engine_loop_db_add_motion(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px,
+                                       int32_t floor_code, const double *velocities /* n x 3 or NULL */, double period,
+                                       int32_t *first_index_out);
+int32_t roam_engine_time_loop_cloud_motion(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx,
+                                           const double *velocities /* n x 3 or NULL */, double period, int32_t reps, float *rows_ms,
+                                           float *gather_ms);
 
 /* ---- origin-shifted scan contexts: revisits metres off the stored place (csrc/loop_offset.hip; the augmentation of Scan Context++,
  * Kim, Choi, Kim, T-RO 2021).  PARITY UNPINNED as the sections above; the contract is tests/scan_context_offset_model.py.

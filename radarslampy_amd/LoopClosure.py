@@ -32,6 +32,12 @@ pool has forgotten the scan long before a revisit is recognised.  verify and que
 second with no host round trip between the query and the verification; closeLoops uses it when the detector keeps clouds.  The
 rule of the stored points (every step-th peak, tables from the host's libm) is tests/loop_cloud_model.py.
 
+Motion compensation.  A scan sweeps its azimuths over 0.25 s; at driving speed a cloud stored as if the sweep were instantaneous is
+skewed by metres, the ICP still reports success, and the edge is 0.5 to 1.4 m off (docs/PARITY.md).  Given the scan's velocity
+(add(velocity=), Engine.loop_db_add(velocities=), polarIndToLocalMetres(velocity=), closeLoops(undistort=True)) every peak is moved
+to where mid-scan would have seen it while the cloud is built: MotionDistortionSolver.undistort with the time taken from the peak's
+row, tests/loop_cloud_motion_model.py.  The descriptor and its origin-shifted variants are not compensated.
+
 Global map.  The stored clouds are also what a map is made of: LoopDetector.renderMap takes one pose per entry and bins every entry's
 points in the world frame on the device (csrc/loop_map.hip) -> Mapping.GlobalMap, an occupancy grid (points and distinct keyframes per
 cell) and a thinned list of map points; mapFromGraph(detector, graph) is the step after closeLoops.  A closure moves every pose, so
@@ -150,10 +156,12 @@ class LoopDetector:
     def __len__(self):
         return len(self.db)
 
-    def add(self, polarImg):
+    def add(self, polarImg, velocity=None, period=0.25):
         """describe a float32 polar image (or a 3-D batch) on the device and store it -> the index of the (first) new entry.  With
-        keepClouds the image's peak cloud (all its columns) is stored too"""
-        return self.db.add_f32(polarImg, self.clip_px, self.floor)
+        keepClouds the image's peak cloud (all its columns) is stored too.  velocity (keepClouds): the scan's (vx, vy, vtheta) in m/s,
+        m/s, rad/s, sensor frame (Keyframe.velocity) - (3,) for one image, (n, 3) for a batch, None entries allowed; the stored cloud
+        is motion-compensated over the scan period (tests/loop_cloud_motion_model.py).  None: the plain cloud"""
+        return self.db.add_f32(polarImg, self.clip_px, self.floor, velocity, period)
 
     def addDescriptors(self, desc, clouds=None):
         """store ready-made descriptors, (sectors, rings) or (n, sectors, rings) -> the index of the first new entry.  clouds (with
@@ -269,11 +277,15 @@ class LoopDetector:
 
 
 # ---------------------------------------------------------------------------------------------------------------- verification
-def polarIndToLocalMetres(pointCloud, rows, rangeResolutionM=RANGE_RESOLUTION_M):
+def polarIndToLocalMetres(pointCloud, rows, rangeResolutionM=RANGE_RESOLUTION_M, velocity=None, period=0.25):
     """The (K, 2) [thetaInd, rInd] rows of getPointCloudPolarInd -> (K, 2) float64 metres in the sensor-centred frame of
     Keyframe.featurePointsLocal: r res (cos phi, sin phi) with phi = 2 pi thetaInd / rows - (pixel - centre) resolution of the image
-    convertPolarImageToCartesian makes, x along its columns and y along its rows.  Host code."""
+    convertPolarImageToCartesian makes, x along its columns and y along its rows.  Host code.
+    velocity (vx, vy, vtheta) in m/s, m/s, rad/s (Keyframe.velocity): the points are motion-compensated over the scan period as the
+    loop database's clouds are (tests/loop_cloud_motion_model.py): row t was seen at tau = period (2 t - rows) / (2 rows), the point
+    becomes R(vtheta tau) p + (vx, vy) tau - MotionDistortionSolver.undistort with the time taken from the row"""
     pc = np.asarray(pointCloud)
+    v, period = _ffi.loop_motion_args(velocity, period, 1)
     if pc.size == 0:
         return np.zeros((0, 2), np.float64)
     if pc.ndim != 2 or pc.shape[1] != 2:
@@ -283,7 +295,13 @@ def polarIndToLocalMetres(pointCloud, rows, rangeResolutionM=RANGE_RESOLUTION_M)
     pc = pc.astype(np.float64)
     phi = 2.0 * np.pi * pc[:, 0] / rows
     r = pc[:, 1] * float(rangeResolutionM)
-    return np.stack([r * np.cos(phi), r * np.sin(phi)], axis=1)
+    x0, y0 = r * np.cos(phi), r * np.sin(phi)
+    if v is None or np.isnan(v[0, 0]):
+        return np.stack([x0, y0], axis=1)
+    tau = period * ((2.0 * pc[:, 0] - rows) / (2.0 * rows))
+    a = v[0, 2] * tau
+    c, s = np.cos(a), np.sin(a)
+    return np.stack([((c * x0) - (s * y0)) + v[0, 0] * tau, ((s * x0) + (c * y0)) + v[0, 1] * tau], axis=1)
 
 
 def _align_batch(pairs, init, opts):
@@ -399,7 +417,7 @@ def _accept(n_query, rows, pos, seeds, poses, stats, sizes, minInlierFraction, m
 
 
 def closeLoops(keyframes, detector, clouds=None, *, rows=None, rangeResolutionM=RANGE_RESOLUTION_M, loopInformation=np.eye(3), huber=None,
-               odomInformation=np.eye(3), max_iterations=20, ctx=None, **verify):
+               odomInformation=np.eye(3), max_iterations=20, ctx=None, undistort=False, period=0.25, **verify):
     """Close the loops of a keyframe list: keyframes with .pose and .pointCloud (Mapping.Map.keyframes) and a LoopDetector that already
     holds their scans, entry k = keyframe k.  The peak clouds are converted to metres (rows: the azimuths of the polar images, by default
     those of keyframes[0].radarPolarImg; or pass ready clouds), every keyframe is queried, the candidates are verified in one device
@@ -407,7 +425,9 @@ def closeLoops(keyframes, detector, clouds=None, *, rows=None, rangeResolutionM=
     and optimised.  -> (graph, edges, table); graph.get_pose(k) is keyframe k's optimised pose.  Without an accepted edge the graph is
     returned un-optimised (odometry alone has nothing to correct).  A detector that keeps clouds (LoopDetector(keepClouds=True)) and
     clouds = None: the candidates are found and verified from the detector's own store in one device pass (queryAndVerify) and
-    keyframe.pointCloud, rows and rangeResolutionM are not used."""
+    keyframe.pointCloud, rows and rangeResolutionM are not used.  undistort=True (the path that converts keyframe.pointCloud): every
+    cloud is motion-compensated with its keyframe.velocity over `period` (polarIndToLocalMetres(velocity=)); a detector's own store
+    is compensated when its scans are added (LoopDetector.add(velocity=), Engine.loop_db_add(velocities=)), not here."""
     keyframes = list(keyframes)
     if len(detector) != len(keyframes):
         raise ValueError(f"closeLoops: the detector holds {len(detector)} scans for {len(keyframes)} keyframes")
@@ -417,7 +437,7 @@ def closeLoops(keyframes, detector, clouds=None, *, rows=None, rangeResolutionM=
     if clouds is None:
         if rows is None:
             rows = int(np.asarray(keyframes[0].radarPolarImg).shape[0])
-        clouds = [polarIndToLocalMetres(k.pointCloud, rows, rangeResolutionM) for k in keyframes]
+        clouds = [polarIndToLocalMetres(k.pointCloud, rows, rangeResolutionM, k.velocity if undistort else None, period) for k in keyframes]
     elif len(clouds) != len(keyframes):
         raise ValueError(f"closeLoops: {len(clouds)} clouds for {len(keyframes)} keyframes")
     idx = np.arange(len(keyframes), dtype=np.int32)

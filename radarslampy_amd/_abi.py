@@ -163,6 +163,11 @@ _SIGS = {
     "roam_loop_db_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _P(IcpOpts), _vp, _vp]),
     "roam_loop_db_query_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, _P(IcpOpts), _vp, _vp, _vp, _vp, _vp]),
     "roam_engine_time_loop_cloud": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, _P(C.c_float), _P(C.c_float)]),
+    "roam_cloud_motion_table": (C.c_int32, [C.c_int32, C.c_double, C.c_int32, _vp, _vp]),
+    "roam_loop_db_add_f32_motion": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_double,
+                                                _vp, C.c_double, _P(C.c_int32)]),
+    "roam_engine_loop_db_add_motion": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, C.c_double, _P(C.c_int32)]),
+    "roam_engine_time_loop_cloud_motion": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_double, C.c_int32, _P(C.c_float), _P(C.c_float)]),
     "roam_time_loop_db_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _P(IcpOpts), C.c_int32, _P(C.c_float)]),
     "roam_scan_context_offset_table": (C.c_int32, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "roam_loop_db_keep_offsets": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_double]),

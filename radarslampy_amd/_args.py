@@ -356,6 +356,53 @@ def loop_cloud_args(capacity, rows, max_points, point_stride, range_resolution_m
     return int(rows), int(max_points), int(point_stride), float(res)
 
 
+def loop_motion_args(velocities, period, n, keeps_clouds=True, cols=None, range_resolution_m=None):
+    """the checks of the velocities of an add of n scans (LoopDb.add_f32, Engine.loop_db_add, Engine.time_loop_cloud) and of
+    cloud_motion_table before any library call -> (velocities (n, 3) float64 rows (vx, vy, vtheta), C order, or None; period).
+    velocities: None (no motion compensation: period is not read), one (3,) velocity for a single scan, an (n, 3) array in which a
+    NaN vx marks a scan without a velocity, or a sequence of n entries, each (3,) or None.  ValueError: velocities for a database
+    that keeps no clouds, a period that is not finite or <= 0, a wrong shape, a component that is not finite, a velocity for which
+    hypot(vx, vy) period / 2 plus the largest range cols range_resolution_m exceeds 1e6 m (checked when both are given)"""
+    if velocities is None:
+        return None, 0.25
+    if not keeps_clouds:
+        raise ValueError("loop db: velocities for a database that keeps no clouds (keep_clouds)")
+    if not isinstance(period, numbers.Real) or isinstance(period, bool) or not np.isfinite(period) or not period > 0:
+        raise ValueError(f"loop db: period finite and > 0, not {period!r}")
+    if isinstance(velocities, np.ndarray):
+        v = velocities.reshape(1, 3) if velocities.shape == (3,) else velocities
+        if v.dtype.kind not in "fiu" or v.shape != (n, 3):
+            raise ValueError(f"loop db: velocities ({n}, 3) numbers, rows (vx, vy, vtheta), not {v.dtype} {velocities.shape}")
+        out = np.array(v, np.float64, order="C")
+    else:
+        v = list(velocities)
+        if len(v) == 3 and all(isinstance(c, numbers.Real) and not isinstance(c, bool) for c in v):
+            v = [v]                                   # one velocity, not three scans
+        if len(v) != n:
+            raise ValueError(f"loop db: {len(v)} velocities for {n} scans")
+        out = np.full((n, 3), np.nan)
+        for i, row in enumerate(v):
+            if row is None:
+                continue
+            r = np.asarray(row)
+            if r.shape != (3,) or r.dtype.kind not in "fiu":
+                raise ValueError(f"loop db: velocities[{i}] is (vx, vy, vtheta) or None, not {row!r}")
+            if np.isnan(r[0]):
+                raise ValueError(f"loop db: velocities[{i}] = {row!r} is not finite (None: no velocity)")
+            out[i] = r
+    moving = ~np.isnan(out[:, 0])
+    bad = np.flatnonzero(moving & ~np.isfinite(out).all(axis=1))
+    if bad.size:
+        raise ValueError(f"loop db: velocities[{int(bad[0])}] = {out[bad[0]].tolist()} is not finite")
+    if cols is not None and range_resolution_m is not None:
+        reach = np.hypot(out[:, 0], out[:, 1]) * float(period) / 2.0 + cols * range_resolution_m
+        bad = np.flatnonzero(moving & ~(reach <= ICP_MAX_COORD))
+        if bad.size:
+            raise ValueError(f"loop db: velocities[{int(bad[0])}] = {out[bad[0]].tolist()} over {period} s moves a point at "
+                             f"{cols * range_resolution_m:g} m beyond {ICP_MAX_COORD:g} m")
+    return out, float(period)
+
+
 def loop_cloud_points(xy, max_points):
     """a cloud for LoopDb.set_cloud -> (n, 2) float64, C order.  ValueError: not (n, 2) numbers, n > max_points, a coordinate that is not
     finite or beyond 1e6 m"""

@@ -20,7 +20,7 @@ from ._abi import (ABI_SYMBOLS, COMM_ID_BYTES, FMT_MAX_COLS, FMT_MAX_R, FMT_MAX_
                    IcpStats, KeyframeHdr, LaneResult, PoseGraphOpts, RoamError, _INTERNAL_SIGS, _P, _SIGS, _vp)
 from ._args import (_batch_operands, _batch_strides, _f32_rows_in_place, _int_in, auto_prior_args, fmt_cart_radius, fmt_clip_radius,
                     fmt_register_batch_args, fmt_rotation_batch_args, icp2d_args, icp2d_opts, invert_affine, klt_flow_args,
-                    loop_cloud_args, loop_cloud_points, loop_map_args, loop_offsets_args, loop_query_args, loop_verify_args,
+                    loop_cloud_args, loop_cloud_points, loop_map_args, loop_motion_args, loop_offsets_args, loop_query_args, loop_verify_args,
                     motion_prior_args, peak_conditions, phase_correlate_args, pose_graph_args, scan_context_floor, warp_affine_args)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -143,6 +143,27 @@ def polar_cloud_table(rows):
     if load_library().roam_polar_cloud_table(int(rows), _ptr(c), _ptr(s)) != ROAM_OK:
         raise ValueError(f"loop db: roam_polar_cloud_table refused rows {rows}")
     return c, s
+
+
+def cloud_motion_table(rows, velocities, period=0.25):
+    """roam_cloud_motion_table, host code only (no device, no context): the table a cloud-keeping loop database compensates a scan's
+    motion with -> (n, rows, 4) float64, C S DX DY of every azimuth row: tau_t = period ((2 t - rows) / (2 rows)), (C, S) = (cos, sin)
+    of vtheta tau_t by the host's libm, (DX, DY) = (vx, vy) tau_t.  velocities: (3,) -> n = 1, (n, 3), or a sequence with None
+    entries; a scan without a velocity (None, or NaN in vx) has rows of NaN.  ValueError: rows no integer in [1, 65536], and what
+    loop_motion_args refuses"""
+    if not _int_in(rows, 1, SCAN_CONTEXT_MAX_ROWS):
+        raise ValueError(f"loop db: rows an integer in [1, {SCAN_CONTEXT_MAX_ROWS}], not {rows!r}")
+    if velocities is None:
+        raise ValueError("loop db: cloud_motion_table needs velocities")
+    if not isinstance(velocities, np.ndarray):
+        velocities = list(velocities)
+    one = len(velocities) == 3 and all(isinstance(c, numbers.Real) for c in velocities)       # (vx, vy, vtheta) itself
+    n = 1 if one else len(velocities)
+    v, period = loop_motion_args(velocities, period, n)
+    out = np.empty((n, rows, 4), np.float64)
+    if load_library().roam_cloud_motion_table(int(rows), period, n, _ptr(v), _ptr(out)) != ROAM_OK:
+        raise ValueError(f"loop db: roam_cloud_motion_table refused rows {rows}, period {period}, velocities {v.tolist()}")
+    return out
 
 
 def map_pose_table(poses):
@@ -672,7 +693,7 @@ class LoopDb:
         h = _vp()
         ctx.check(ctx.lib.roam_loop_db_create(ctx.h, self.capacity, self.sectors, self.rings, C.byref(h)))
         self.h = h
-        self.cloud_rows = self.max_points = None             # set by keep_clouds
+        self.cloud_rows = self.max_points = self.range_resolution_m = None      # set by keep_clouds
         self.offsets_m = None                                # set by keep_offsets: (n_offsets, 2) float64 metres
 
     def close(self):
@@ -691,13 +712,21 @@ class LoopDb:
         self.ctx.check(self.ctx.lib.roam_loop_db_count(self.h, C.byref(n)))
         return n.value
 
-    def add_f32(self, polar, clip_px=None, floor=0.0):
-        """describe a 2-D float32 polar image or a 3-D batch on the device and append -> the index of the first new entry"""
+    def add_f32(self, polar, clip_px=None, floor=0.0, velocities=None, period=0.25):
+        """describe a 2-D float32 polar image or a 3-D batch on the device and append -> the index of the first new entry.
+        velocities (a database that keeps clouds): the scans' velocities (vx, vy, vtheta) in m/s, m/s, rad/s - (3,) for one image,
+        (n, 3) or a sequence with None entries for a batch; the stored clouds are motion-compensated over the scan period
+        (cloud_motion_table, roam_loop_db_add_f32_motion).  None: the plain clouds, and period is not read"""
         a3, n, rows, cols, row_stride, image_stride, _ = scan_context_images(polar, clip_px, self.sectors, self.rings)
         floor = scan_context_floor(floor)
+        v, period = loop_motion_args(velocities, period, n, self.cloud_rows is not None, cols, self.range_resolution_m)
         first = C.c_int32(-1)
-        self.ctx.check(self.ctx.lib.roam_loop_db_add_f32(self.ctx.h, self.h, _ptr(a3), n, rows, cols, row_stride, image_stride,
-                                                         int(clip_px or 0), floor, C.byref(first)))
+        if v is None:
+            self.ctx.check(self.ctx.lib.roam_loop_db_add_f32(self.ctx.h, self.h, _ptr(a3), n, rows, cols, row_stride, image_stride,
+                                                             int(clip_px or 0), floor, C.byref(first)))
+        else:
+            self.ctx.check(self.ctx.lib.roam_loop_db_add_f32_motion(self.ctx.h, self.h, _ptr(a3), n, rows, cols, row_stride, image_stride,
+                                                                    int(clip_px or 0), floor, _ptr(v), period, C.byref(first)))
         return first.value
 
     def add_desc(self, desc):
@@ -814,7 +843,7 @@ class LoopDb:
         if self.cloud_rows is not None:
             raise ValueError("loop db: keeps clouds already")
         self.ctx.check(self.ctx.lib.roam_loop_db_keep_clouds(self.ctx.h, self.h, rows, mp, ps, res))
-        self.cloud_rows, self.max_points = rows, mp
+        self.cloud_rows, self.max_points, self.range_resolution_m = rows, mp, res
 
     def _needs_clouds(self):
         if self.cloud_rows is None:

@@ -227,10 +227,16 @@ static LoopPool loop_pool(const roam_ctx *ctx, const Engine *e)
 int32_t roam_engine_loop_db_add(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
                                 int32_t *first_index_out)
 {
+    return roam_engine_loop_db_add_motion(ctx, db, n, pool_idx, clip_px, floor_code, nullptr, 0.25, first_index_out);
+}
+
+int32_t roam_engine_loop_db_add_motion(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
+                                       const double *velocities, double period, int32_t *first_index_out)
+{
     ENGINE();
     ARG_CHECK(ctx, db && n >= 1 && pool_idx);
     for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
-    return loop_records_append(ctx, db, loop_pool(ctx, e), n, pool_idx, clip_px, floor_code, first_index_out);
+    return loop_records_append(ctx, db, loop_pool(ctx, e), n, pool_idx, clip_px, floor_code, first_index_out, velocities, period);
 }
 
 int32_t roam_engine_time_loop_describe(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t clip_px, int32_t floor_code,
@@ -254,11 +260,17 @@ int32_t roam_engine_time_loop_offsets(roam_ctx *ctx, roam_loop_db *db, int32_t n
 int32_t roam_engine_time_loop_cloud(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, int32_t reps, float *rows_ms,
                                     float *gather_ms)
 {
+    return roam_engine_time_loop_cloud_motion(ctx, db, n, pool_idx, nullptr, 0.25, reps, rows_ms, gather_ms);
+}
+
+int32_t roam_engine_time_loop_cloud_motion(roam_ctx *ctx, roam_loop_db *db, int32_t n, const int32_t *pool_idx, const double *velocities,
+                                           double period, int32_t reps, float *rows_ms, float *gather_ms)
+{
     ENGINE();
     ARG_CHECK(ctx, db && n >= 1 && pool_idx && rows_ms && gather_ms);
     for (int i = 0; i < n; i++) ARG_CHECK(ctx, pool_idx[i] >= 0 && pool_idx[i] < e->cfg.pool_scans);
     float ms[2] = {0, 0};
-    const int32_t rc = loop_records_time_cloud(ctx, db, loop_pool(ctx, e), n, pool_idx, reps, ms);
+    const int32_t rc = loop_records_time_cloud(ctx, db, loop_pool(ctx, e), n, pool_idx, reps, ms, velocities, period);
     *rows_ms = ms[0];
     *gather_ms = ms[1];
     return rc;

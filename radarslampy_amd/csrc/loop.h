@@ -6,7 +6,8 @@
 //                      resident records (loop_records_prepare / _append / _time_describe / _time_offsets / _time_cloud)
 //   loop_query.hip     loop_distance_kernel, loop_variant_fold_kernel, loop_select_kernel, loop_variant_gather_kernel; the query pass
 //                      (LoopQueryBufs and the loop_query_* steps); roam_loop_db_query, roam_loop_db_query_offsets and their timing entries
-//   loop_cloud.hip     cloud_gather_kernel, the row staging and the cloud build; roam_polar_cloud_table, roam_loop_db_keep_clouds,
+//   loop_cloud.hip     cloud_gather_kernel and its motion form, the row staging and the cloud build; roam_polar_cloud_table,
+//                      roam_cloud_motion_table (cloud_motion.h: the velocity checks and the table, host only), roam_loop_db_keep_clouds,
 //                      set_cloud, get_cloud, cloud_counts
 //   loop_verify.hip    loop_pairs_kernel, the pair scratch and staging; roam_loop_db_verify, roam_time_loop_db_verify,
 //                      roam_loop_db_query_verify
@@ -20,7 +21,8 @@
 //   icp.hip            the ICP of a pair of stored clouds (icp2d_store_kernel), which loop_verify.hip launches
 // engine_lanes.hip describes the engine's pool (LoopPool) and calls the record entries.  The reference has no place recognition (a
 // commented-out "import m2dp" at Mapping.py:7 and an unused Keyframe.pointCloud at :61-62), so parity is unpinned: the contracts are
-// tests/scan_context_model.py, tests/loop_cloud_model.py, tests/scan_context_offset_model.py and tests/global_map_model.py.
+// tests/scan_context_model.py, tests/loop_cloud_model.py, tests/loop_cloud_motion_model.py, tests/scan_context_offset_model.py and
+// tests/global_map_model.py.
 #pragma once
 #include "roam_internal.h"
 #include <vector>
@@ -99,10 +101,12 @@ LOOP_UNIT hipError_t sc_launch_norm(hipStream_t st, const roam_loop_db *db, int6
 LOOP_UNIT hipError_t sc_launch_norm_rows(hipStream_t st, const float *desc, int64_t n_rows, int R, int Rp, double *nrm, int32_t *valid);
 // host float32 images in chunks under the scratch limit: upload the clipped columns tightly, describe into desc (+ nrm, valid) from
 // entry `first` on.  cloud_db (optional, a database that keeps clouds; cols = the images' full width): all the columns are uploaded,
-// and the images' peak clouds go to the entries from `first` on as well
+// and the images' peak clouds go to the entries from `first` on as well - with h_motion (sc_motion_table's table of the n images on the
+// host, null: none) motion-compensated; its rows follow the chunks
 LOOP_UNIT int32_t sc_describe_host_f32(roam_ctx *ctx, const float *polar, int n, int rows, int64_t row_stride, int64_t image_stride, int clip,
                                        int S, int R, double floor_v, float *desc, double *nrm, int32_t *valid, int64_t first,
-                                       const roam_loop_db *cloud_db = nullptr, int cols = 0, const ScOffsets *offs = nullptr);
+                                       const roam_loop_db *cloud_db = nullptr, int cols = 0, const ScOffsets *offs = nullptr,
+                                       const double *h_motion = nullptr);
 
 // ---- loop_offset.hip
 // where the variants of a describing call come from and go to: device pointers, the store's at its entry 0 (vnrm / vvalid may be null)
@@ -132,10 +136,21 @@ LOOP_UNIT void sc_offsets_free(roam_loop_db *db);
 static inline int64_t sc_stage_bytes(int rows, int cols) { return (int64_t)rows * ((cols + 1) / 2) * sizeof(uint16_t) + (int64_t)rows * sizeof(int32_t); }
 // the staging of nb scans (taken from the scratch slots S_TMP0 / S_TMP1, which no enqueued engine step reads: a step owns its buffers)
 LOOP_UNIT int32_t sc_cloud_stage(roam_ctx *ctx, int rows, int cols, int nb, uint16_t **stage, int32_t **rcount);
+// motion: the launch's motion table on the device, nb x rows x 4 (null: no scan has a velocity, the plain kernel)
 LOOP_UNIT hipError_t sc_launch_cloud_gather(hipStream_t st, const roam_loop_db *db, int nb, const uint16_t *stage, int stage_cap, const int32_t *rcount,
-                                            int64_t first);
-// the clouds of the nb scans of `ps` (cols range bins each) -> the entries from `first` on; enqueued, not awaited
-LOOP_UNIT int32_t sc_build_clouds(roam_ctx *ctx, const roam_loop_db *db, const PeakSrc &ps, int nb, int cols, int64_t first);
+                                            int64_t first, const double *motion = nullptr);
+// the clouds of the nb scans of `ps` (cols range bins each) -> the entries from `first` on; enqueued, not awaited.  h_motion: these
+// scans' rows of sc_motion_table's table on the host (null: none), which the caller keeps until the stream has been waited for
+LOOP_UNIT int32_t sc_build_clouds(roam_ctx *ctx, const roam_loop_db *db, const PeakSrc &ps, int nb, int cols, int64_t first,
+                                  const double *h_motion = nullptr);
+// the checks of an add's velocities (n x 3, null: none -> an empty table) against scans of `cols` range bins, then the motion table of
+// the n scans, n x cloud_rows x 4 (cloud_motion.h).  No device call
+LOOP_UNIT int32_t sc_motion_table(roam_ctx *ctx, const roam_loop_db *db, int n, const double *velocities, double period, int cols,
+                                  std::vector<double> *table);
+// nb scans' rows of that table -> the device (scratch S_IN2), enqueued; h_motion null -> *d_motion null
+LOOP_UNIT int32_t sc_motion_upload(roam_ctx *ctx, int rows, int nb, const double *h_motion, const double **d_motion);
+// bytes of motion table one scan takes
+static inline int64_t sc_motion_bytes(int rows) { return (int64_t)rows * 4 * sizeof(double); }
 // what an add to a cloud-keeping database refuses beyond the descriptor's checks
 LOOP_UNIT int32_t sc_check_cloud_add(roam_ctx *ctx, const roam_loop_db *db, int rows, int cols);
 // the end of a blocking add of n entries from `first` on: their counts to the host mirror; waits for the stream
@@ -150,18 +165,20 @@ struct LoopPool {
 };
 // Each entry first checks (db, the geometry, floor_code, the clouds, the room for n entries; a timing entry then its reps) and only
 // then enqueues: the wait for the pool's uploads and the upload of pool_idx (host, n indices the caller has checked).
-// describe the records and append them to db, blocking; a database that keeps clouds gets the records' peak clouds too
+// describe the records and append them to db, blocking; a database that keeps clouds gets the records' peak clouds too, with
+// velocities (n x 3, null: none; refused before anything is enqueued - sc_motion_table) motion-compensated over `period`
 LOOP_UNIT int32_t loop_records_append(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
-                                      int32_t floor_code, int32_t *first_index_out);
+                                      int32_t floor_code, int32_t *first_index_out, const double *velocities = nullptr, double period = 0.25);
 // nothing is appended: `reps` launches of the describing kernel into the free entries, timed (roam_time_launches)
 LOOP_UNIT int32_t loop_records_time_describe(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
                                              int32_t floor_code, int32_t reps, float *ms_per_rep);
 // likewise the variants of the records (the clear, the binning kernel and the finishing kernel as one launch) into the free entries
 LOOP_UNIT int32_t loop_records_time_offsets(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
                                             int32_t floor_code, int32_t reps, float *ms_per_rep);
-// likewise the two kernels of the cloud build, each alone: ms[0] the peak row kernel, ms[1] the cloud gather
+// likewise the two kernels of the cloud build, each alone: ms[0] the peak row kernel, ms[1] the cloud gather - with velocities its
+// motion form, the table uploaded once before the launches
 LOOP_UNIT int32_t loop_records_time_cloud(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t reps,
-                                          float *ms);
+                                          float *ms, const double *velocities = nullptr, double period = 0.25);
 
 // ---- loop_query.hip: the query pass of one chunk of nq queries at k candidates each, shared with roam_loop_db_query_verify
 LOOP_UNIT int32_t sc_check_query(roam_ctx *ctx, const roam_loop_db *db, int32_t n_query, const int32_t *query_index, const int32_t *max_index,

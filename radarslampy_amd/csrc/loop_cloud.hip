@@ -8,7 +8,16 @@
 // and writes the selected peaks straight to the entry's slot - the int32 peak list is never made.  A lane owns a run of consecutive
 // rows and knows the global index of their first peak from the scan, so what is stored depends on the scan alone, not on the batch or
 // the chunk.
+//
+// Motion compensation (roam_cloud_motion_table).  A scan sweeps its azimuths over `period` seconds; with the scan's velocity
+// v = (vx, vy, vtheta) in the sensor frame the peak of row t is moved to where mid-scan would have seen it: tau_t =
+// period ((2 t - rows) / (2 rows)), a = vtheta tau_t, (x, y) = R(a) (x0, y0) + (vx, vy) tau_t - MotionDistortionSolver.undistort with
+// the time taken from the peak's row.  The host makes the per-row table C S DX DY with its libm, cloud_gather_motion_kernel reads a
+// row of it for every azimuth row a lane owns and applies it in registers before the two stores: six float64 operations per point,
+// each rounded once.  A scan without a velocity has a table of NaN and takes the plain path inside the same launch; a launch without
+// any table runs cloud_gather_kernel, whose code the motion form does not touch.
 #include "loop.h"
+#include "cloud_motion.h"
 #include "peaks_common.h"
 #include <math.h>
 
@@ -16,11 +25,13 @@
 
 // ---------------------------------------------------------------------------------------------------------------- device
 // the stored cloud of scan b of the launch (entry first + b, the pointers already moved there) from the row kernel's staging: see the
-// head of the file.  A lane takes the rows [lo, hi) and walks their peaks with the global index q = off + j
-__global__ __launch_bounds__(CG_THREADS) void cloud_gather_kernel(const uint16_t *__restrict__ row_stage, int stage_cap,
-                                                                  const int32_t *__restrict__ row_count, int rows, const double *__restrict__ trig,
-                                                                  double res, int max_points, int point_stride, double *__restrict__ cloud,
-                                                                  int32_t *__restrict__ cloud_n, int32_t *__restrict__ cloud_peaks)
+// head of the file.  A lane takes the rows [lo, hi) and walks their peaks with the global index q = off + j.  MOTION: `motion` is the
+// launch's table, rows x 4 per scan; a scan whose first value is NaN has no velocity (uniform over the workgroup)
+template <bool MOTION>
+__device__ __forceinline__ void cloud_gather_body(const uint16_t *__restrict__ row_stage, int stage_cap, const int32_t *__restrict__ row_count,
+                                                  int rows, const double *__restrict__ trig, double res, int max_points, int point_stride,
+                                                  double *__restrict__ cloud, int32_t *__restrict__ cloud_n, int32_t *__restrict__ cloud_peaks,
+                                                  const double *__restrict__ motion)
 {
     __shared__ int scan_sh[8];
     const int64_t b = blockIdx.x;
@@ -35,16 +46,32 @@ __global__ __launch_bounds__(CG_THREADS) void cloud_gather_kernel(const uint16_t
     const int fit = (total + max_points - 1) / max_points;
     const int step = fit > point_stride ? fit : point_stride;
     double *out = cloud + 2 * b * max_points;
+    const double2 *mt = nullptr;
+    bool moving = false;
+    if constexpr (MOTION) {
+        mt = (const double2 *)(motion + 4 * b * rows);
+        moving = mt[0].x == mt[0].x;
+    }
     for (int r = lo; r < hi; ++r) {
         const int n = min(rc[r], stage_cap);
         const uint16_t *sr = row_stage + (b * rows + r) * stage_cap;
         const double ct = trig[r], st = trig[rows + r];
+        double2 cs = make_double2(1.0, 0.0), d = make_double2(0.0, 0.0);
+        if constexpr (MOTION)
+            if (moving && n > 0) { cs = mt[2 * r]; d = mt[2 * r + 1]; }
         const int rem = off % step;
         for (int j = rem ? step - rem : 0; j < n; j += step) {
             const int slot = (off + j) / step;             // < ceil(total / step) <= max_points
             const double rho = (double)sr[j] * res;
-            out[2 * slot] = rho * ct;
-            out[2 * slot + 1] = rho * st;
+            double x = rho * ct, y = rho * st;
+            if constexpr (MOTION)
+                if (moving) {
+                    const double x0 = x, y0 = y;
+                    x = __dadd_rn(__dadd_rn(__dmul_rn(cs.x, x0), -__dmul_rn(cs.y, y0)), d.x);
+                    y = __dadd_rn(__dadd_rn(__dmul_rn(cs.y, x0), __dmul_rn(cs.x, y0)), d.y);
+                }
+            out[2 * slot] = x;
+            out[2 * slot + 1] = y;
         }
         off += n;
     }
@@ -54,13 +81,36 @@ __global__ __launch_bounds__(CG_THREADS) void cloud_gather_kernel(const uint16_t
     }
 }
 
+__global__ __launch_bounds__(CG_THREADS) void cloud_gather_kernel(const uint16_t *__restrict__ row_stage, int stage_cap,
+                                                                  const int32_t *__restrict__ row_count, int rows, const double *__restrict__ trig,
+                                                                  double res, int max_points, int point_stride, double *__restrict__ cloud,
+                                                                  int32_t *__restrict__ cloud_n, int32_t *__restrict__ cloud_peaks)
+{
+    cloud_gather_body<false>(row_stage, stage_cap, row_count, rows, trig, res, max_points, point_stride, cloud, cloud_n, cloud_peaks, nullptr);
+}
+
+__global__ __launch_bounds__(CG_THREADS) void cloud_gather_motion_kernel(const uint16_t *__restrict__ row_stage, int stage_cap,
+                                                                         const int32_t *__restrict__ row_count, int rows,
+                                                                         const double *__restrict__ trig, double res, int max_points,
+                                                                         int point_stride, double *__restrict__ cloud,
+                                                                         int32_t *__restrict__ cloud_n, int32_t *__restrict__ cloud_peaks,
+                                                                         const double *__restrict__ motion)
+{
+    cloud_gather_body<true>(row_stage, stage_cap, row_count, rows, trig, res, max_points, point_stride, cloud, cloud_n, cloud_peaks, motion);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
 // the staging and the build: what they do is said where loop.h declares them
 hipError_t sc_launch_cloud_gather(hipStream_t st, const roam_loop_db *db, int nb, const uint16_t *stage, int stage_cap, const int32_t *rcount,
-                                  int64_t first)
+                                  int64_t first, const double *motion)
 {
-    hipLaunchKernelGGL(cloud_gather_kernel, dim3(nb), dim3(CG_THREADS), 0, st, stage, stage_cap, rcount, db->cloud_rows, db->trig, db->res,
-                       db->max_points, db->point_stride, db->cloud + 2 * first * db->max_points, db->cloud_n + first, db->cloud_peaks + first);
+    if (motion)
+        hipLaunchKernelGGL(cloud_gather_motion_kernel, dim3(nb), dim3(CG_THREADS), 0, st, stage, stage_cap, rcount, db->cloud_rows, db->trig,
+                           db->res, db->max_points, db->point_stride, db->cloud + 2 * first * db->max_points, db->cloud_n + first,
+                           db->cloud_peaks + first, motion);
+    else
+        hipLaunchKernelGGL(cloud_gather_kernel, dim3(nb), dim3(CG_THREADS), 0, st, stage, stage_cap, rcount, db->cloud_rows, db->trig, db->res,
+                           db->max_points, db->point_stride, db->cloud + 2 * first * db->max_points, db->cloud_n + first, db->cloud_peaks + first);
     return hipGetLastError();
 }
 
@@ -72,13 +122,38 @@ int32_t sc_cloud_stage(roam_ctx *ctx, int rows, int cols, int nb, uint16_t **sta
     return *stage && *rcount ? ROAM_OK : ROAM_E_HIP;
 }
 
-int32_t sc_build_clouds(roam_ctx *ctx, const roam_loop_db *db, const PeakSrc &ps, int nb, int cols, int64_t first)
+int32_t sc_motion_upload(roam_ctx *ctx, int rows, int nb, const double *h_motion, const double **d_motion)
+{
+    *d_motion = nullptr;
+    if (!h_motion) return ROAM_OK;
+    const size_t bytes = sizeof(double) * 4 * (size_t)nb * rows;
+    double *d = (double *)roam_scratch(ctx, S_IN2, bytes);
+    if (!d) return ROAM_E_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(d, h_motion, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *d_motion = d;
+    return ROAM_OK;
+}
+
+int32_t sc_build_clouds(roam_ctx *ctx, const roam_loop_db *db, const PeakSrc &ps, int nb, int cols, int64_t first, const double *h_motion)
 {
     uint16_t *stage;
     int32_t *rcount;
+    const double *d_motion;
     LOOP_TRY(sc_cloud_stage(ctx, db->cloud_rows, cols, nb, &stage, &rcount));
+    LOOP_TRY(sc_motion_upload(ctx, db->cloud_rows, nb, h_motion, &d_motion));
     HIP_TRY(ctx, launch_peaks_rows(ctx->stream, ps, nb, db->cloud_rows, cols, stage, (cols + 1) / 2, rcount));
-    HIP_TRY(ctx, sc_launch_cloud_gather(ctx->stream, db, nb, stage, (cols + 1) / 2, rcount, first));
+    HIP_TRY(ctx, sc_launch_cloud_gather(ctx->stream, db, nb, stage, (cols + 1) / 2, rcount, first, d_motion));
+    return ROAM_OK;
+}
+
+int32_t sc_motion_table(roam_ctx *ctx, const roam_loop_db *db, int n, const double *velocities, double period, int cols, std::vector<double> *table)
+{
+    table->clear();
+    if (!velocities) return ROAM_OK;
+    if (!db->cloud_rows) { ROAM_SET_ERR(ctx, "loop db: velocities for a db that keeps no clouds (roam_loop_db_keep_clouds)"); return ROAM_E_ARG; }
+    if (!cloud_motion_check(ctx->err, sizeof(ctx->err), n, velocities, period, cols, db->res, ROAM_ICP_MAX_COORD)) return ROAM_E_ARG;
+    table->resize(4 * (size_t)n * db->cloud_rows);
+    cloud_motion_fill(db->cloud_rows, period, n, velocities, table->data());
     return ROAM_OK;
 }
 
@@ -108,6 +183,14 @@ extern "C" int32_t roam_polar_cloud_table(int32_t rows, double *cos_out, double 
         cos_out[t] = cos(phi);
         sin_out[t] = sin(phi);
     }
+    return ROAM_OK;
+}
+
+extern "C" int32_t roam_cloud_motion_table(int32_t rows, double period, int32_t n, const double *velocities, double *out)
+{
+    if (rows < 1 || rows > SC_MAX_ROWS || n < 1 || !velocities || !out) return ROAM_E_ARG;
+    if (!cloud_motion_check(nullptr, 0, n, velocities, period, 0, 0.0, INFINITY)) return ROAM_E_ARG;
+    cloud_motion_fill(rows, period, n, velocities, out);
     return ROAM_OK;
 }
 

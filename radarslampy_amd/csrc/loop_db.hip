@@ -92,17 +92,26 @@ static int32_t sc_check_room(roam_ctx *ctx, const roam_loop_db *db, int32_t n)
 extern "C" int32_t roam_loop_db_add_f32(roam_ctx *ctx, roam_loop_db *db, const float *polar, int32_t n, int32_t rows, int32_t cols,
                                         int64_t row_stride, int64_t image_stride, int32_t clip_px, double floor, int32_t *first_index_out)
 {
+    return roam_loop_db_add_f32_motion(ctx, db, polar, n, rows, cols, row_stride, image_stride, clip_px, floor, nullptr, 0.25, first_index_out);
+}
+
+extern "C" int32_t roam_loop_db_add_f32_motion(roam_ctx *ctx, roam_loop_db *db, const float *polar, int32_t n, int32_t rows, int32_t cols,
+                                               int64_t row_stride, int64_t image_stride, int32_t clip_px, double floor, const double *velocities,
+                                               double period, int32_t *first_index_out)
+{
     if (!ctx) return ROAM_E_ARG;
     if (!db) { ROAM_SET_ERR(ctx, "loop db: db is null"); return ROAM_E_ARG; }
     int clip;
     LOOP_TRY(sc_check_f32_args(ctx, polar, n, rows, cols, row_stride, image_stride, clip_px, db->S, db->R, floor, &clip));
     if (db->cloud_rows) LOOP_TRY(sc_check_cloud_add(ctx, db, rows, cols));
+    std::vector<double> motion;
+    LOOP_TRY(sc_motion_table(ctx, db, n, velocities, period, cols, &motion));
     LOOP_TRY(sc_check_room(ctx, db, n));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ScOffsets offs;
     if (db->n_off) LOOP_TRY(sc_offsets_of_db(ctx, db, rows, &offs));
     LOOP_TRY(sc_describe_host_f32(ctx, polar, n, rows, row_stride, image_stride, clip, db->S, db->R, floor, db->desc, db->nrm, db->valid, db->count,
-                                  db->cloud_rows ? db : nullptr, cols, db->n_off ? &offs : nullptr));
+                                  db->cloud_rows ? db : nullptr, cols, db->n_off ? &offs : nullptr, velocities ? motion.data() : nullptr));
     if (db->cloud_rows) LOOP_TRY(sc_mirror_counts(ctx, db, db->count, n));
     if (first_index_out) *first_index_out = db->count;
     db->count += n;
@@ -188,10 +197,12 @@ static int32_t sc_records_offsets(roam_ctx *ctx, roam_loop_db *db, const LoopPoo
 }
 
 int32_t loop_records_append(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t clip_px,
-                            int32_t floor_code, int32_t *first_index_out)
+                            int32_t floor_code, int32_t *first_index_out, const double *velocities, double period)
 {
     int clip;
     LOOP_TRY(sc_check_records(ctx, db, pool, n, clip_px, floor_code, false, &clip));
+    std::vector<double> motion;                           // lives until the stream has been waited for
+    LOOP_TRY(sc_motion_table(ctx, db, n, velocities, period, pool.clip, &motion));
     ScSrc src;
     PeakSrc ps;
     LOOP_TRY(sc_stage_records(ctx, pool, n, pool_idx, &src, &ps));
@@ -203,13 +214,13 @@ int32_t loop_records_append(roam_ctx *ctx, roam_loop_db *db, const LoopPool &poo
         LOOP_TRY(sc_records_offsets(ctx, db, pool, src, n, clip, floor_code, offs));
     }
     if (db->cloud_rows) {                                 // in chunks that bound the staging; what is stored does not depend on the cut
-        int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / sc_stage_bytes(pool.rows, pool.clip);
+        int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / (sc_stage_bytes(pool.rows, pool.clip) + (velocities ? sc_motion_bytes(pool.rows) : 0));
         if (chunk < 1) chunk = 1;
         for (int64_t i0 = 0; i0 < n; i0 += chunk) {
             const int nb = (int)(n - i0 < chunk ? n - i0 : chunk);
             PeakSrc part = ps;
             part.lane_index += i0;
-            LOOP_TRY(sc_build_clouds(ctx, db, part, nb, pool.clip, db->count + i0));
+            LOOP_TRY(sc_build_clouds(ctx, db, part, nb, pool.clip, db->count + i0, velocities ? motion.data() + 4 * i0 * pool.rows : nullptr));
         }
         LOOP_TRY(sc_mirror_counts(ctx, db, db->count, n));
     }
@@ -258,20 +269,25 @@ int32_t loop_records_time_offsets(roam_ctx *ctx, roam_loop_db *db, const LoopPoo
     return rc != ROAM_OK ? rc : rt;
 }
 
-int32_t loop_records_time_cloud(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t reps, float *ms)
+int32_t loop_records_time_cloud(roam_ctx *ctx, roam_loop_db *db, const LoopPool &pool, int32_t n, const int32_t *pool_idx, int32_t reps, float *ms,
+                                const double *velocities, double period)
 {
     const int rows = pool.rows, cols = pool.clip;
     int clip;
     LOOP_TRY(sc_check_records(ctx, db, pool, n, 0, 0, true, &clip));
     LOOP_TRY(sc_check_reps(ctx, reps));
-    if (n * sc_stage_bytes(rows, cols) > SC_DB_BYTES) { ROAM_SET_ERR(ctx, "loop db timing: %d records do not fit one launch", n); return ROAM_E_ARG; }
+    std::vector<double> motion;
+    LOOP_TRY(sc_motion_table(ctx, db, n, velocities, period, cols, &motion));
+    if (n * (sc_stage_bytes(rows, cols) + (velocities ? sc_motion_bytes(rows) : 0)) > SC_DB_BYTES) { ROAM_SET_ERR(ctx, "loop db timing: %d records do not fit one launch", n); return ROAM_E_ARG; }
     ScSrc src;
     PeakSrc ps;
     LOOP_TRY(sc_stage_records(ctx, pool, n, pool_idx, &src, &ps));
     const hipStream_t st = ctx->stream;
     uint16_t *stage;
     int32_t *rcount;
+    const double *d_motion;
     LOOP_TRY(sc_cloud_stage(ctx, rows, cols, n, &stage, &rcount));
+    LOOP_TRY(sc_motion_upload(ctx, rows, n, velocities ? motion.data() : nullptr, &d_motion));
     LOOP_TRY(roam_time_launches(ctx, st, reps, ms, [&] { return launch_peaks_rows(st, ps, n, rows, cols, stage, (cols + 1) / 2, rcount); }));
-    return roam_time_launches(ctx, st, reps, ms + 1, [&] { return sc_launch_cloud_gather(st, db, n, stage, (cols + 1) / 2, rcount, db->count); });
+    return roam_time_launches(ctx, st, reps, ms + 1, [&] { return sc_launch_cloud_gather(st, db, n, stage, (cols + 1) / 2, rcount, db->count, d_motion); });
 }

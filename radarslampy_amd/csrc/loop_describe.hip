@@ -133,12 +133,12 @@ hipError_t sc_launch_norm(hipStream_t st, const roam_loop_db *db, int64_t first,
 
 int32_t sc_describe_host_f32(roam_ctx *ctx, const float *polar, int n, int rows, int64_t row_stride, int64_t image_stride, int clip, int S,
                              int R, double floor_v, float *desc, double *nrm, int32_t *valid, int64_t first, const roam_loop_db *cloud_db,
-                             int cols, const ScOffsets *offs)
+                             int cols, const ScOffsets *offs, const double *h_motion)
 {
     const hipStream_t st = ctx->stream;
     const int width = cloud_db ? cols : clip;
     const int64_t per = (int64_t)sizeof(float) * rows * width + (cloud_db ? sc_stage_bytes(rows, cols) : 0) +
-                        (offs ? sc_offset_part_bytes(false, rows, S, R, offs->n_off) : 0);
+                        (offs ? sc_offset_part_bytes(false, rows, S, R, offs->n_off) : 0) + (h_motion ? sc_motion_bytes(rows) : 0);
     int64_t chunk = roam_chunk_limit(SC_CHUNK_ENV, SC_DB_BYTES) / per;
     if (chunk < 1) chunk = 1;
     for (int64_t i0 = 0; i0 < n; i0 += chunk) {
@@ -151,7 +151,7 @@ int32_t sc_describe_host_f32(roam_ctx *ctx, const float *polar, int n, int rows,
         if (offs) LOOP_TRY(sc_launch_offsets(ctx, false, src, nb, rows, clip, S, R, floor_v, 0, *offs, first + i0));
         if (cloud_db) {
             const PeakSrc ps = {d_in, (int64_t)rows * width, width, 0, 0, nullptr};
-            LOOP_TRY(sc_build_clouds(ctx, cloud_db, ps, nb, cols, first + i0));
+            LOOP_TRY(sc_build_clouds(ctx, cloud_db, ps, nb, cols, first + i0, h_motion ? h_motion + 4 * i0 * rows : nullptr));
         }
         HIP_TRY(ctx, hipStreamSynchronize(st));           // the next chunk reuses the upload buffer
     }

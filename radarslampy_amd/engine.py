@@ -295,11 +295,15 @@ class Engine:
                                                          int(downsample), int(cart_downsample), _ffi._ptr(out)))
         return out
 
-    def loop_db_add(self, detector, pool_idx, clip_px=None, floor_code=None):
+    def loop_db_add(self, detector, pool_idx, clip_px=None, floor_code=None, velocities=None, period=0.25):
         """describe resident scans as scan contexts and store them in a LoopClosure.LoopDetector (or an _ffi.LoopDb) without moving
         image data (roam_engine_loop_db_add): the u8 form, mean of max(code - floor_code, 0) / 255 over the bins -> the index of the
         first new entry; a detector that keeps clouds gets the scans' peak clouds too.  clip_px / floor_code default to the detector's.  Runs behind the steps enqueued so far, blocks until done and
-        leaves the engine's state alone.  ValueError before any device call for a bad index list, clip or floor."""
+        leaves the engine's state alone.  ValueError before any device call for a bad index list, clip or floor.
+        velocities (a detector that keeps clouds): one (vx, vy, vtheta) per pool index in m/s, m/s, rad/s, sensor frame - (n, 3), or a
+        sequence with None for a scan without one; the stored clouds are motion-compensated over the scan period
+        (roam_engine_loop_db_add_motion, tests/loop_cloud_motion_model.py).  The natural source is the velocity the engine estimated
+        for that scan: map_keyframe(lane, k)["velocity"].  None: the plain clouds, bit for bit, and period is not read."""
         db = getattr(detector, "db", detector)
         idx = np.ascontiguousarray(pool_idx, np.int32).ravel()
         if len(idx) < 1 or idx.min() < 0 or idx.max() >= self.pool_scans:
@@ -311,20 +315,31 @@ class Engine:
         if not isinstance(floor_code, (int, np.integer)) or isinstance(floor_code, bool) or not 0 <= floor_code <= 254:
             raise ValueError(f"loop_db_add: floor_code an integer in [0, 254], not {floor_code!r}")
         _ffi.scan_context_plan(self.rows, self.cfg.clip, clip_px, db.sectors, db.rings)
+        v, period = _ffi.loop_motion_args(velocities, period, len(idx), db.cloud_rows is not None, self.cfg.clip, db.range_resolution_m)
         first = C.c_int32(-1)
-        self.ctx.check(self.lib.roam_engine_loop_db_add(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), int(clip_px or 0), int(floor_code),
-                                                        C.byref(first)))
+        if v is None:
+            self.ctx.check(self.lib.roam_engine_loop_db_add(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), int(clip_px or 0), int(floor_code),
+                                                            C.byref(first)))
+        else:
+            self.ctx.check(self.lib.roam_engine_loop_db_add_motion(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), int(clip_px or 0), int(floor_code),
+                                                                   _ffi._ptr(v), period, C.byref(first)))
         return first.value
 
-    def time_loop_cloud(self, detector, pool_idx, reps=20):
+    def time_loop_cloud(self, detector, pool_idx, reps=20, velocities=None, period=0.25):
         """(peak row kernel ms, cloud gather kernel ms) per launch of the cloud build of these resident scans into the free entries of a
-        cloud-keeping LoopDetector / LoopDb; nothing is appended (roam_engine_time_loop_cloud)"""
+        cloud-keeping LoopDetector / LoopDb; nothing is appended (roam_engine_time_loop_cloud).  velocities (as loop_db_add's): the
+        gather's motion form, its table uploaded once before the launches (roam_engine_time_loop_cloud_motion)"""
         db = getattr(detector, "db", detector)
         idx = np.ascontiguousarray(pool_idx, np.int32).ravel()
         if len(idx) < 1 or idx.min() < 0 or idx.max() >= self.pool_scans:
             raise ValueError(f"time_loop_cloud: at least one pool index, all in [0, {self.pool_scans})")
+        v, period = _ffi.loop_motion_args(velocities, period, len(idx), db.cloud_rows is not None, self.cfg.clip, db.range_resolution_m)
         a, b = C.c_float(0), C.c_float(0)
-        self.ctx.check(self.lib.roam_engine_time_loop_cloud(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), int(reps), C.byref(a), C.byref(b)))
+        if v is None:
+            self.ctx.check(self.lib.roam_engine_time_loop_cloud(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), int(reps), C.byref(a), C.byref(b)))
+        else:
+            self.ctx.check(self.lib.roam_engine_time_loop_cloud_motion(self.ctx.h, db.h, len(idx), _ffi._ptr(idx), _ffi._ptr(v), period, int(reps),
+                                                                       C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
     def lane_image(self, lane: int, level: int = 0):
