@@ -647,7 +647,7 @@ int32_t roam_time_loop_db_map(roam_ctx *ctx, roam_loop_db *db, const double *pos
  * keyframe bookkeeping (Mapping.py:37-66,118-125,149-174). */
 typedef struct roam_engine_cfg {
     int32_t lanes;            /* B                                                       */
-    int32_t rows;             /* 400                                                      */
+    int32_t rows;             /* 400; 2 ... 1020 (ROAM_E_ARG outside: the warp's zero-weight tap row rows + 1 wraps to row 1) */
     int32_t stride;           /* 3779 bytes per record row                                */
     int32_t payload_off;      /* 11                                                       */
     int32_t clip;             /* 2025                                                     */

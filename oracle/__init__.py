@@ -133,6 +133,16 @@ def convertPolarImageToCartesian(imgPolar: np.ndarray, want_u8: bool = False):
     return (cart, u8) if want_u8 else cart
 
 
+def polar_sampling_map(rows: int, cols: int):
+    """the sampling coordinates of convertPolarImageToCartesian for a (rows, cols) polar image -> (sx, sy), each (W, W) int32 in 1/32 px,
+    W = 2 * (cols // 2): pixel (y, x) reads range bins ix = sx >> 5 and ix + 1 of the padded rows iy = sy >> 5 and iy + 1 (padded row p is
+    polar row p - 1, rows 0 and rows + 1 wrap) with the bilinear fractions (sx & 31) / 32 and (sy & 31) / 32"""
+    W = 2 * (int(cols) // 2)
+    sx, sy = np.empty((W, W), np.int32), np.empty((W, W), np.int32)
+    lib().oracle_polar_map(int(rows), int(cols), _p(sx, C.c_int32), _p(sy, C.c_int32))
+    return sx, sy
+
+
 def convertPolarImageToCartesianTies(imgPolar: np.ndarray, tie_eps: float, want_u8: bool = False, every: int = 1):
     """sensitivity probe: the same warp with every `every`-th radial sampling coordinate within tie_eps (in 1/32-px units) of a rounding tie
     rounded the OTHER way - what an ulp of difference in the radius (IPP's magnitude in the reference's cv2 build, DESIGN.md

@@ -83,9 +83,12 @@ static inline float polar_tap(const float *polar, int rows, int cols, int64_t st
 }
 
 /* polar (rows x cols f32) -> cart (2R x 2R f32), R = cols/2.  Optionally also the u8
- * quantisation the KLT wrapper applies.  Either output may be NULL. */
+ * quantisation the KLT wrapper applies.  Either output may be NULL.  map_sx / map_sy (optional, 2R x 2R each): the sampling
+ * coordinates in 1/32 px every pixel is read at, as rounded here (after the tie probe); polar may then be NULL when no image
+ * is asked for. */
 static int64_t polar_to_cart_impl(const float *polar, int rows, int cols, int64_t stride,
-                                  float *cart_f32, uint8_t *cart_u8, float tie_eps, int tie_every)
+                                  float *cart_f32, uint8_t *cart_u8, float tie_eps, int tie_every,
+                                  int32_t *map_sx, int32_t *map_sy)
 {
     int64_t n_flipped = 0, n_ties = 0;
     const int R = cols / 2;
@@ -112,6 +115,9 @@ static int64_t polar_to_cart_impl(const float *polar, int rows, int cols, int64_
                 float t = mx * 32.f, fl = floorf(t), fr = t - fl;
                 if (fabsf(fr - 0.5f) < tie_eps && (n_ties++ % tie_every) == 0) { sx = (sx == (int)fl) ? (int)fl + 1 : (int)fl; n_flipped++; }
             }
+            if (map_sx) map_sx[(int64_t)y * W + x] = sx;
+            if (map_sy) map_sy[(int64_t)y * W + x] = sy;
+            if (!cart_f32 && !cart_u8) continue;
             int ix = sx >> 5, iy = sy >> 5;
             int fxq = sx & 31, fyq = sy & 31;
             float wx1 = (float)fxq * (1.f / 32.f), wx0 = 1.f - wx1;
@@ -139,7 +145,14 @@ static int64_t polar_to_cart_impl(const float *polar, int rows, int cols, int64_
 void oracle_polar_to_cart(const float *polar, int rows, int cols, int64_t stride,
                           float *cart_f32, uint8_t *cart_u8)
 {
-    polar_to_cart_impl(polar, rows, cols, stride, cart_f32, cart_u8, 0.f, 1);
+    polar_to_cart_impl(polar, rows, cols, stride, cart_f32, cart_u8, 0.f, 1, NULL, NULL);
+}
+
+/* the sampling map of oracle_polar_to_cart alone: sx, sy (2R x 2R int32 each) in 1/32 px of the polar image padded by one wrap row
+ * above and below (ix = sx >> 5 the range bin, iy = sy >> 5 the padded row, the low five bits the bilinear fractions) */
+void oracle_polar_map(int rows, int cols, int32_t *sx, int32_t *sy)
+{
+    polar_to_cart_impl(NULL, rows, cols, cols, NULL, NULL, 0.f, 1, sx, sy);
 }
 
 /* sensitivity probe (tests/test_oracle_reference_dump.py): the same warp with every tie_every-th radial sampling coordinate that
@@ -147,7 +160,7 @@ void oracle_polar_to_cart(const float *polar, int rows, int cols, int64_t stride
 int64_t oracle_polar_to_cart_ties(const float *polar, int rows, int cols, int64_t stride,
                                   float *cart_f32, uint8_t *cart_u8, float tie_eps, int tie_every)
 {
-    return polar_to_cart_impl(polar, rows, cols, stride, cart_f32, cart_u8, tie_eps, tie_every < 1 ? 1 : tie_every);
+    return polar_to_cart_impl(polar, rows, cols, stride, cart_f32, cart_u8, tie_eps, tie_every < 1 ? 1 : tie_every, NULL, NULL);
 }
 
 /* (img*255).astype(uint8) on an arbitrary f32 image in [0,1] */

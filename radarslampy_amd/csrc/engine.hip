@@ -525,7 +525,9 @@ int32_t roam_engine_create(roam_ctx *ctx, const roam_engine_cfg *cfg)
 {
     if (!ctx) return ROAM_E_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ARG_CHECK(ctx, cfg && cfg->lanes >= 1 && cfg->rows >= 1 && cfg->rows <= 1020 && cfg->clip >= 32 && cfg->clip <= 4094 && (cfg->clip / 2) % 2 == 0 &&
+    // rows >= 2: the sampling map reaches iy == rows + 1 (a tap row of weight zero) and the warp and the re-detection's integral wrap a
+    // staged polar row ONCE, to row 1 - with one azimuth that is the next record, or past the pool (docs/KERNELS.md, warp_gather_kernel)
+    ARG_CHECK(ctx, cfg && cfg->lanes >= 1 && cfg->rows >= 2 && cfg->rows <= 1020 && cfg->clip >= 32 && cfg->clip <= 4094 && (cfg->clip / 2) % 2 == 0 &&
                        (int64_t)cfg->rows * cfg->stride < (1ll << 30) &&
                        cfg->payload_off >= 0 && cfg->stride >= cfg->payload_off + cfg->clip && cfg->pool_scans >= 1 &&
                        cfg->peaks_cap >= 1);

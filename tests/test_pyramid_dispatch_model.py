@@ -130,8 +130,8 @@ def test_engine_layouts_reach_every_branch_at_every_level_it_can_occur():
 
 
 def test_engine_layouts_are_accepted_by_roam_engine_create():
-    # engine.hip roam_engine_create: rows 1 ... 1020, clip 32 ... 4094 with clip / 2 even, payload inside the stride
+    # engine.hip roam_engine_create: rows 2 ... 1020, clip 32 ... 4094 with clip / 2 even, payload inside the stride
     for clip, rows, stride, off in ENGINE_LAYOUTS:
-        assert 1 <= rows <= 1020 and 32 <= clip <= 4094 and (clip // 2) % 2 == 0 and off >= 0 and stride >= off + clip
+        assert 2 <= rows <= 1020 and 32 <= clip <= 4094 and (clip // 2) % 2 == 0 and off >= 0 and stride >= off + clip
     assert any(stride % 4 for _, _, stride, _ in ENGINE_LAYOUTS) and any(off % 4 for _, _, _, off in ENGINE_LAYOUTS)
     assert any(rows != 400 for _, rows, _, _ in ENGINE_LAYOUTS) and max(c for c, _, _, _ in ENGINE_LAYOUTS) > 2048
