@@ -640,6 +640,70 @@ int32_t roam_loop_db_map_render(roam_ctx *ctx, roam_loop_db *db, const double *p
 int32_t roam_time_loop_db_map(roam_ctx *ctx, roam_loop_db *db, const double *poses, const int8_t *use, double res, double ox, double oy,
                               int32_t W, int32_t H, int32_t min_hits, int32_t min_views, int32_t reps, float *ms /* 3 */);
 
+/* ---- map matching: a scan localised in a rendered global map by correlative scan-to-map matching (csrc/map_match.hip; the host-only
+ * half is csrc/map_match.h).  The reference left Map.mapPoints a TODO and computes none of this, so PARITY UNPINNED as the sections
+ * above; the contract is tests/map_match_model.py.  Every floating-point step below is one float64 operation rounded once; everything
+ * accumulated is an integer, so the result is bit-reproducible and no order of arrival can show.
+ * Table.  roam_map_field_table (host only, no context): the side is 2 radius + 1,
+ * T[dv + r][du + r] = (uint8) floor(255 * exp(-(double)(du du + dv dv) / (2 sigma sigma)) + 0.5) by the host's libm - the device never
+ * calls exp.  ROAM_E_ARG: radius outside [0, ROAM_MATCH_MAX_RADIUS], sigma_cells not finite or <= 0, a null pointer.
+ * Field.  roam_map_field_create: hits, views (H, W) uint32 on the host (what roam_loop_db_map_render gave), the extent as there.  A
+ * cell is occupied when hits >= min_hits and views >= min_views; F[v][u] = the maximum over |dv|, |du| <= radius, (v + dv, u + du) inside
+ * the grid and occupied, of T[dv + r][du + r], 0 without such a cell.  One byte per cell, built by mm_field_kernel from the uploaded
+ * grids (scratch of the call) and resident in the handle until roam_map_field_destroy; roam_map_field_read copies it out, (H, W).
+ * ROAM_E_ARG before any device call, the text naming the argument: a null pointer, res not finite or <= 0, an origin that is not
+ * finite, W or H < 1, W H > ROAM_MAP_MAX_CELLS, a threshold < 1, radius outside [0, ROAM_MATCH_MAX_RADIUS].
+ * Match.  roam_map_match_clouds: n_query (1 ... 65535) clouds concatenated in xy ((total, 2) float64 metres, sensor frame, |coord| <=
+ * ROAM_ICP_MAX_COORD), cloud q the rows [offsets[q], offsets[q + 1]) (offsets (n_query + 1) int64, ascending from 0, at most
+ * ROAM_ICP_MAX_POINTS rows each); priors (n_query, 3) rows x0, y0, th0 (limits of the render's poses); the window: n_theta odd in
+ * [1, ROAM_MATCH_MAX_ANGLES] angles step_rad apart (finite, >= 0), kx, ky in [0, ROAM_MATCH_MAX_SHIFT] cells of shift to either side.
+ * Angles.  c = (n_theta - 1) / 2, th_i = th0 + (double)(i - c) * step_rad; roam_map_match_angles (host only, no context): cs_out
+ * (n_query, n_theta, 2) = (cos th_i, sin th_i) by the host's libm - what the device multiplies with.
+ * Cell of a point (px, py) at angle i: wx = ((c_i px) - (s_i py)) + x0, wy = ((s_i px) + (c_i py)) + y0 (the global map's world
+ * point); dx = (wx - ox) / res, dy likewise; the point is far when not -2^30 <= dx < 2^30 (dy likewise) and never scores; otherwise
+ * u = (int32) floor(dx), v = (int32) floor(dy).
+ * Score.  score(i, b, a) = the sum over the not-far points of F[v + (b - ky)][u + (a - kx)], positions outside the grid counting 0: a
+ * translation is an exact shift of the cell index, not a re-binning of a translated point.  A uint32 (8192 x 255 fits).
+ * Best.  The largest score, among ties the lowest flat index (i (2 ky + 1) + b) (2 kx + 1) + a - through an integer maximum of
+ * (score << 32 | ~flat), so no order shows.  pose_out (n_query, 3): x0 + (double)(a - kx) * res, y0 + (double)(b - ky) * res, th_i;
+ * info_out (n_query, 6) int32: score, i, b, a, n_points, n_inside (the not-far points whose shifted cell is inside the grid at the
+ * best candidate).  A score of 0: nothing matched (the best is then flat index 0).  scores_out (NULL, or (n_query, n_theta, 2 ky + 1,
+ * 2 kx + 1) uint32, at most ROAM_MATCH_MAX_VOLUME entries): the whole score volume.
+ * roam_loop_db_map_match: the same with cloud q = the resident cloud of entry index[q] of a cloud-keeping database; no cloud crosses
+ * the host.  ROAM_E_STATE: the database keeps no clouds.  ROAM_E_ARG, before any device call and with the text naming the argument:
+ * null pointers, a database and a field of different contexts (or not of ctx), an index out of range, and what the clouds entry refuses.
+ * roam_map_match_plan (host only, no context): how a call of n_query queries with this window is cut on a device of cu_count compute
+ * units: one workgroup per (query, angle, block of *rows_out of the 2 ky + 1 shift rows), *n_blk_out blocks - at most 2048 candidates
+ * to a workgroup, fewer rows while fewer than about four workgroups per unit would result, never fewer than fill 256 lanes.  The cut
+ * changes no result.  ROAM_E_ARG: a null pointer, cu_count < 1, n_query or a window that the match refuses.
+ * roam_time_map_match: measurement only (HIP events, two warm launches, `reps` timed): ms[0] the field's build from the uploaded grids
+ * into scratch (the handle's field is untouched), ms[1] the match kernels of this call's window on the handle's field. */
+#define ROAM_MATCH_MAX_RADIUS 8
+#define ROAM_MATCH_MAX_ANGLES 1025
+#define ROAM_MATCH_MAX_SHIFT 128
+#define ROAM_MATCH_MAX_VOLUME (1 << 26)
+typedef struct roam_map_field roam_map_field;
+int32_t roam_map_field_table(double sigma_cells, int32_t radius, uint8_t *table_out /* (2 radius + 1)^2 */);
+int32_t roam_map_field_create(roam_ctx *ctx, double ox, double oy, double res, int32_t W, int32_t H, const uint32_t *hits /* H x W */,
+                              const uint32_t *views /* H x W */, int32_t min_hits, int32_t min_views, int32_t radius,
+                              const uint8_t *table /* (2 radius + 1)^2 */, roam_map_field **field_out);
+int32_t roam_map_field_read(roam_ctx *ctx, roam_map_field *field, uint8_t *out /* H x W */);
+int32_t roam_map_field_destroy(roam_ctx *ctx, roam_map_field *field);
+int32_t roam_map_match_angles(int32_t n_query, const double *priors /* n x 3 */, int32_t n_theta, double step_rad,
+                              double *cs_out /* n x n_theta x 2 */);
+int32_t roam_map_match_plan(int32_t cu_count, int32_t n_query, int32_t n_theta, int32_t kx, int32_t ky, int32_t *rows_out, int32_t *n_blk_out);
+int32_t roam_map_match_clouds(roam_ctx *ctx, roam_map_field *field, int32_t n_query, const double *xy /* total x 2 */,
+                              const int64_t *offsets /* n_query + 1 */, const double *priors /* n_query x 3 */, int32_t n_theta,
+                              double step_rad, int32_t kx, int32_t ky, double *pose_out /* n_query x 3 */,
+                              int32_t *info_out /* n_query x 6 */, uint32_t *scores_out /* NULL or the volume */);
+int32_t roam_loop_db_map_match(roam_ctx *ctx, roam_loop_db *db, roam_map_field *field, int32_t n_query, const int32_t *index,
+                               const double *priors, int32_t n_theta, double step_rad, int32_t kx, int32_t ky, double *pose_out,
+                               int32_t *info_out, uint32_t *scores_out);
+int32_t roam_time_map_match(roam_ctx *ctx, roam_map_field *field, const uint32_t *hits, const uint32_t *views, int32_t min_hits,
+                            int32_t min_views, int32_t radius, const uint8_t *table, int32_t n_query, const double *xy,
+                            const int64_t *offsets, const double *priors, int32_t n_theta, double step_rad, int32_t kx, int32_t ky,
+                            int32_t reps, float *ms /* 2 */);
+
 /* ---- engine: B resident lanes, one scan pair per lane per step ---------------------------
  * Replaces the body of the RawROAMSystem.run loop (RawROAMSystem.py:162-298) minus plotting:
  * a1/a2 ingest+peaks, a3 warp+quantise, pyramid, a7 KLT against the lane's previous

@@ -41,7 +41,13 @@ row, tests/loop_cloud_motion_model.py.  The descriptor and its origin-shifted va
 Global map.  The stored clouds are also what a map is made of: LoopDetector.renderMap takes one pose per entry and bins every entry's
 points in the world frame on the device (csrc/loop_map.hip) -> Mapping.GlobalMap, an occupancy grid (points and distinct keyframes per
 cell) and a thinned list of map points; mapFromGraph(detector, graph) is the step after closeLoops.  A closure moves every pose, so
-the map is rendered again after each; nothing of it is kept in the detector.  The definition is tests/global_map_model.py."""
+the map is rendered again after each; nothing of it is kept in the detector.  The definition is tests/global_map_model.py.
+
+Localisation.  GlobalMap.localizer() turns a rendered map into a resident match field, and LoopDetector.localize(localizer, indices,
+priors) places stored scans in it: correlative scan-to-map matching (csrc/map_match.hip), an exhaustive search over rotations and
+whole-cell shifts around a prior pose that scores every candidate against all the keyframes of the map at once - what corrects a
+drifting pose between keyframes, or a second traversal after a restart, where a scan-context hit plus pairwise ICP only recognises one
+stored place.  Scores are sums of bytes, so the answer is bit-reproducible; the definition is tests/map_match_model.py."""
 import numbers
 
 import numpy as np
@@ -198,6 +204,15 @@ class LoopDetector:
             extent = _ffi.map_plan(b, res) if n else (0.0, 0.0, 1, 1)
         r = self.db.map_render(p, res, extent, minHits, minViews, u, grids)
         return GlobalMap(extent[:2], res, (extent[3], extent[2]), r["hits"], r["views"], r["points"], r["point_hits"], r["point_views"], r["outside"])
+
+    def localize(self, localizer, indices=None, priors=(0.0, 0.0, 0.0), reachM=3.0, reachRad=0.12, stepRad=0.01, volume=False):
+        """Mapping.MapLocalizer.match on the stored clouds (keepClouds) of the entries `indices` (None: the newest), which never leave
+        the device: priors (3,) or (n, 3) rows x, y, theta in the map's frame, the window as there -> the _ffi.MATCH_TABLE rows, with
+        volume=True also the list of score volumes"""
+        if not self.keepClouds:
+            raise ValueError("LoopDetector.localize: the detector keeps no clouds (keepClouds=True)")
+        poses, info, scores = localizer._field.match_db(self.db, indices, priors, localizer.window(reachM, reachRad, stepRad), volume)
+        return (_ffi.match_table(poses, info), list(scores)) if volume else _ffi.match_table(poses, info)
 
     def verify(self, queryIndex, candIndex, candYaw, candOffset=None, **verify):
         """verifyCandidates from the stored clouds: the arguments, keywords and results are verifyCandidates' without `clouds`.

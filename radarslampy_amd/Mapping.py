@@ -83,6 +83,50 @@ class GlobalMap():
         a = np.asarray(xy, np.float64).reshape(-1, 2)
         return np.floor((a - np.array(self.origin)) / self.cellM).astype(np.int64)
 
+    def localizer(self, minHits=1, minViews=1, sigmaCells=1.0, radiusCells=2, ctx=None) -> "MapLocalizer":
+        """The map as something a scan can be placed in -> MapLocalizer: the cells with at least minHits points from at least minViews
+        keyframes, smeared over radiusCells cells with a Gaussian of sigmaCells (a maximum, one byte per cell), resident on the device.
+        ValueError for a map rendered with grids=False, and before the device is touched for a bad argument"""
+        if self.hits is None or self.views is None:
+            raise ValueError("GlobalMap.localizer: the map was rendered with grids=False; it needs hits and views")
+        return MapLocalizer(self, minHits, minViews, sigmaCells, radiusCells, ctx)
+
+
+class MapLocalizer():
+    """Correlative scan-to-map matching (Olson 2009) against a GlobalMap: an exhaustive search over a window of rotations and
+    whole-cell translations around a prior pose, every candidate scored by the sum of the smeared occupancy under the scan's points
+    (csrc/map_match.hip; the definition is include/roam_abi.h's "map matching" and tests/map_match_model.py).  The score is a sum of
+    bytes, so the result is bit-reproducible.  Made by GlobalMap.localizer; origin, cellM and shape are the map's."""
+
+    def __init__(self, globalMap, minHits=1, minViews=1, sigmaCells=1.0, radiusCells=2, ctx=None) -> None:
+        from . import _ffi
+        self.origin, self.cellM, self.shape = globalMap.origin, globalMap.cellM, globalMap.shape
+        self._field = _ffi.MapField(ctx, globalMap.hits, globalMap.views, globalMap.origin, globalMap.cellM, minHits, minViews, sigmaCells, radiusCells)
+
+    def close(self) -> None:
+        self._field.close()
+
+    def field(self) -> np.ndarray:
+        """-> (H, W) uint8: 255 on an occupied cell, falling off to 0 beyond radiusCells"""
+        return self._field.read()
+
+    def window(self, reachM=3.0, reachRad=0.12, stepRad=0.01):
+        """-> (n_theta, step_rad, kx, ky): the angles and the cells of shift to either side that match searches"""
+        from . import _ffi
+        return _ffi.map_match_window(self.cellM, reachM, reachRad, stepRad)
+
+    def match(self, clouds, priors, reachM=3.0, reachRad=0.12, stepRad=0.01, volume=False):
+        """clouds: one (n, 2) cloud or a list of them, metres in the sensor frame (LoopClosure.polarIndToLocalMetres), at most 8192
+        points each; priors (3,) or (n, 3) rows x, y, theta in the map's frame.  Searched: the angles theta0 + j stepRad with
+        |j| <= floor(reachRad / stepRad + 1e-9) and the shifts of whole cells within reachM (a scalar, or (x, y)) ->
+        a structured array of _ffi.MATCH_TABLE rows: x, y, theta (the best candidate), score, fraction = score / (255 nPoints),
+        nPoints, nInside (the points inside the grid at the best candidate), i, b, a (its indices in the window) and found
+        (score > 0).  Among equal scores the lowest angle, then the lowest y, then the lowest x wins.  volume=True: also the list of
+        the queries' score volumes, (n_theta, 2 ky + 1, 2 kx + 1) uint32 each"""
+        from . import _ffi
+        poses, info, scores = self._field.match_clouds(clouds, priors, self.window(reachM, reachRad, stepRad), volume)
+        return (_ffi.match_table(poses, info), list(scores)) if volume else _ffi.match_table(poses, info)
+
 
 class DeviceMap():
     """the keyframes of one engine lane, resident in HBM (roam_engine_map_*).  Read-only view with the

@@ -83,6 +83,12 @@ LOOP_MAX_K = 32                         # roam_abi.h ROAM_LOOP_MAX_K
 LOOP_MAX_OFFSETS = 48                   # roam_abi.h ROAM_LOOP_MAX_OFFSETS
 LOOP_DB_BYTES = 2000 << 20              # a database, and the device scratch of one launch
 MAP_MAX_CELLS = 1 << 26                 # roam_abi.h ROAM_MAP_MAX_CELLS: the cells of a global map's grid
+# map matching: roam_abi.h ROAM_MATCH_MAX_RADIUS, _ANGLES, _SHIFT and _VOLUME (tests/test_map_match_cpu.py holds them against the header)
+MAP_MATCH_MAX_RADIUS, MAP_MATCH_MAX_ANGLES, MAP_MATCH_MAX_SHIFT, MAP_MATCH_MAX_VOLUME = 8, 1025, 128, 1 << 26
+MAP_MATCH_MAX_QUERIES = 65535           # queries of one roam_map_match_clouds / roam_loop_db_map_match call
+# MapLocalizer.match's rows, one per query: what roam_map_match_clouds returns in pose_out and info_out, and what follows from it
+MATCH_TABLE = np.dtype([("x", np.float64), ("y", np.float64), ("theta", np.float64), ("score", np.uint32), ("fraction", np.float64),
+                        ("nPoints", np.int32), ("nInside", np.int32), ("i", np.int32), ("b", np.int32), ("a", np.int32), ("found", np.bool_)])
 
 
 PRIOR_RECORD = np.dtype([("out6", np.float64, (6,)), ("affine", np.float32, (2, 3)), ("source", np.uint8)])     # Engine.step_prior's rows
@@ -189,6 +195,17 @@ _SIGS = {
                                             _vp, _vp, _vp, _vp, C.c_int32, _P(C.c_int32), _P(C.c_int64)]),
     "roam_time_loop_db_map": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, _vp]),
+    "roam_map_field_table": (C.c_int32, [C.c_double, C.c_int32, _vp]),
+    "roam_map_field_create": (C.c_int32, [_vp, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                          _P(_vp)]),
+    "roam_map_field_read": (C.c_int32, [_vp, _vp, _vp]),
+    "roam_map_field_destroy": (C.c_int32, [_vp, _vp]),
+    "roam_map_match_angles": (C.c_int32, [C.c_int32, _vp, C.c_int32, C.c_double, _vp]),
+    "roam_map_match_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "roam_map_match_clouds": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "roam_loop_db_map_match": (C.c_int32, [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "roam_time_map_match": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_double,
+                                        C.c_int32, C.c_int32, C.c_int32, _vp]),
     "roam_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), _vp, _vp]),
     "roam_time_icp2d_batch": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _P(IcpOpts), C.c_int32, _P(C.c_float)]),
     "roam_engine_create": (C.c_int32, [_vp, _P(EngineCfg)]),

@@ -5,7 +5,8 @@ import numbers
 import numpy as np
 
 from ._abi import (FMT_MAX_COLS, FMT_MAX_R, FMT_MAX_ROWS, FMT_MIN_R, ICP_DEFAULTS, ICP_ITERATION_LIMIT, ICP_MAX_COORD, ICP_MAX_PAIRS,
-                   ICP_MAX_POINTS, KLT_MAX_GUESS, LOOP_DB_BYTES, LOOP_MAX_K, LOOP_MAX_OFFSETS, MAP_MAX_CELLS, PHASE_CORRELATE_MAX,
+                   ICP_MAX_POINTS, KLT_MAX_GUESS, LOOP_DB_BYTES, LOOP_MAX_K, LOOP_MAX_OFFSETS, MAP_MATCH_MAX_ANGLES, MAP_MATCH_MAX_QUERIES,
+                   MAP_MATCH_MAX_RADIUS, MAP_MATCH_MAX_SHIFT, MAP_MATCH_MAX_VOLUME, MAP_MAX_CELLS, PHASE_CORRELATE_MAX,
                    POSE_GRAPH_MAX_GRAPHS, POSE_GRAPH_MAX_ITERATIONS, POSE_GRAPH_MAX_TRIALS, POSE_GRAPH_MAX_VERTICES, PRIOR_MAX_LINEAR,
                    SCAN_CONTEXT_MAX_ROWS, WARP_AFFINE_MAX_COORD, WARP_AFFINE_MAX_SIDE, AutoPriorCfg, IcpOpts, PoseGraphOpts)
 
@@ -474,6 +475,129 @@ def loop_map_args(count, poses, use=None, res=0.5, extent=None, min_hits=1, min_
         if not _int_in(v, 1, 2 ** 31 - 1):
             raise ValueError(f"global map: {name} an integer >= 1, not {v!r}")
     return p, use, float(res), extent, int(min_hits), int(min_views)
+
+
+def _real(v):
+    return isinstance(v, numbers.Real) and not isinstance(v, bool) and np.isfinite(v)
+
+
+def map_field_table_args(sigma_cells, radius_cells):
+    """the checks of map_field_table before any library call -> (sigma, radius)"""
+    if not (_real(sigma_cells) and sigma_cells > 0):
+        raise ValueError(f"map field: sigmaCells finite and > 0, not {sigma_cells!r}")
+    if not _int_in(radius_cells, 0, MAP_MATCH_MAX_RADIUS):
+        raise ValueError(f"map field: radiusCells an integer in [0, {MAP_MATCH_MAX_RADIUS}], not {radius_cells!r}")
+    return float(sigma_cells), int(radius_cells)
+
+
+def map_field_args(hits, views, origin, cell_m, min_hits=1, min_views=1, radius=2, table=None):
+    """the checks of MapField before any library call -> (hits, views (H, W) uint32 C order, ox, oy, res, W, H, min_hits, min_views,
+    radius, table (2 radius + 1, 2 radius + 1) uint8 or None when none was given)"""
+    if hits is None or views is None:
+        raise ValueError("map field: a map rendered with its grids (grids=True), not hits / views = None")
+    h, v = np.asarray(hits), np.asarray(views)
+    if h.dtype.kind not in "iu" or v.dtype.kind not in "iu" or h.ndim != 2 or h.shape != v.shape or h.size == 0:
+        raise ValueError(f"map field: hits and views two (H, W) integer grids of one shape, not {h.dtype} {h.shape} and {v.dtype} {v.shape}")
+    if h.size > MAP_MAX_CELLS:
+        raise ValueError(f"map field: W H = {h.size} cells, more than {MAP_MAX_CELLS}")
+    if (h.dtype != np.uint32 and (h.min() < 0 or h.max() >= 2 ** 32)) or (v.dtype != np.uint32 and (v.min() < 0 or v.max() >= 2 ** 32)):
+        raise ValueError("map field: hits and views of counts in [0, 2^32)")
+    if len(origin) != 2 or not all(_real(o) for o in origin):
+        raise ValueError(f"map field: origin (ox, oy) finite, not {origin!r}")
+    if not (_real(cell_m) and cell_m > 0):
+        raise ValueError(f"map field: cellM finite and > 0, not {cell_m!r}")
+    for name, t in (("minHits", min_hits), ("minViews", min_views)):
+        if not _int_in(t, 1, 2 ** 31 - 1):
+            raise ValueError(f"map field: {name} an integer >= 1, not {t!r}")
+    if not _int_in(radius, 0, MAP_MATCH_MAX_RADIUS):
+        raise ValueError(f"map field: radiusCells an integer in [0, {MAP_MATCH_MAX_RADIUS}], not {radius!r}")
+    if table is not None:
+        t = np.asarray(table)
+        if t.dtype != np.uint8 or t.shape != (2 * radius + 1, 2 * radius + 1):
+            raise ValueError(f"map field: table ({2 * radius + 1}, {2 * radius + 1}) uint8, not {t.dtype} {t.shape}")
+        table = np.ascontiguousarray(t)
+    H, W = h.shape
+    return (np.ascontiguousarray(h, np.uint32), np.ascontiguousarray(v, np.uint32), float(origin[0]), float(origin[1]), float(cell_m), int(W), int(H),
+            int(min_hits), int(min_views), int(radius), table)
+
+
+def map_match_window(cell_m, reach_m=3.0, reach_rad=0.12, step_rad=0.01):
+    """MapLocalizer.match's window in metres and radians -> (n_theta, step_rad, kx, ky): k = floor(reach / cellM + 1e-9) cells to either
+    side, reachM a scalar or (x, y); n_theta = 2 floor(reachRad / stepRad + 1e-9) + 1 (reachRad = 0: the prior's angle alone).
+    ValueError: a reach that is not finite or < 0, more than MAP_MATCH_MAX_SHIFT cells or MAP_MATCH_MAX_ANGLES angles, stepRad not
+    finite or <= 0 with a reachRad > 0"""
+    rx, ry = (reach_m, reach_m) if isinstance(reach_m, numbers.Real) else (tuple(reach_m) if len(reach_m) == 2 else (None, None))
+    if not (_real(rx) and _real(ry) and rx >= 0 and ry >= 0):
+        raise ValueError(f"map match: reachM a finite scalar or (x, y) >= 0, not {reach_m!r}")
+    kx, ky = int(np.floor(rx / cell_m + 1e-9)), int(np.floor(ry / cell_m + 1e-9))
+    if kx > MAP_MATCH_MAX_SHIFT or ky > MAP_MATCH_MAX_SHIFT:
+        raise ValueError(f"map match: reachM {reach_m!r} at cellM {cell_m} is ({kx}, {ky}) cells, more than {MAP_MATCH_MAX_SHIFT}")
+    if not (_real(reach_rad) and reach_rad >= 0):
+        raise ValueError(f"map match: reachRad finite and >= 0, not {reach_rad!r}")
+    if not (_real(step_rad) and step_rad >= 0) or (step_rad == 0 and reach_rad > 0):
+        raise ValueError(f"map match: stepRad finite and > 0, not {step_rad!r}")
+    half = int(np.floor(reach_rad / step_rad + 1e-9)) if reach_rad > 0 else 0
+    if 2 * half + 1 > MAP_MATCH_MAX_ANGLES:
+        raise ValueError(f"map match: reachRad {reach_rad} at stepRad {step_rad} is {2 * half + 1} angles, more than {MAP_MATCH_MAX_ANGLES}")
+    return 2 * half + 1, float(step_rad), kx, ky
+
+
+def map_match_priors(priors, n, window, volume=False):
+    """priors (3,) for every query or (n, 3) rows x, y, theta, and the raw window (n_theta, step_rad, kx, ky) -> priors (n, 3) float64"""
+    n_theta, step_rad, kx, ky = window
+    if not (_int_in(n_theta, 1, MAP_MATCH_MAX_ANGLES) and n_theta % 2 == 1):
+        raise ValueError(f"map match: n_theta an odd integer in [1, {MAP_MATCH_MAX_ANGLES}], not {n_theta!r}")
+    if not (_real(step_rad) and step_rad >= 0):
+        raise ValueError(f"map match: step_rad finite and >= 0, not {step_rad!r}")
+    for name, k in (("kx", kx), ("ky", ky)):
+        if not _int_in(k, 0, MAP_MATCH_MAX_SHIFT):
+            raise ValueError(f"map match: {name} an integer in [0, {MAP_MATCH_MAX_SHIFT}], not {k!r}")
+    if not 1 <= n <= MAP_MATCH_MAX_QUERIES:
+        raise ValueError(f"map match: between 1 and {MAP_MATCH_MAX_QUERIES} queries, not {n}")
+    p = np.asarray(priors)
+    if p.dtype.kind not in "fiu":
+        raise ValueError(f"map match: priors of numbers, not {p.dtype}")
+    if p.shape == (3,):
+        p = np.tile(p, (n, 1))
+    if p.shape != (n, 3):
+        raise ValueError(f"map match: priors (3,) or ({n}, 3) rows x, y, theta - one per query - not {p.shape}")
+    p = np.ascontiguousarray(p, np.float64)
+    reach = float((n_theta - 1) // 2) * step_rad
+    if not (np.all(np.isfinite(p)) and np.all(np.abs(p[:, :2]) <= ICP_MAX_COORD) and np.all(np.isfinite(p[:, 2] + reach))
+            and np.all(np.isfinite(p[:, 2] - reach))):
+        raise ValueError(f"map match: priors with an entry that is not finite or beyond {ICP_MAX_COORD:g} m")
+    if volume and n * n_theta * (2 * ky + 1) * (2 * kx + 1) > MAP_MATCH_MAX_VOLUME:
+        raise ValueError(f"map match: a score volume of {n * n_theta * (2 * ky + 1) * (2 * kx + 1)} entries, more than {MAP_MATCH_MAX_VOLUME}: "
+                         "fewer queries per call, or volume=False")
+    return p
+
+
+def map_match_clouds(clouds):
+    """one (n, 2) cloud or a sequence of them, metres in the sensor frame -> (xy (total, 2) float64, offsets (n_query + 1,) int64).
+    ValueError as loop_cloud_points, at most ICP_MAX_POINTS points each"""
+    if isinstance(clouds, np.ndarray) and clouds.ndim == 2:
+        clouds = [clouds]
+    parts = [loop_cloud_points(c, ICP_MAX_POINTS) for c in clouds]
+    if not parts:
+        raise ValueError("map match: no cloud")
+    offsets = np.zeros(len(parts) + 1, np.int64)
+    np.cumsum([len(c) for c in parts], out=offsets[1:])
+    return np.ascontiguousarray(np.concatenate(parts, axis=0)), offsets
+
+
+def map_match_indices(count, indices):
+    """entries of a loop database as queries (None: the newest) -> (n,) int32.  ValueError: none, or one outside [0, count)"""
+    if indices is None:
+        if count < 1:
+            raise ValueError("map match: an empty database has no newest entry")
+        return np.array([count - 1], np.int32)
+    a = np.asarray(indices)
+    if a.dtype.kind not in "iu" or a.size == 0:
+        raise ValueError(f"map match: indices of at least one integer, not {a.dtype} {a.shape}")
+    a = a.ravel()
+    if a.min() < 0 or a.max() >= count:
+        raise ValueError(f"map match: entry indices in [0, {count})")
+    return np.ascontiguousarray(a, np.int32)
 
 
 def icp2d_opts(opts=None):

@@ -11,7 +11,8 @@ import numpy as np
 
 from ._abi import (ABI_SYMBOLS, COMM_ID_BYTES, FMT_MAX_COLS, FMT_MAX_R, FMT_MAX_ROWS, FMT_MIN_R, ICP_DEFAULTS, ICP_FEW_PAIRS,
                    ICP_ITERATION_LIMIT, ICP_MAX_COORD, ICP_MAX_ITERATIONS, ICP_MAX_PAIRS, ICP_MAX_POINTS, ICP_OK, ICP_STATS, KLT_MAX_GUESS,
-                   LOOP_DB_BYTES, LOOP_MAX_K, LOOP_MAX_OFFSETS, MAP_MAX_CELLS, MAX_FEATURES, PHASE_CORRELATE_MAX, POSE_GRAPH_CHUNK_BYTES,
+                   LOOP_DB_BYTES, LOOP_MAX_K, LOOP_MAX_OFFSETS, MAP_MATCH_MAX_ANGLES, MAP_MATCH_MAX_QUERIES, MAP_MATCH_MAX_RADIUS,
+                   MAP_MATCH_MAX_SHIFT, MAP_MATCH_MAX_VOLUME, MAP_MAX_CELLS, MATCH_TABLE, MAX_FEATURES, PHASE_CORRELATE_MAX, POSE_GRAPH_CHUNK_BYTES,
                    POSE_GRAPH_MAX_GRAPHS, POSE_GRAPH_MAX_ITERATIONS, POSE_GRAPH_MAX_TRIALS, POSE_GRAPH_MAX_VERTICES, POSE_GRAPH_STATS,
                    PRIOR_MAX_LINEAR, PRIOR_RECORD, ROAM_E_ARG, ROAM_E_CAPACITY, ROAM_E_HIP, ROAM_E_NODEVICE, ROAM_E_STATE, ROAM_OK,
                    SCAN_CONTEXT_MAX_CLIP, SCAN_CONTEXT_MAX_RINGS, SCAN_CONTEXT_MAX_ROWS, SCAN_CONTEXT_MAX_SECTORS, STEP_NEW_SEQUENCE,
@@ -21,6 +22,7 @@ from ._abi import (ABI_SYMBOLS, COMM_ID_BYTES, FMT_MAX_COLS, FMT_MAX_R, FMT_MAX_
 from ._args import (_batch_operands, _batch_strides, _f32_rows_in_place, _int_in, auto_prior_args, fmt_cart_radius, fmt_clip_radius,
                     fmt_register_batch_args, fmt_rotation_batch_args, icp2d_args, icp2d_opts, invert_affine, klt_flow_args,
                     loop_cloud_args, loop_cloud_points, loop_map_args, loop_motion_args, loop_offsets_args, loop_query_args, loop_verify_args,
+                    map_field_args, map_field_table_args, map_match_clouds, map_match_indices, map_match_priors, map_match_window,
                     motion_prior_args, peak_conditions, phase_correlate_args, pose_graph_args, scan_context_floor, warp_affine_args)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -194,6 +196,41 @@ def map_plan(bounds, res):
     if rc != ROAM_OK:
         raise ValueError(f"global map: finite bounds with min <= max and a res finite, > 0 and not below 2^-50 of them, not {b.tolist()} and {res!r}")
     return ox.value, oy.value, W.value, H.value
+
+
+def map_field_table(sigma_cells=1.0, radius_cells=2):
+    """roam_map_field_table, host code only (no device, no context): the smear of a match field -> (2 r + 1, 2 r + 1) uint8,
+    T[dv + r][du + r] = floor(255 exp(-(du du + dv dv) / (2 sigma sigma)) + 0.5) by the host's libm.  ValueError: sigma not finite or
+    <= 0, radius no integer in [0, MAP_MATCH_MAX_RADIUS]"""
+    sigma, r = map_field_table_args(sigma_cells, radius_cells)
+    t = np.empty((2 * r + 1, 2 * r + 1), np.uint8)
+    if load_library().roam_map_field_table(sigma, r, _ptr(t)) != ROAM_OK:
+        raise ValueError(f"map field: roam_map_field_table refused sigma {sigma}, radius {r}")
+    return t
+
+
+def map_match_angles(priors, n_theta, step_rad):
+    """roam_map_match_angles, host code only: priors (3,) or (n, 3) rows x, y, theta -> (n, n_theta, 2) float64 rows (cos th_i, sin th_i)
+    by the host's libm, th_i = th0 + float(i - (n_theta - 1) / 2) * step_rad - what a match multiplies with"""
+    n = 1 if np.shape(priors) == (3,) else len(priors)
+    p = map_match_priors(priors, n, (n_theta, step_rad, 0, 0))
+    cs = np.empty((n, int(n_theta), 2), np.float64)
+    if load_library().roam_map_match_angles(n, _ptr(p), int(n_theta), float(step_rad), _ptr(cs)) != ROAM_OK:
+        raise ValueError(f"map match: roam_map_match_angles refused n_theta {n_theta}, step_rad {step_rad}")
+    return cs
+
+
+def map_match_plan(cu_count, n_query, window):
+    """roam_map_match_plan, host code only: how a match of n_query queries over the raw window (n_theta, step_rad, kx, ky) is cut on a
+    device of cu_count compute units -> (rows of shift per workgroup, blocks of rows): one workgroup per query, angle and block.  The
+    cut changes no result"""
+    p = map_match_priors((0.0, 0.0, 0.0), n_query, window)
+    if not _int_in(cu_count, 1, 2 ** 31 - 1):
+        raise ValueError(f"map match: cu_count an integer >= 1, not {cu_count!r}")
+    rows, n_blk = C.c_int32(0), C.c_int32(0)
+    if load_library().roam_map_match_plan(int(cu_count), len(p), int(window[0]), int(window[2]), int(window[3]), C.byref(rows), C.byref(n_blk)) != ROAM_OK:
+        raise ValueError(f"map match: roam_map_match_plan refused {n_query} queries, window {window!r}")
+    return rows.value, n_blk.value
 
 
 class Context:
@@ -960,6 +997,93 @@ class LoopDb:
         self.ctx.check(self.ctx.lib.roam_time_loop_db_query(self.ctx.h, self.h, len(q), _ptr(q), _ptr(m), int(k), float(max_distance), int(reps),
                                                             C.byref(d_ms), C.byref(s_ms)))
         return float(d_ms.value), float(s_ms.value)
+
+
+def _match_outputs(n, window, volume):
+    n_theta, _, kx, ky = window
+    return (np.empty((n, 3), np.float64), np.empty((n, 6), np.int32),
+            np.empty((n, n_theta, 2 * ky + 1, 2 * kx + 1), np.uint32) if volume else None)
+
+
+class MapField:
+    """The match field of a rendered global map, resident in HBM (roam_map_field): one byte per cell, the occupied cells (hits >=
+    min_hits and views >= min_views) smeared with `table` (None: map_field_table(sigma_cells, radius)) by a maximum.  Bound to the
+    context it was made on (None: the default context, asked for after the arguments have passed)."""
+
+    def __init__(self, ctx, hits, views, origin, cell_m, min_hits=1, min_views=1, sigma_cells=1.0, radius=2, table=None):
+        h, v, ox, oy, res, W, H, min_hits, min_views, radius, table = map_field_args(hits, views, origin, cell_m, min_hits, min_views, radius, table)
+        if table is None:
+            table = map_field_table(sigma_cells, radius)
+        ctx = ctx or default_context()
+        self.ctx, self.origin, self.cell_m, self.shape, self.radius, self.table = ctx, (ox, oy), res, (H, W), radius, table
+        f = _vp()
+        ctx.check(ctx.lib.roam_map_field_create(ctx.h, ox, oy, res, W, H, _ptr(h), _ptr(v), min_hits, min_views, radius, _ptr(table), C.byref(f)))
+        self.h = f
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.roam_map_field_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def read(self):
+        """-> the field, (H, W) uint8"""
+        out = np.empty(self.shape, np.uint8)
+        self.ctx.check(self.ctx.lib.roam_map_field_read(self.ctx.h, self.h, _ptr(out)))
+        return out
+
+    def match_clouds(self, clouds, priors, window, volume=False):
+        """roam_map_match_clouds: clouds (one (n, 2) array or a sequence, metres in the sensor frame) at priors ((3,) or (n, 3) rows x, y,
+        theta) over the raw window (n_theta, step_rad, kx, ky) -> (poses (n, 3) float64, info (n, 6) int32: score, i, b, a, n_points,
+        n_inside, the score volume (n, n_theta, 2 ky + 1, 2 kx + 1) uint32 or None)"""
+        xy, offsets = map_match_clouds(clouds)
+        p = map_match_priors(priors, len(offsets) - 1, window, volume)
+        out = _match_outputs(len(p), window, volume)
+        self.ctx.check(self.ctx.lib.roam_map_match_clouds(self.ctx.h, self.h, len(p), _ptr(xy), _ptr(offsets), _ptr(p), int(window[0]), float(window[1]),
+                                                          int(window[2]), int(window[3]), *map(_ptr, out)))
+        return out
+
+    def match_db(self, db, indices, priors, window, volume=False):
+        """roam_loop_db_map_match: the same with the resident clouds of the entries `indices` (None: the newest) of a LoopDb that keeps
+        clouds; no cloud crosses the host"""
+        db._needs_clouds()
+        if db.ctx is not self.ctx:
+            raise ValueError("map match: the database and the field were made on different contexts")
+        idx = map_match_indices(len(db), indices)
+        p = map_match_priors(priors, len(idx), window, volume)
+        out = _match_outputs(len(p), window, volume)
+        self.ctx.check(self.ctx.lib.roam_loop_db_map_match(self.ctx.h, db.h, self.h, len(p), _ptr(idx), _ptr(p), int(window[0]), float(window[1]),
+                                                           int(window[2]), int(window[3]), *map(_ptr, out)))
+        return out
+
+    def time_match(self, hits, views, clouds, priors, window, min_hits=1, min_views=1, reps=5):
+        """(field build ms, match ms) per launch (roam_time_map_match): the build of this field from hits / views into scratch, and the
+        match kernels of this call on the resident field"""
+        h, v, _, _, _, W, H, min_hits, min_views, _, _ = map_field_args(hits, views, self.origin, self.cell_m, min_hits, min_views, self.radius)
+        if (H, W) != self.shape:
+            raise ValueError(f"map field: hits and views {(H, W)}, the field is {self.shape}")
+        xy, offsets = map_match_clouds(clouds)
+        p = map_match_priors(priors, len(offsets) - 1, window)
+        ms = (C.c_float * 2)()
+        self.ctx.check(self.ctx.lib.roam_time_map_match(self.ctx.h, self.h, _ptr(h), _ptr(v), min_hits, min_views, self.radius, _ptr(self.table), len(p),
+                                                        _ptr(xy), _ptr(offsets), _ptr(p), int(window[0]), float(window[1]), int(window[2]),
+                                                        int(window[3]), int(reps), ms))
+        return tuple(float(t) for t in ms)
+
+
+def match_table(poses, info):
+    """the two outputs of a match -> MATCH_TABLE rows: fraction = score / (255 n_points) (0 without points), found = score > 0"""
+    t = np.zeros(len(poses), MATCH_TABLE)
+    t["x"], t["y"], t["theta"] = poses[:, 0], poses[:, 1], poses[:, 2]
+    t["score"], t["i"], t["b"], t["a"], t["nPoints"], t["nInside"] = (info[:, k] for k in range(6))
+    t["fraction"] = np.where(info[:, 4] > 0, info[:, 0] / (255.0 * np.maximum(info[:, 4], 1)), 0.0)
+    t["found"] = info[:, 0] > 0
+    return t
 
 
 def default_context(device_id: int = None) -> Context:

@@ -18,11 +18,15 @@
 //                      (map_count_kernel, map_scan_kernel, map_write_kernel); roam_map_pose_table, roam_map_plan,
 //                      roam_loop_db_map_bounds, roam_loop_db_map_render, roam_time_loop_db_map.  It reads the database and writes
 //                      scratch of the context only; no other unit calls into it
+//   map_match.hip      a scan localised in a rendered map (correlative matching): the resident match field (roam_map_field),
+//                      mm_field_kernel, mm_match_kernel, mm_finish_kernel; roam_map_field_*, roam_map_match_angles, roam_map_match_plan,
+//                      roam_map_match_clouds, roam_loop_db_map_match, roam_time_map_match (map_match.h: the tables and the argument
+//                      checks, host only).  It reads the database's clouds and the grids a render returned; it calls no other unit
 //   icp.hip            the ICP of a pair of stored clouds (icp2d_store_kernel), which loop_verify.hip launches
 // engine_lanes.hip describes the engine's pool (LoopPool) and calls the record entries.  The reference has no place recognition (a
 // commented-out "import m2dp" at Mapping.py:7 and an unused Keyframe.pointCloud at :61-62), so parity is unpinned: the contracts are
-// tests/scan_context_model.py, tests/loop_cloud_model.py, tests/loop_cloud_motion_model.py, tests/scan_context_offset_model.py and
-// tests/global_map_model.py.
+// tests/scan_context_model.py, tests/loop_cloud_model.py, tests/loop_cloud_motion_model.py, tests/scan_context_offset_model.py,
+// tests/global_map_model.py and tests/map_match_model.py.
 #pragma once
 #include "roam_internal.h"
 #include <vector>
@@ -39,6 +43,7 @@
 #define SC_MAX_ROWS 65536
 
 struct roam_loop_db {
+    roam_ctx *owner = nullptr;   // the context it was created on: its allocations live on that context's device (map_match.hip asks)
     int S = 0, R = 0, Rp = 0, capacity = 0, count = 0;
     float *desc = nullptr;       // capacity x S x R
     double *nrm = nullptr;       // capacity x S x Rp: normalised columns, zero for an invalid sector and in the padding

@@ -35,6 +35,7 @@ extern "C" int32_t roam_loop_db_create(roam_ctx *ctx, int32_t capacity, int32_t 
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     roam_loop_db *db = new roam_loop_db;
+    db->owner = ctx;
     db->S = sectors; db->R = rings; db->Rp = Rp; db->capacity = capacity;
     const size_t rows = (size_t)capacity * sectors;
     if (hipMalloc(&db->desc, sizeof(float) * rows * rings) != hipSuccess || hipMalloc(&db->nrm, sizeof(double) * rows * Rp) != hipSuccess ||
